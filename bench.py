@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — device-resident FEC encode+decode throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2c3|c4] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...
 
@@ -20,9 +20,17 @@ Multi-GPU: one process per GPU, each with its own contiguous range of the global
 stream; no data-path collective (groups are independent), a barrier and a MAX
 all-reduce of the elapsed time only.  scaling = "weak".
 
-Prints ONE JSON line on rank 0.  Extra keys: per-kernel timings ("kernels"), the HBM
-roofline of the dominant kernel ("roofline") and the CPU baseline ("cpu_baseline",
-rank 0 at N=1 only; the oracle restatement timed on this host).
+Prints ONE JSON line on rank 0.  A plain run sets up, runs the W untimed and K timed steps and
+prints the headline (value, ms_per_step) with the in-step kernel times ("kernels").  --full adds
+everything that takes runs of its own: the round-trip check before timing ("verified"), each
+kernel alone and the other decode API ("kernels.*.isolated", "other_api"), the HBM roofline of
+the dominant kernel ("roofline"), the other multi-GPU configs at N > 1 (--legs), and at N = 1 the
+CPU baseline ("cpu_baseline", the oracle restatement timed on this host) and "call_site".
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last step left in the
+caller's buffers, for a fixed seeded sample of groups, as DIR/<name>.npy (float32): "parity",
+and "rebuilt" / "data" by decode API (dump_outputs).  Inputs are seeded, so two builds run
+with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -630,6 +638,60 @@ def load_pmc_traffic(config: str, workload: dict, path=None, sha: str | None = N
     return pmc, f"{name} (rocprofv3 PMC on this build, lib_sha256 {pmc['lib_sha256'][:16]}, same workload)"
 
 
+DUMP_BUDGET_BYTES = 48_000_000   # all of a run's .npy files together (float32), under 64 MB
+
+
+def dump_sample(G: int, arrays: int, row_bytes: int, seed: int = SEED + 11):
+    """The groups a dump keeps: all of them when `arrays` float32 arrays of row_bytes per group
+    fit the budget, else a seeded sample (ascending), the same for every run of the same shape."""
+    import numpy as np
+    n = max(1, DUMP_BUDGET_BYTES // (4 * arrays * row_bytes))
+    if n >= G:
+        return np.arange(G, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(G, size=n, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, cfg: dict, G: int, api: str, data, parity, rebuilt, row_start, masks_h) -> dict:
+    """--dump-outputs: what the last timed step left in the caller's buffers, for dump_sample()'s
+    groups, one float32 .npy per buffer (byte values 0..255):
+      parity   [n, r, P]  the encode's repair rows;
+      rebuilt  [n, r, P]  the recover APIs' rebuilt packets, slot m = the group's m-th lost data
+                          shard (the packed API's rows gathered through its row starts); slots
+                          the call leaves unwritten (beyond the group's lost data shards, or a
+                          group past recovery) are 0;
+      data     [n, k, P]  the in-place API's data after the rebuild.
+    Returns {name: shape} (the line's `dumped`)."""
+    import numpy as np
+    import torch
+    k, r, P = cfg["k"], cfg["r"], cfg["P"]
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = 2 if cfg["decode"] else 1
+    sample = dump_sample(G, arrays, (k if cfg["decode"] and api == "in-place" else r) * P)
+    idx = torch.from_numpy(sample).to(parity.device)
+    outs = {"parity": parity.view(G, r, P)[idx]}
+    if cfg["decode"] and api == "in-place":
+        outs["data"] = data.view(G, k, P)[idx]
+    elif cfg["decode"]:
+        m = masks_h[sample]
+        e = _popcount(m & np.uint64((1 << k) - 1))
+        alive = r - _popcount((m >> np.uint64(k)) & np.uint64((1 << r) - 1))
+        e[e > alive] = 0                                        # past recovery: nothing rebuilt
+        written = torch.from_numpy(np.arange(r)[None, :] < e[:, None]).to(parity.device)
+        if api == "packed":
+            rows = row_start[idx].to(torch.int64).view(-1, 1) + torch.arange(r, device=parity.device).view(1, r)
+            got = rebuilt.view(-1, P)[torch.where(written, rows, torch.zeros_like(rows))]
+        else:
+            got = rebuilt.view(G, r, P)[idx]
+        outs["rebuilt"] = got * written.view(-1, r, 1).to(torch.uint8)
+    shapes = {}
+    for name, t in outs.items():
+        a = t.cpu().numpy().astype(np.float32)
+        np.save(out_dir / f"{name}.npy", a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 # ----------------------------------------------------------------------------- main
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -638,6 +700,13 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c2c3", choices=sorted(CONFIGS))
     ap.add_argument("--groups", type=int, default=0, help="groups per GPU (default: the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the round-trip check before timing, each "
+                         "kernel alone, the other decode API, the roofline, the legs (N > 1), the CPU baseline "
+                         "and call_site (N = 1); the --no-* switches and --legs narrow it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs (a fixed seeded sample of groups, "
+                         "float32) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--loss", type=float, default=None,
                     help="iid per-shard loss probability (c5; 0.05 = mobile profile)")
@@ -661,7 +730,7 @@ def parse_args(argv=None):
     ap.add_argument("--legs", default="auto", choices=("auto", "on", "off"),
                     help="after the headline, measure the other multi-GPU BASELINE configs in the same ranks: "
                          "C4 (k=20 r=5 encode) and C5 (satellite loss, device-resident and host-resident with "
-                         "H2D/D2H); auto = on when N > 1")
+                         "H2D/D2H); auto = on when N > 1; part of --full")
     ap.add_argument("--leg-groups", type=int, default=0, help="groups per GPU of the legs (default: each config's)")
     ap.add_argument("--e2e-groups", type=int, default=0,
                     help="groups per rank of the host-resident legs (default: all at N = 1, 250k per rank at N > 1, "
@@ -670,7 +739,10 @@ def parse_args(argv=None):
                     help="skip the call_site section (the reference's one-group-per-call site; N = 1, runs with "
                          "the cpu_baseline leg, so --no-cpu-baseline skips it too)")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # The other multi-GPU BASELINE lines, measured after the headline when N > 1 (--legs): C4
@@ -680,7 +752,7 @@ LEGS = (("c4", "c4", False), ("c5_e2e", "c5", True))
 
 
 def legs_enabled(args, world: int) -> bool:
-    return args.legs == "on" or (args.legs == "auto" and world > 1)
+    return args.full and (args.legs == "on" or (args.legs == "auto" and world > 1))
 
 
 def leg_section(res: dict) -> dict:
@@ -756,9 +828,12 @@ class Bench:
         self.copy = None  # the box's copy rate (measured once per process)
 
     def measure(self, config: str, cfg: dict, G: int, steps: int, warmup: int, api: str, verify: bool,
-                other_api: bool, e2e: bool) -> dict:
-        """One workload on this rank: verify, W untimed + K timed steps between barriers, per-kernel
-        timings, roofline.  Every rank calls it with the same arguments (collectives line up)."""
+                other_api: bool, e2e: bool, full: bool = True, dump_dir=None) -> dict:
+        """One workload on this rank: W untimed + K timed steps between barriers and the in-step
+        kernel times; with `full` also the runs beside them (verify before, each kernel alone, the
+        other decode API, the box's copy rate and the roofline after).  dump_dir: rank 0 writes the
+        last timed step's outputs there (dump_outputs).  Every rank calls it with the same arguments
+        (collectives line up)."""
         import numpy as np
         import torch
         args, rank, world, ctx, stream, sp = self.args, self.rank, self.world, self.ctx, self.stream, self.sp
@@ -809,7 +884,7 @@ class Bench:
         torch.cuda.synchronize()
 
         verified = None
-        if verify:
+        if full and verify:
             # correctness of this exact configuration before timing: encode, poison the erased
             # data shards, rebuild, compare with the untouched copy; sampled groups vs oracle
             # parity are covered by tests/test_gpu_parity.py.
@@ -890,6 +965,10 @@ class Bench:
         torch.cuda.synchronize()
         barrier()
         elapsed = time.perf_counter() - t0
+        dumped = None
+        if dump_dir is not None and rank == 0:
+            dumped = dump_outputs(dump_dir, cfg, G, api, data, parity, rebuilt, row_start,
+                                  masks_h if cfg["decode"] else None)
         enc_ms = sum(e[0].elapsed_time(e[1]) for e in events) / steps
         dec_ms = (sum(e[1].elapsed_time(e[2]) for e in events) / steps) if cfg["decode"] else 0.0
 
@@ -912,73 +991,78 @@ class Bench:
             kernels["decode"] = {"ms": round(dec_ms, 4), "algorithmic_bytes": dec_bytes,
                                  "achieved_GBps": round(dec_gbs, 1),
                                  "payload_GiBps": round(k * P * G / (dec_ms * 1e-3) / 2**30, 2)}
-        # Each kernel alone, back to back (decode is idempotent on rebuilt data): its own time,
-        # without the write-back of the other kernel's output still draining from the caches
-        # when it starts (which the in-step times above include).
-        reps = max(5, steps // 4)
-
-        def isolated(fn, nbytes):
-            evs = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
-            evs[0].record(stream)
-            for i in range(reps):
-                fn()
-                evs[i + 1].record(stream)
-            torch.cuda.synchronize()
-            ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(reps))[reps // 2]
-            return {"ms_median": round(ms, 4), "achieved_GBps": round(nbytes / (ms * 1e-3) / 1e9, 1)}
-
-        kernels["encode"]["isolated"] = isolated(lambda: ctx.encode_dev(data, G, k, r, P, parity, stream=sp), enc_bytes)
+        roofline = None
+        wl = workload_key(cfg, G)
         if cfg["decode"]:
             kernels["decode"]["api"] = api
-            kernels["decode"]["isolated"] = isolated(lambda: decode_call(api), dec_bytes)
-            # the other decode API on the same buffers, for comparison (not in `value`)
-            # (sparse loss: the packed rows, the form the slot rows were chosen over)
-            other = {"packed": "recover",
-                     "recover": "packed" if cfg.get("loss") and packed_supported(k, r, P) else "in-place"}.get(api, "recover")
-            if other_api:
-                if other == "recover" and rebuilt is None:
-                    rebuilt = dev_buffer(G * r * P, args.rebuilt_offset)
-                if other == "packed" and row_start is None:
-                    row_start = torch.empty(G, dtype=torch.int32, device="cuda")
-                kernels["decode"]["other_api"] = {"api": other, **isolated(lambda: decode_call(other), dec_bytes)}
-        # The box's own HBM copy rate (fec_copy_dev: the encode's 16-B-per-lane pattern, no
-        # arithmetic), measured the same way once per process: box-to-box spread is a few
-        # percent, so the kernels are also quoted against it.
-        if self.copy is None:
-            half = (data.numel() // 2) // 16 * 16
-            scratch = torch.empty(half, dtype=torch.uint8, device="cuda")
-            self.copy = isolated(lambda: ctx.copy_dev(data, scratch, half, stream=sp), 2 * half)
-            del scratch
-            torch.cuda.empty_cache()
-        copy = self.copy
-        dom = max(kernels, key=lambda n: kernels[n]["ms"])
-        dom_read = k * P * G if dom == "encode" else dec_read
-        wl = workload_key(cfg, G)
-        pmc, pmc_note = load_pmc_traffic(config, wl)
-        pmc = pmc or {}
-        roofline = {"bound": "hbm", "kernel": dom, "achieved": kernels[dom]["achieved_GBps"],
-                    "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(kernels[dom]["achieved_GBps"] / HBM_PEAK_GBS, 4),
-                    # PMC entries are keyed per decode API (recover_packed / recover_slots / decode)
-                    "traffic": pmc.get(pmc_key(dom, api) if cfg["decode"] else dom, {}).get("hbm_bytes_per_launch"),
-                    "algorithmic_bytes_per_launch": kernels[dom]["algorithmic_bytes"],
-                    "traffic_source": pmc_note,
-                    "read_frac": round(dom_read / (kernels[dom]["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                    "read_frac_of_box_copy": round(dom_read / (kernels[dom]["ms"] * 1e-3) / 1e9 / copy["achieved_GBps"], 4),
-                    # north_star's "70% of the HBM-read roofline": reads at 0.70 x 8 TB/s while this
-                    # kernel also writes its bytes needs this much total traffic -- above the box's
-                    # copy ceiling (box_copy_GBps), so that literal target is out of reach
-                    "read_target_total_GBps": round(0.70 * HBM_PEAK_GBS * kernels[dom]["algorithmic_bytes"] / dom_read, 1),
-                    "box_copy_GBps": copy["achieved_GBps"],
-                    "frac_of_box_copy": round(kernels[dom]["achieved_GBps"] / copy["achieved_GBps"], 4),
-                    "timing": ("torch.cuda.Event on torch's default stream, kernels on the context's stream"
-                               if args.null_stream else
-                               "torch.cuda.Event on the launch stream (one torch stream for launches, ops and "
-                               "events), averaged over the timed steps")}
+        if full:
+            # Each kernel alone, back to back (decode is idempotent on rebuilt data): its own time,
+            # without the write-back of the other kernel's output still draining from the caches
+            # when it starts (which the in-step times above include).
+            reps = max(5, steps // 4)
+
+            def isolated(fn, nbytes):
+                evs = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
+                evs[0].record(stream)
+                for i in range(reps):
+                    fn()
+                    evs[i + 1].record(stream)
+                torch.cuda.synchronize()
+                ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(reps))[reps // 2]
+                return {"ms_median": round(ms, 4), "achieved_GBps": round(nbytes / (ms * 1e-3) / 1e9, 1)}
+
+            kernels["encode"]["isolated"] = isolated(lambda: ctx.encode_dev(data, G, k, r, P, parity, stream=sp), enc_bytes)
+            if cfg["decode"]:
+                kernels["decode"]["isolated"] = isolated(lambda: decode_call(api), dec_bytes)
+                # the other decode API on the same buffers, for comparison (not in `value`)
+                # (sparse loss: the packed rows, the form the slot rows were chosen over)
+                other = {"packed": "recover",
+                         "recover": "packed" if cfg.get("loss") and packed_supported(k, r, P) else "in-place"}.get(api, "recover")
+                if other_api:
+                    if other == "recover" and rebuilt is None:
+                        rebuilt = dev_buffer(G * r * P, args.rebuilt_offset)
+                    if other == "packed" and row_start is None:
+                        row_start = torch.empty(G, dtype=torch.int32, device="cuda")
+                    kernels["decode"]["other_api"] = {"api": other, **isolated(lambda: decode_call(other), dec_bytes)}
+            # The box's own HBM copy rate (fec_copy_dev: the encode's 16-B-per-lane pattern, no
+            # arithmetic), measured the same way once per process: box-to-box spread is a few
+            # percent, so the kernels are also quoted against it.
+            if self.copy is None:
+                half = (data.numel() // 2) // 16 * 16
+                scratch = torch.empty(half, dtype=torch.uint8, device="cuda")
+                self.copy = isolated(lambda: ctx.copy_dev(data, scratch, half, stream=sp), 2 * half)
+                del scratch
+                torch.cuda.empty_cache()
+            copy = self.copy
+            dom = max(kernels, key=lambda n: kernels[n]["ms"])
+            dom_read = k * P * G if dom == "encode" else dec_read
+            pmc, pmc_note = load_pmc_traffic(config, wl)
+            pmc = pmc or {}
+            roofline = {"bound": "hbm", "kernel": dom, "achieved": kernels[dom]["achieved_GBps"],
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(kernels[dom]["achieved_GBps"] / HBM_PEAK_GBS, 4),
+                        # PMC entries are keyed per decode API (recover_packed / recover_slots / decode)
+                        "traffic": pmc.get(pmc_key(dom, api) if cfg["decode"] else dom, {}).get("hbm_bytes_per_launch"),
+                        "algorithmic_bytes_per_launch": kernels[dom]["algorithmic_bytes"],
+                        "traffic_source": pmc_note,
+                        "read_frac": round(dom_read / (kernels[dom]["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                        "read_frac_of_box_copy": round(dom_read / (kernels[dom]["ms"] * 1e-3) / 1e9 / copy["achieved_GBps"], 4),
+                        # north_star's "70% of the HBM-read roofline": reads at 0.70 x 8 TB/s while this
+                        # kernel also writes its bytes needs this much total traffic -- above the box's
+                        # copy ceiling (box_copy_GBps), so that literal target is out of reach
+                        "read_target_total_GBps": round(0.70 * HBM_PEAK_GBS * kernels[dom]["algorithmic_bytes"] / dom_read, 1),
+                        "box_copy_GBps": copy["achieved_GBps"],
+                        "frac_of_box_copy": round(kernels[dom]["achieved_GBps"] / copy["achieved_GBps"], 4),
+                        "timing": ("torch.cuda.Event on torch's default stream, kernels on the context's stream"
+                                   if args.null_stream else
+                                   "torch.cuda.Event on the launch stream (one torch stream for launches, ops and "
+                                   "events), averaged over the timed steps")}
         res = {"workload": cfg["workload"], "value": round(value, 3), "unit": "GiB/s", "ranks": ranks,
                "groups_per_gpu": G, "steps": steps, "warmup": warmup, "ms_per_step": round(ms_per_step, 4),
                "verified": verified, "decode_api": api if cfg["decode"] else None,
                "kernels": kernels, "roofline": roofline, "workload_key": wl}
+        if dumped is not None:
+            res["dumped"] = dumped
         if e2e:
             # host-resident legs on the first Ge groups: the whole batch at N = 1 (15.6 GB page-locked
             # at C5), --e2e-groups (default 250k, ~3.9 GB) per rank when N ranks share one node's RAM
@@ -1041,7 +1125,7 @@ def main() -> int:
     bench = Bench(args, rank, world, local)
     t = time.monotonic()
     head = bench.measure(args.config, cfg, G, args.steps, args.warmup, args.decode_api, not args.no_verify,
-                         not args.no_other_api, args.e2e)
+                         not args.no_other_api, args.e2e, full=args.full, dump_dir=args.dump_outputs)
     wall["headline"] = round(time.monotonic() - t, 2)
 
     legs = None
@@ -1060,12 +1144,12 @@ def main() -> int:
 
     cpu = None
     t = time.monotonic()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg)
         wall["cpu_baseline"] = round(time.monotonic() - t, 2)
     site = None  # beside the headline like cpu_baseline, and skipped with it (profiled and A/B runs)
     t = time.monotonic()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_call_site:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_call_site:
         site = call_site(cpu.get("ref_encode_batch_1t_GiBps") if cpu else None)
         wall["call_site"] = round(time.monotonic() - t, 2)
     wall["total"] = round(time.monotonic() - T_START, 2)
@@ -1076,6 +1160,7 @@ def main() -> int:
             "metric": "FEC encode+decode GiB/s (device-resident), k=10 r=3 1200B pkts, 1/2/4/8 GPU",
             "value": head["value"], "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True,
+            "full": args.full,
             "scaling": "weak", "vs_baseline": None, "dtype": "u8",
             "data": "synthetic (counter-based splitmix64 bytes generated in HBM; seeded erasure masks)",
             "config": {"workload": cfg["workload"], "k": k, "r": r, "packet_bytes": P,
@@ -1092,6 +1177,8 @@ def main() -> int:
             out["e2e_pinned"] = head["e2e_pinned"]
         if site is not None:
             out["call_site"] = site
+        if "dumped" in head:
+            out["dumped"] = {"dir": args.dump_outputs, "arrays": head["dumped"]}
         if "buffers" in head:
             out["buffers"] = head["buffers"]
         if legs:

@@ -13,7 +13,7 @@ run() {  # config bits window waves
   local line wv=()
   [ "$4" != 0 ] && wv=(QUICFEC_ENCODE_WAVES="$4")
   line=$(env QUICFEC_ENCODE_BITS="$2" QUICFEC_ENCODE_BITS_WINDOW="$3" "${wv[@]}" timeout -k 10 150 python3 "$ROOT/bench.py" \
-         --config "$1" --steps 20 --warmup 3 --no-cpu-baseline --no-other-api 2>/dev/null | tail -1) || return 1
+         --full --config "$1" --steps 20 --warmup 3 --no-cpu-baseline --no-other-api 2>/dev/null | tail -1) || return 1
   python3 - "$1" "$2" "$3" "$4" "$line" >> "$OUT" <<'PY'
 import json, sys
 cfg, bits, win, waves, line = sys.argv[1:6]

@@ -9,7 +9,7 @@ mkdir -p "$E"
 cd "$ROOT"
 for rd in $(seq 1 "${ROUNDS:-3}"); do
   for api in packed recover; do
-    timeout -k 10 200 python bench.py --config c5 --steps 20 --warmup 3 --no-cpu-baseline --no-call-site \
+    timeout -k 10 200 python bench.py --full --config c5 --steps 20 --warmup 3 --no-cpu-baseline --no-call-site \
       --decode-api $api --no-other-api > "$E/ab_c5_$api.json" 2> /dev/null
     python - "$E/ab_c5_$api.json" "$api" "$rd" >> "$E/ab_c5_api.jsonl" <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ set -euo pipefail
 export QUICFEC_LIB="${QUICFEC_LIB:-$(pwd)/quic-test_amd/lib/libfec_hip_test.so}"
 for rd in $(seq 1 "${ROUNDS:-2}"); do
   for v in ${VALUES:-0 1}; do
-    env "$VAR=$v" timeout -k 10 200 python bench.py --config "${CFG:-c2c3}" --steps "${STEPS:-10}" --warmup 2 \
+    env "$VAR=$v" timeout -k 10 200 python bench.py --full --config "${CFG:-c2c3}" --steps "${STEPS:-10}" --warmup 2 \
       --no-cpu-baseline --no-verify ${BENCH_ARGS:-} > /tmp/ab.json
     python - "$VAR=$v" <<'PY'
 import json, sys

@@ -7,7 +7,7 @@ OUT="$ROOT/gpurun_out/ab_lib.jsonl"
 : > "$OUT"
 for rep in $(seq "${REPS:-3}"); do
   for lib in ${LIBS:-quic-test_amd/lib/libfec_hip.so quic-test_amd/lib/old/libfec_hip.so}; do
-    line=$(QUICFEC_LIB="$ROOT/$lib" timeout -k 10 200 python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | tail -1) || exit 1
+    line=$(QUICFEC_LIB="$ROOT/$lib" timeout -k 10 200 python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | tail -1) || exit 1
     python3 - "$lib" "$line" >> "$OUT" <<'PY'
 import json, sys
 lib, line = sys.argv[1:3]

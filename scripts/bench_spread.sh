@@ -7,7 +7,7 @@ OUT="$ROOT/gpurun_out/bench_spread.jsonl"
 : > "$OUT"
 for cfg in ${CFGS:-c2c3 c4}; do
   for i in $(seq "${N:-6}"); do
-    line=$(timeout -k 10 200 python3 "$ROOT/bench.py" --config "$cfg" --steps 20 --warmup 5 --no-cpu-baseline --no-other-api 2>/dev/null | tail -1) || exit 1
+    line=$(timeout -k 10 200 python3 "$ROOT/bench.py" --full --config "$cfg" --steps 20 --warmup 5 --no-cpu-baseline --no-other-api 2>/dev/null | tail -1) || exit 1
     python3 - "$cfg" "$line" >> "$OUT" <<'PY'
 import json, sys
 cfg, line = sys.argv[1:3]

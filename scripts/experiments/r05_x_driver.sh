@@ -11,5 +11,5 @@ timeout -k 10 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout
 tail -1 "$E/pytest_gpu.log"
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$E/smoke.log" 2>&1 || { tail -30 "$E/smoke.log"; exit 1; }
 tail -2 "$E/smoke.log"
-timeout -k 10 600 python bench.py > "$E/bench.json" 2> "$E/bench.err" || { tail -30 "$E/bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full > "$E/bench.json" 2> "$E/bench.err" || { tail -30 "$E/bench.err"; exit 1; }
 python -c "import json; d=json.load(open('$E/bench.json')); print(d['value'], d['roofline']['frac'], d['roofline']['traffic'], d['call_site']['streams_16']['groups_per_s'])"

@@ -13,7 +13,7 @@ pass() {  # tag config extra-bench-args...
   for c in FETCH_SIZE WRITE_SIZE; do
     echo "== pmc $cfg $tag $c"
     timeout -s KILL 240 rocprofv3 --pmc "$c" -d "$OUT/pmc_${cfg}_${tag}_$c" -o run --output-format csv -- \
-      python3 "$ROOT/bench.py" --config "$cfg" --steps 3 --warmup 1 --no-cpu-baseline --no-verify "$@" \
+      python3 "$ROOT/bench.py" --full --config "$cfg" --steps 3 --warmup 1 --no-cpu-baseline --no-verify "$@" \
       > "$OUT/pmc_${cfg}_${tag}_$c.json" 2> "$OUT/pmc_${cfg}_${tag}_$c.err"
   done
 }

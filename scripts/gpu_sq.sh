@@ -24,7 +24,7 @@ for CFG in ${SQ_CONFIGS:-c4 c2c3}; do
     [ $ok = 1 ] || continue
     echo "== $CFG pass $i: $group"
     timeout -s KILL 120 rocprofv3 --pmc $group -d "$OUT/${CFG}_p$i" -o run --output-format csv -- \
-      python3 "$ROOT/bench.py" --config "$CFG" --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-other-api \
+      python3 "$ROOT/bench.py" --full --config "$CFG" --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-other-api \
       > "$OUT/${CFG}_p$i.json" 2> "$OUT/${CFG}_p$i.err" || { echo "pass failed rc=$?"; tail -3 "$OUT/${CFG}_p$i.err"; exit 1; }
   done
   python3 "$ROOT/scripts/pmc_generic.py" "$OUT/sq_$CFG.json" "$OUT/${CFG}_p"* > /dev/null

@@ -43,18 +43,18 @@ CFGS="${PMC_CFGS:-c2c3 c5 c4}" bash scripts/gpu_pmc.sh > "$E/pmc.log" 2>&1
 for c in ${PMC_CFGS:-c2c3 c5 c4}; do cp "$ROOT/gpurun_out/pmc_$c.json" "$ROOT/profiles/pmc_$c.json"; cp "$ROOT/gpurun_out/pmc_$c.json" "$E/pmc_$c.json"; done
 fi
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$E/prof" -o run --output-format csv -- \
-  python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$E/prof_bench.json" 2> "$E/prof_bench.err"
+  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$E/prof_bench.json" 2> "$E/prof_bench.err"
 find "$E/prof" -name "*kernel_stats.csv" -exec cp {} "$E/kernel_stats.csv" \;
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > "$E/bench.json" 2> "$E/bench.err"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > "$E/bench.json" 2> "$E/bench.err"
 python -c "import json; d=json.loads(open('$E/bench.json').read().strip().splitlines()[-1]); print(d['value'], d['roofline']['frac'], d['roofline']['traffic'], d['kernels']['encode']['ms'], d['kernels']['decode']['ms'], d['cpu_baseline']['value'], d['call_site']['raw'], d['call_site']['streams_16'], d['call_site'].get('batcher_16_r1'), d['call_site'].get('batcher_16_r3'), d['wall_s'])"
 mkdir -p "$E/legs"
 T="timeout -k 10 300"
-$T python bench.py --config c4 --no-cpu-baseline > "$E/legs/c4.json" 2> /dev/null
-$T python bench.py --config c5 --e2e --no-cpu-baseline > "$E/legs/c5_satellite.json" 2> /dev/null
+$T python bench.py --full --config c4 --no-cpu-baseline > "$E/legs/c4.json" 2> /dev/null
+$T python bench.py --full --config c5 --e2e --no-cpu-baseline > "$E/legs/c5_satellite.json" 2> /dev/null
 for f in "$E"/legs/*.json; do
   python -c "import json; d=json.loads(open('$f').read().strip().splitlines()[-1]); k=d['kernels']; print('$f'.split('/')[-1], d['value'], d['verified'], {n: (v['ms'], v['achieved_GBps']) for n, v in k.items()}, d['roofline']['frac'], d['roofline']['traffic'])"
 done
 # the --gpus 2 rehearsal (two gloo ranks sharing the card) at the driver's default sizes: every
 # section verified, traffic from this build's PMC (1M groups per rank = the PMC workload), wall_s
-QUICFEC_DIST_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 2 > "$E/bench_gpus2_gloo_rehearsal.json" 2> "$E/bench_gpus2.err"
+QUICFEC_DIST_BACKEND=gloo timeout -k 10 600 python bench.py --full --gpus 2 > "$E/bench_gpus2_gloo_rehearsal.json" 2> "$E/bench_gpus2.err"
 python -c "import json; d=json.loads(open('$E/bench_gpus2_gloo_rehearsal.json').read().strip().splitlines()[-1]); print('gpus2', d['n_gpus'], d['value'], d['verified'], d['roofline']['traffic'], d.get('wall_s'), {s: (d[s]['ranks'], d[s]['value'], d[s]['verified'], d[s]['roofline']['traffic']) for s in ('c4', 'c5_e2e')})"

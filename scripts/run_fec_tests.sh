@@ -110,7 +110,7 @@ run_bench() {
   local tag="$1"; shift
   echo "== $tag (gpus=$GPUS)"
   # bench.py --gpus N starts one rank per GPU itself (no WORLD_SIZE in the environment)
-  timeout -k 10 900 python bench.py --gpus "$GPUS" "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.err"
+  timeout -k 10 900 python bench.py --gpus "$GPUS" --full "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.err"
   cat "$OUT/$tag.json"
 }
 run_bench c2c3 --config c2c3 --steps 30 --warmup 5

@@ -8,7 +8,7 @@ for S in $SHAPES; do
   G=$((6000000000 / (K * P)))
   for API in recover in-place; do
     printf "%s %s " "$S" "$API"
-    timeout -k 10 120 python bench.py --config c2c3 --shape "$S" --groups "$G" --steps 10 --warmup 2 \
+    timeout -k 10 120 python bench.py --full --config c2c3 --shape "$S" --groups "$G" --steps 10 --warmup 2 \
         --no-cpu-baseline --decode-api "$API" | python -c "import json,sys; d=json.loads(sys.stdin.read()); e=d['kernels']; print(d['verified'], 'dec', e['decode']['ms'], e['decode']['achieved_GBps'])"
   done
 done

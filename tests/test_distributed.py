@@ -95,7 +95,7 @@ def test_bench_gpus_n_spawns_n_ranks(world):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["QUICFEC_DIST_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", str(world), "--launch-selftest"],
+    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", str(world), "--full", "--launch-selftest"],
                          env=env, capture_output=True, text=True, timeout=180)
     assert out.returncode == 0, out.stderr
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -104,8 +104,24 @@ def test_bench_gpus_n_spawns_n_ranks(world):
     assert rec["n_gpus"] == world and rec["gpus_arg"] == world
     assert rec["max_elapsed"] == pytest.approx(0.25 * world)
     assert rec["total_groups"] == pytest.approx(1000 * world)
-    # the multi-GPU BASELINE legs (C4, C5 with H2D/D2H) run after the headline when N > 1 only
+    # the multi-GPU BASELINE legs (C4, C5 with H2D/D2H) run after the headline of a --full run
+    # when N > 1 only
     assert ("c4" in rec) == (world > 1) and ("c5_e2e" in rec) == (world > 1)
+
+
+def test_bench_plain_run_has_no_legs():
+    """Without --full the ranks of `bench.py --gpus N` measure the headline alone: no C4 / C5 legs,
+    not even with --legs on."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["QUICFEC_DIST_BACKEND"] = "gloo"
+    for extra in ([], ["--legs", "on"]):
+        out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", *extra, "--launch-selftest"],
+                             env=env, capture_output=True, text=True, timeout=180)
+        assert out.returncode == 0, out.stderr
+        rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+        assert rec["n_gpus"] == 2 and "c4" not in rec and "c5_e2e" not in rec
 
 
 @pytest.mark.parametrize("world", [2, 8])
@@ -117,7 +133,7 @@ def test_bench_gpus_n_carries_every_multi_gpu_config(world):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["QUICFEC_DIST_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", str(world), "--launch-selftest"],
+    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", str(world), "--full", "--launch-selftest"],
                          env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
@@ -133,7 +149,7 @@ def test_bench_gpus_n_carries_every_multi_gpu_config(world):
         return
     assert "C4" in rec["c4"]["workload"] and "C5" in rec["c5_e2e"]["workload"]
     # --legs off drops them
-    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--legs", "off", "--launch-selftest"],
+    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--full", "--legs", "off", "--launch-selftest"],
                          env=env, capture_output=True, text=True, timeout=180)
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     assert "c4" not in rec and "c5_e2e" not in rec
