@@ -124,8 +124,10 @@ int fec_decode_prepare(FECEncoderCtx* ctx, uint32_t k, uint32_t r, uint64_t* byt
  * = all rows.  d_rebuilt holds at most num_groups * r rows.  No gaps between groups' rows:
  * the stores stream like encode's parity (C5-style sparse loss: 15% faster than the slot
  * layout in the probe, profiles/r02_probe_recover_write_layout.txt).  Mask-addressed shapes
- * only (k + r with an inline-classify form, r <= 3, 256 < P <= 2048); others return
- * FEC_ERR_RANGE.  Asynchronous on `stream` like the call above. */
+ * only (k + r with an inline-classify form, r <= 3: k=10 with r = 1, 2, 3 and k=4 r=2), at
+ * 256 < P <= 2047 (2048 has no inline-classify form); k=10 r=2, which has no tiled form for
+ * short packets, also at 16 <= P <= 256.  Every other shape or size returns FEC_ERR_RANGE with
+ * nothing written.  Asynchronous on `stream` like the call above. */
 int fec_recover_batch_rs_dev_packed(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
                                     const uint64_t* d_masks, uint64_t num_groups, uint32_t k, uint32_t r,
                                     uint32_t packet_size, uint8_t* d_rebuilt, uint32_t* d_row_start,

@@ -2256,9 +2256,32 @@ uint64_t max_wave_blocks() {
   const long n = test_knob(TestKnob::kMaxWaveBlocks, 0);
   return n > 0 && static_cast<uint64_t>(n) < kMaxWaveBlocks ? static_cast<uint64_t>(n) : kMaxWaveBlocks;
 }
+// Work items per launch of the kernels that map one item to a lane: kMaxThreadsPerLaunch (the
+// test library's TestKnob::kMaxLaunchThreads lowers it, so the chunk loops below, which otherwise
+// start only past 2^30 items, run at a few thousand).
+uint32_t max_launch_threads() {
+  const long n = test_knob(TestKnob::kMaxLaunchThreads, 0);
+  return n > 0 && static_cast<uint64_t>(n) < kMaxThreadsPerLaunch ? static_cast<uint32_t>(n) : kMaxThreadsPerLaunch;
+}
+// Groups per launch when each takes `per_group` work items (at least one group).
+uint64_t groups_per_launch(uint32_t per_group) {
+  const uint64_t n = max_launch_threads() / (per_group ? per_group : 1u);
+  return n ? n : 1;
+}
 constexpr uint32_t kVecMinP = 16;  // shorter packets take the byte kernels
 
 inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + 255) / 256); }
+
+// The launch trace's record (fec_knobs.hpp; trace_launch() is empty in the product library).
+LaunchRecord launch_record(LaunchForm form, uint64_t grid, uint32_t block, uint64_t first_item, uint64_t items) {
+  LaunchRecord t{};
+  t.form = static_cast<int64_t>(form);
+  t.grid = static_cast<int64_t>(grid);
+  t.block = block;
+  t.first_item = static_cast<int64_t>(first_item);
+  t.items = static_cast<int64_t>(items);
+  return t;
+}
 
 }  // namespace
 
@@ -2311,10 +2334,16 @@ template <int K, int R, int OFF, bool FIRST, int POL = kNtStore>
 hipError_t run_encode_v16(const EncodeLaunch& a, uint32_t row0, hipStream_t s) {
   const uint32_t cpp = (a.P + 15u) / 16u;
   const uint32_t tile = encode_tile(a);
-  const uint64_t gchunk = kMaxThreadsPerLaunch / cpp;
+  const uint64_t gchunk = groups_per_launch(cpp);
   for (uint64_t g0 = 0; g0 < a.groups; g0 += gchunk) {
     const uint64_t gn = (a.groups - g0 < gchunk) ? a.groups - g0 : gchunk;
     const uint32_t n = static_cast<uint32_t>(gn * cpp);
+    {
+      const uint32_t bs = tile > 0 ? (tile * cpp + 63) / 64 * 64 : 256u;
+      LaunchRecord t = launch_record(LaunchForm::kEncodeV16, tile > 0 ? (gn + tile - 1) / tile : blocks_for(n), bs, g0, gn);
+      t.k = K, t.r = R, t.off = OFF, t.first = FIRST, t.pol = POL, t.tile = tile, t.aux = row0;
+      trace_launch(t);
+    }
     if (tile > 0) {
       const uint32_t bs = (tile * cpp + 63) / 64 * 64;
       const uint32_t blocks = static_cast<uint32_t>((gn + tile - 1) / tile);
@@ -2366,6 +2395,11 @@ hipError_t run_encode_bits(const EncodeLaunch& a, hipStream_t s) {
     const int waves = a.waves_per_cu ? a.waves_per_cu : knob(TestKnob::kEncodeWaves, kDefWaves);
     uint32_t smem = occupancy_cap_lds(waves, bs / 64);
     if constexpr ((POL & kStageRows) != 0) smem = std::max<uint32_t>(smem, 2 * tile * R * a.P);
+    {
+      LaunchRecord t = launch_record(LaunchForm::kEncodeBits, blocks, bs, g0, gn);
+      t.k = K, t.r = R, t.off = 0, t.pol = POL, t.tile = tile, t.aux = W;
+      trace_launch(t);
+    }
     hipLaunchKernelGGL((encode_bits<K, R, W, POL>), dim3(blocks), dim3(bs), smem, s, a.data, a.parity, g0, cpp, a.P,
                        tile, gn, 0u);
     const hipError_t e = hipGetLastError();
@@ -2383,7 +2417,9 @@ bool use_encode_bits(uint32_t r) {
 }
 
 // kStageRows for a launch whose workgroup window (groups_per_block * r * P bytes) fits the LDS a
-// workgroup may take (the test library's TestKnob::kEncodeStage: 1 on, 0 off).
+// workgroup may take (the test library's TestKnob::kEncodeStage: 1 on, 0 off).  A flat launch
+// (P > 8192, groups_per_block 0) passes too: it runs the kStageRows instantiation, whose kernel
+// stages only when tiled and otherwise stores directly.
 bool use_stage_rows(const EncodeLaunch& a, uint32_t groups_per_block) {
   const int mode = knob(TestKnob::kEncodeStage, kEncodeStageDefault);
   return mode == 1 && a.P % 16 == 0 && uint64_t(groups_per_block) * a.r * a.P <= 64u * 1024u;
@@ -2392,10 +2428,15 @@ bool use_stage_rows(const EncodeLaunch& a, uint32_t groups_per_block) {
 template <int OFF>
 hipError_t run_encode_generic(const EncodeLaunch& a, hipStream_t s) {
   if (a.P < kVecMinP) {
-    const uint64_t gchunk = kMaxThreadsPerLaunch / a.P;
+    const uint64_t gchunk = groups_per_launch(a.P);
     for (uint64_t g0 = 0; g0 < a.groups; g0 += gchunk) {
       const uint64_t gn = (a.groups - g0 < gchunk) ? a.groups - g0 : gchunk;
       const uint32_t n = static_cast<uint32_t>(gn * a.P);
+      {
+        LaunchRecord t = launch_record(LaunchForm::kEncodeBytes, blocks_for(n), 256, g0, gn);
+        t.k = 0, t.off = OFF;
+        trace_launch(t);
+      }
       hipLaunchKernelGGL(encode_bytes<OFF>, dim3(blocks_for(n)), dim3(256), 0, s, a.data, a.offsets,
                          a.parity, g0, n, a.P, a.k, a.r, static_cast<const Tab*>(a.tables));
       const hipError_t e = hipGetLastError();
@@ -2501,6 +2542,11 @@ hipError_t run_decode_v16(const DecodeLaunch& a, hipStream_t s) {
       const uint64_t bn = (blocks - b0 < max_blocks) ? blocks - b0 : max_blocks;
       const uint64_t g0 = b0 * 4;
       const uint64_t gn = (a.groups - g0 < bn * 4) ? a.groups - g0 : bn * 4;
+      {
+        LaunchRecord t = launch_record(LaunchForm::kDecodeV16, bn, 256, g0, gn);
+        t.k = K, t.r = MAXE, t.aux = m0;
+        trace_launch(t);
+      }
       hipLaunchKernelGGL((decode_v16<K, MAXE>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
                          a.data + g0 * a.k * static_cast<uint64_t>(a.P),
                          a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook,
@@ -2528,6 +2574,11 @@ hipError_t run_decode_wave(const DecodeLaunch& a, hipStream_t s) {
       const uint64_t bn = (blocks - b0 < max_blocks) ? blocks - b0 : max_blocks;
       const uint64_t g0 = b0 * 4;
       const uint64_t gn = (a.groups - g0 < bn * 4) ? a.groups - g0 : bn * 4;
+      {
+        LaunchRecord t = launch_record(LaunchForm::kDecodeWave, bn, 256, g0, gn);
+        t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
+        trace_launch(t);
+      }
       hipLaunchKernelGGL((decode_wave<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), smem, s,
                          a.data + g0 * a.k * static_cast<uint64_t>(a.P),
                          a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook, gn, a.P,
@@ -2565,6 +2616,11 @@ hipError_t run_decode_fused(const DecodeLaunch& a, hipStream_t s) {
       const uint64_t bn = (blocks - b0 < max_blocks) ? blocks - b0 : max_blocks;
       const uint64_t g0 = b0 * kGroupsPerBlock;
       const uint64_t gn = (a.groups - g0 < bn * kGroupsPerBlock) ? a.groups - g0 : bn * kGroupsPerBlock;
+      {
+        LaunchRecord t = launch_record(LaunchForm::kDecodeFused, bn, 256, g0, gn);
+        t.k = K, t.r = MAXE, t.nm = NM, t.nt = NT, t.pol = POL, t.direct = DIRECT, t.scan = SCAN, t.aux = m0;
+        trace_launch(t);
+      }
       hipLaunchKernelGGL((decode_fused<K, MAXE, POL, NM, NT, DIRECT, INLINE, SCAN>), dim3(static_cast<uint32_t>(bn)), dim3(256), smem, s,
                          a.data + g0 * a.k * static_cast<uint64_t>(a.P),
                          a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook, gn, a.P,
@@ -2578,9 +2634,13 @@ hipError_t run_decode_fused(const DecodeLaunch& a, hipStream_t s) {
 }
 
 // The fused form for this (k, r, P), if instantiated; hipErrorNotSupported otherwise.
-// Instantiated for every P in [16, 2048] of the compiled (k, r) shapes: NM 16-B and NT 4-B
-// pieces per lane (P <= 256: one 4-B piece; the in-place decode of such packets takes the
-// tiled form, the recover layout this one).  r <= 3 shapes only in the mask-addressed form (the one auto uses for
+// Instantiated for every P in [16, 2047] of the compiled (k, r) shapes: NM = P / 1024 16-B and
+// NT = ceil((P % 1024) / 256) 4-B pieces per lane, (NM, NT) in (0,1..4), (1,0..4); P = 2048 would
+// be (2,0), which is not instantiated, so 2048 and up take the wave kernel.  P <= 256 is the one
+// 4-B piece (0,1): the shapes with a tiled form decode such packets there in both layouts, so of
+// the mask-addressed (0,1) forms only k=10 r=2's compact one is ever launched (recover layouts);
+// k=10 r=2 in place at P <= 256 goes to the runtime-k wave kernel (a known slow
+// path).  r <= 3 shapes only in the mask-addressed form (the one auto uses for
 // them), r > 3 only in the record-addressed one; k=10 r=3 1200 B in both (probes).
 // Measured at k=10 r=3, 2 erasures (tools/probe_decode.hip): 512 B 5.89 TB/s vs 3.12 for
 // the looped wave kernel, 768 B 5.49 vs 3.24 (profiles/r01_probe_decode_small.txt).  The
@@ -2644,11 +2704,16 @@ hipError_t run_decode_tiled(const DecodeLaunch& a, uint32_t tile, hipStream_t s)
   const uint32_t cpp = (a.P + 15u) / 16u;
   const uint32_t bs = (tile * cpp + 63) / 64 * 64;
   const uint64_t blocks = (a.groups + tile - 1) / tile;
-  const uint64_t max_blocks = kMaxThreadsPerLaunch / bs;  // blocks * bs stays a 32-bit grid
+  const uint64_t max_blocks = groups_per_launch(bs);  // blocks * bs stays a 32-bit grid
   for (uint64_t b0 = 0; b0 < blocks; b0 += max_blocks) {
     const uint64_t bn = (blocks - b0 < max_blocks) ? blocks - b0 : max_blocks;
     const uint64_t g0 = b0 * tile;
     const uint64_t gn = (a.groups - g0 < bn * tile) ? a.groups - g0 : bn * tile;
+    {
+      LaunchRecord t = launch_record(LaunchForm::kDecodeTiled, bn, bs, g0, gn);
+      t.k = K, t.r = MAXE, t.pol = POL, t.tile = tile;
+      trace_launch(t);
+    }
     hipLaunchKernelGGL((decode_tiled<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(bs), 0, s,
                        a.data + g0 * a.k * static_cast<uint64_t>(a.P),
                        a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook, gn, cpp,
@@ -2688,7 +2753,7 @@ bool decode_direct_form(const DecodeLaunch& a) {
 
 bool decode_needs_rec_off(const DecodeLaunch& a) { return a.groups > 0 && !decode_direct_form(a); }
 
-// The record-addressed LDS-table forms (QFEC_FUSED_L: k=20 r=5, 256 < P < 2048) read compact
+// The record-addressed LDS-table forms (QFEC_FUSED_L: k=20 r=5, 16 <= P < 2048) read compact
 // codebooks; every other form reads CoefEntry records.
 bool decode_compact_tables(const DecodeLaunch& a) {
   if (a.groups == 0 || a.P < kVecMinP || a.rec_ready || decode_tiled_form(a) || decode_direct_form(a)) return false;
@@ -2709,8 +2774,16 @@ hipError_t launch_rows_prefix(const uint64_t* masks, uint64_t groups, uint32_t k
   // the two-launch form's block limit (the test library's TestKnob::kRowsDirectBlocks forces the other form)
   const uint64_t direct_max = static_cast<uint64_t>(knob(TestKnob::kRowsDirectBlocks, kRowsDirectBlocks));
   const dim3 grid(static_cast<uint32_t>(nb));
+  const bool direct = nb <= direct_max;
+  {
+    trace_launch(launch_record(LaunchForm::kRowsBlockSums, nb, 256, 0, groups));
+    if (!direct) trace_launch(launch_record(LaunchForm::kRowsScanBlocks, 1, 256, 0, groups));
+    LaunchRecord t = launch_record(LaunchForm::kRowsWrite, nb, 256, 0, groups);
+    t.direct = direct;
+    trace_launch(t);
+  }
   hipLaunchKernelGGL(rows_block_sums, grid, dim3(256), 0, s, masks, groups, k, r, block_sums);
-  if (nb <= direct_max) {
+  if (direct) {
     hipLaunchKernelGGL(rows_write<true>, grid, dim3(256), 0, s, masks, groups, k, r, block_sums, row_start, total);
   } else {
     hipLaunchKernelGGL(rows_scan_blocks, dim3(1), dim3(256), 0, s, block_sums, static_cast<uint32_t>(nb), total);
@@ -2758,6 +2831,11 @@ hipError_t run_recover_runs(const RunsLaunch& a, uint32_t stage, hipStream_t s) 
     const uint64_t g0 = c * per;
     const uint64_t gn = a.groups - g0 < per ? a.groups - g0 : per;
     const uint32_t nb = static_cast<uint32_t>((gn + kRunGroups - 1) / kRunGroups);
+    {
+      LaunchRecord t = launch_record(LaunchForm::kRecoverRuns, nb, 64 * kRunWaves, g0, gn);
+      t.k = K, t.r = R, t.nm = NM, t.nt = NT, t.pol = POL, t.tile = kRunGroups, t.aux = stage;
+      trace_launch(t);
+    }
     hipLaunchKernelGGL((recover_runs<K, R, NM, NT, POL, kRunWaves>), dim3(nb), dim3(64 * kRunWaves), stage, s, a.data + g0 * K * static_cast<uint64_t>(a.P),
                        a.parity + g0 * R * static_cast<uint64_t>(a.P), a.masks + g0, gn, a.P, a.codebook, rm, a.out,
                        a.row_start + g0, a.status ? a.status + g0 : nullptr, lb, ticket, a.epoch + c, stage,
@@ -2769,7 +2847,9 @@ hipError_t run_recover_runs(const RunsLaunch& a, uint32_t stage, hipStream_t s) 
 }
 
 // (k, r, P) shapes with a compiled recover_runs: the mask-addressed decode's (try_decode_fused
-// QFEC_FUSED_DS / _D lists), 256 < P <= 2048 or P <= 256 with one 4-B piece.
+// QFEC_FUSED_DS / _D lists), 256 < P <= 2047 or 16 <= P <= 256 with one 4-B piece (the packed call
+// reaches the latter only for k=10 r=2: the other shapes' short packets are refused, their slot
+// layout being the tiled form's).
 hipError_t try_recover_runs(const RunsLaunch& a, uint32_t stage, hipStream_t s, bool dry) {
   const uint32_t nm = a.P / 1024u, nt = (a.P % 1024u + 255u) / 256u;
 #define QFEC_RUNS(KK, RR, NMM, NTT) \
@@ -2829,18 +2909,25 @@ hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s) {
   const bool tiled = decode_tiled_form(a);
   if (decode_direct_form(a)) return try_decode_fused(a, s, true);
   if (a.rec_off == nullptr) return hipErrorInvalidValue;  // every other form reads rec_off
-  for (uint64_t g0 = 0; !a.rec_ready && g0 < a.groups; g0 += kMaxThreadsPerLaunch) {
-    const uint64_t gn = (a.groups - g0 < kMaxThreadsPerLaunch) ? a.groups - g0 : kMaxThreadsPerLaunch;
+  const uint64_t max_threads = max_launch_threads();
+  for (uint64_t g0 = 0; !a.rec_ready && g0 < a.groups; g0 += max_threads) {
+    const uint64_t gn = (a.groups - g0 < max_threads) ? a.groups - g0 : max_threads;
+    trace_launch(launch_record(LaunchForm::kClassify, blocks_for(gn), 256, g0, gn));
     hipLaunchKernelGGL(classify, dim3(blocks_for(gn)), dim3(256), 0, s, a.masks + g0, gn, a.k, a.r,
                        a.binom, a.meta, a.rec_off ? a.rec_off + g0 : nullptr, a.status ? a.status + g0 : nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if (a.P < kVecMinP) {
-    const uint64_t gchunk = kMaxThreadsPerLaunch / a.P;
+    const uint64_t gchunk = groups_per_launch(a.P);
     for (uint64_t g0 = 0; g0 < a.groups; g0 += gchunk) {
       const uint64_t gn = (a.groups - g0 < gchunk) ? a.groups - g0 : gchunk;
       const uint32_t n = static_cast<uint32_t>(gn * a.P);
+      {
+        LaunchRecord t = launch_record(LaunchForm::kDecodeBytes, blocks_for(n), 256, g0, gn);
+        t.k = 0, t.pol = a.compact_out ? kCompactOut : 0;
+        trace_launch(t);
+      }
       hipLaunchKernelGGL(decode_bytes, dim3(blocks_for(n)), dim3(256), 0, s, a.data, a.parity,
                          a.rec_off, a.codebook, g0, n, a.P, a.k, a.r, a.out ? a.out : a.data,
                          a.compact_out ? 1u : 0u);
@@ -2935,10 +3022,16 @@ hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t nbytes, uint64_t seed, ui
   if (nbytes == 0) return hipSuccess;
   const bool fast = (byte_offset % 8 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0);
   uint64_t done = 0;
+  const uint64_t max_threads = max_launch_threads();
   if (fast) {
     const uint64_t n16 = nbytes / 16;
-    for (uint64_t c0 = 0; c0 < n16; c0 += kMaxThreadsPerLaunch) {
-      const uint64_t cn = (n16 - c0 < kMaxThreadsPerLaunch) ? n16 - c0 : kMaxThreadsPerLaunch;
+    for (uint64_t c0 = 0; c0 < n16; c0 += max_threads) {
+      const uint64_t cn = (n16 - c0 < max_threads) ? n16 - c0 : max_threads;
+      {
+        LaunchRecord t = launch_record(LaunchForm::kFill, blocks_for(cn), 256, c0, cn);
+        t.aux = 16;
+        trace_launch(t);
+      }
       hipLaunchKernelGGL(fill_words, dim3(blocks_for(cn)), dim3(256), 0, s, dst + c0 * 16,
                          static_cast<uint32_t>(cn), seed, (byte_offset / 8) + 2 * c0);
       const hipError_t e = hipGetLastError();
@@ -2946,8 +3039,13 @@ hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t nbytes, uint64_t seed, ui
     }
     done = n16 * 16;
   }
-  for (uint64_t c0 = done; c0 < nbytes; c0 += kMaxThreadsPerLaunch) {
-    const uint64_t cn = (nbytes - c0 < kMaxThreadsPerLaunch) ? nbytes - c0 : kMaxThreadsPerLaunch;
+  for (uint64_t c0 = done; c0 < nbytes; c0 += max_threads) {
+    const uint64_t cn = (nbytes - c0 < max_threads) ? nbytes - c0 : max_threads;
+    {
+      LaunchRecord t = launch_record(LaunchForm::kFill, blocks_for(cn), 256, c0, cn);
+      t.aux = 1;
+      trace_launch(t);
+    }
     hipLaunchKernelGGL(fill_bytes, dim3(blocks_for(cn)), dim3(256), 0, s, dst + c0,
                        static_cast<uint32_t>(cn), seed, byte_offset + c0);
     const hipError_t e = hipGetLastError();
@@ -2966,6 +3064,7 @@ hipError_t launch_legacy_server(ServerSlot* ring, uint8_t* inl, uint64_t* done, 
   if (classes < 1u || classes > kServerMaxClasses || (classes & (classes - 1u)) != 0 || (classes > 1u && !coord) ||
       gen == 0 || gen >= (1ull << 56))
     return hipErrorInvalidValue;
+  trace_launch(launch_record(LaunchForm::kLegacyServer, classes, kServerThreads, 0, 0));
   hipLaunchKernelGGL(legacy_server, dim3(classes), dim3(kServerThreads), 0, s, ring, inl, done, ctl,
                      classes > 1u ? coord : nullptr, classes, gen, idle_ticks, slow_ticks, life_ticks, stamps, epoch);
   return hipGetLastError();
@@ -2973,8 +3072,14 @@ hipError_t launch_legacy_server(ServerSlot* ring, uint8_t* inl, uint64_t* done, 
 
 hipError_t launch_copy_words(const uint8_t* src, uint8_t* dst, uint64_t nbytes, hipStream_t s) {
   const uint64_t n16 = nbytes / 16;
-  for (uint64_t c0 = 0; c0 < n16; c0 += kMaxThreadsPerLaunch) {
-    const uint64_t cn = (n16 - c0 < kMaxThreadsPerLaunch) ? n16 - c0 : kMaxThreadsPerLaunch;
+  const uint64_t max_threads = max_launch_threads();
+  for (uint64_t c0 = 0; c0 < n16; c0 += max_threads) {
+    const uint64_t cn = (n16 - c0 < max_threads) ? n16 - c0 : max_threads;
+    {
+      LaunchRecord t = launch_record(LaunchForm::kCopy, blocks_for(cn), 256, c0, cn);
+      t.aux = 16;
+      trace_launch(t);
+    }
     hipLaunchKernelGGL(copy_words, dim3(blocks_for(cn)), dim3(256), 0, s,
                        reinterpret_cast<const uint4*>(src + c0 * 16), reinterpret_cast<uint4*>(dst + c0 * 16),
                        static_cast<uint32_t>(cn));

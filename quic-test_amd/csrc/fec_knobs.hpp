@@ -13,10 +13,13 @@
 // linked from the same kernel and shim objects.
 #pragma once
 
+#include <cstdint>
+
 namespace qfec {
 
 enum class TestKnob : int {
   kMaxWaveBlocks,     // workgroups per wave-per-group launch (forces the chunked launches)
+  kMaxLaunchThreads,  // work items per launch of every other kernel (forces their chunked launches)
   kEncodeTile,        // groups per workgroup of the tiled encodes
   kEncodeBlocks,      // workgroups per CU of the tiled encodes
   kEncodeWaves,       // occupancy cap of the encodes, waves per CU
@@ -45,5 +48,57 @@ long test_knob(TestKnob k, long def);
 
 // Whether this library reads the test switches (libfec_hip_test.so).
 bool test_knobs_enabled();
+
+// ---- launch trace ----
+// Every host launcher of fec_kernels.hip reports each kernel launch here, so that a test can
+// see which kernel form produced the bytes it checks.  Like test_knob() this is compiled twice:
+// in libfec_hip.so trace_launch() is an empty function and nothing is stored; in
+// libfec_hip_test.so it appends the record to a bounded buffer (under a mutex: the batcher's
+// flusher threads launch too).  Forms are numbers here; their names live with the reader's
+// callers (quicfec.launch_trace), not in either library.
+enum class LaunchForm : int64_t {
+  kEncodeV16 = 1,
+  kEncodeBits = 2,
+  kEncodeBytes = 3,
+  kClassify = 4,
+  kDecodeFused = 5,
+  kDecodeTiled = 6,
+  kDecodeWave = 7,
+  kDecodeBytes = 8,
+  kRowsBlockSums = 9,
+  kRowsScanBlocks = 10,
+  kRowsWrite = 11,
+  kRecoverRuns = 12,
+  kFill = 13,
+  kCopy = 14,
+  kLegacyServer = 15,
+  kDecodeV16 = 16,  // probe builds only
+};
+
+// One launch: 16 words, -1 where a field does not apply to the form.
+struct LaunchRecord {
+  int64_t form;          // LaunchForm
+  int64_t k = -1;        // template K (0: the runtime-k instantiation)
+  int64_t r = -1;        // template R (encodes, recover_runs) or MAXE (decodes)
+  int64_t nm = -1;       // 16-B pieces per lane (decode_fused, recover_runs)
+  int64_t nt = -1;       //  4-B pieces per lane
+  int64_t off = -1;      // encode: OffsetKind of the instantiation
+  int64_t first = -1;    // encode_v16: this pass owns the XOR row
+  int64_t pol = -1;      // memory policy / form bits (fec_kernels.hip kNtLoad .. kStageRows)
+  int64_t direct = -1;   // decode_fused: mask-addressed; rows_write: writes the total itself
+  int64_t scan = -1;     // decode_fused: groups per wave of the scan form (0: one wave per group)
+  int64_t tile = -1;     // groups per workgroup of the tiled mappings, 0 = flat mapping
+  int64_t grid = 0;      // workgroups
+  int64_t block = 0;     // work items per workgroup
+  int64_t first_item = 0;  // first group (fill / copy: first 16-B word or byte) of this launch
+  int64_t items = 0;     // groups (fill / copy: words or bytes) of this launch
+  int64_t aux = -1;      // encode_v16: first parity row; decodes: first rebuilt row of the pass;
+                         // encode_bits: W; recover_runs: run-image bytes; fill / copy: bytes per
+                         // work item
+};
+static_assert(sizeof(LaunchRecord) == 16 * sizeof(int64_t), "the reader copies 16 words per launch");
+constexpr uint64_t kLaunchTraceCapacity = 1u << 16;  // records kept; later launches are only counted
+
+void trace_launch(const LaunchRecord& rec);
 
 }  // namespace qfec

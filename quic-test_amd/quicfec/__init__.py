@@ -534,3 +534,38 @@ def coalesce_stats(reset: bool = False) -> dict:
     st = np.zeros(len(COALESCE_STATS), dtype=np.uint64)
     _check(lib.fec_coalesce_stats_sized(st.ctypes.data, st.nbytes, 1 if reset else 0), "fec_coalesce_stats_sized")
     return dict(zip(COALESCE_STATS, (int(x) for x in st)))
+
+
+# ---- launch trace (csrc/fec_knobs.hpp LaunchRecord; live in libfec_hip_test.so only) ----
+LAUNCH_FORMS = {1: "encode_v16", 2: "encode_bits", 3: "encode_bytes", 4: "classify", 5: "decode_fused",
+                6: "decode_tiled", 7: "decode_wave", 8: "decode_bytes", 9: "rows_block_sums", 10: "rows_scan_blocks",
+                11: "rows_write", 12: "recover_runs", 13: "fill", 14: "copy", 15: "legacy_server", 16: "decode_v16"}
+LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
+                 "first_item", "items", "aux")
+LAUNCH_TRACE_CAPACITY = 1 << 16
+# the `pol` bits (csrc/fec_kernels.hip)
+POL_NT_LOAD, POL_NT_STORE, POL_NO_COEF_BRANCH, POL_LDS_TABS = 1, 2, 4, 64
+POL_COMPACT_OUT, POL_COEF_BYTES, POL_PAIR_MAC, POL_STAGE_ROWS = 1024, 2048, 4096, 8192
+
+
+def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
+    """The kernel launches `lib` recorded since the trace was last cleared, oldest first: one dict
+    per launch with the LAUNCH_FIELDS (form as its LAUNCH_FORMS name; -1 = the field does not
+    apply).  Only libfec_hip_test.so records; libfec_hip.so always returns []."""
+    fn = lib.fec_hip_launch_trace
+    fn.restype, fn.argtypes = _u64, [_vp, _u64, _int]
+    seen = int(fn(None, 0, 0))
+    if seen == 0:
+        return []
+    if seen > LAUNCH_TRACE_CAPACITY:
+        fn(None, 0, 1 if clear else 0)
+        raise OverflowError(f"{seen} launches since the trace was cleared; it keeps {LAUNCH_TRACE_CAPACITY}")
+    # a flusher thread may launch between the two calls: room for more, and the count of the copy
+    buf = np.zeros((LAUNCH_TRACE_CAPACITY, len(LAUNCH_FIELDS)), dtype=np.int64)
+    seen = min(int(fn(buf.ctypes.data, LAUNCH_TRACE_CAPACITY, 1 if clear else 0)), LAUNCH_TRACE_CAPACITY)
+    out = []
+    for row in buf[:seen]:
+        rec = dict(zip(LAUNCH_FIELDS, (int(x) for x in row)))
+        rec["form"] = LAUNCH_FORMS.get(rec["form"], rec["form"])
+        out.append(rec)
+    return out

@@ -83,6 +83,34 @@ def test_product_library_has_no_test_switches(quicfec_mod):
     assert syms[0] == syms[1]
 
 
+def test_product_library_keeps_no_launch_trace(quicfec_mod):
+    """The launch trace (csrc/fec_knobs.hpp) is live in libfec_hip_test.so only: both libraries
+    export its reader (same C-ABI), the product's writes nothing into the caller's buffer and
+    reports no launches, the form names are in neither library, and the Python names cover the
+    enum one for one."""
+    guard = np.int64(0x5A5A5A5A5A5A5A5A)
+    for path in (quicfec_mod.LIB_PATH, quicfec_mod.TEST_LIB_PATH):
+        blob = Path(path).read_bytes()
+        for name in quicfec_mod.LAUNCH_FORMS.values():
+            assert (name + "\0").encode() not in blob, (path, name)   # no such C string
+    lib = quicfec_mod.load_library()
+    fn = lib.fec_hip_launch_trace
+    fn.restype, fn.argtypes = quicfec_mod._u64, [quicfec_mod._vp, quicfec_mod._u64, quicfec_mod._int]
+    buf = np.full(4 * 16, guard, dtype=np.int64)
+    for clear in (0, 1):
+        assert fn(buf.ctypes.data, 4, clear) == 0
+        assert fn(None, 0, clear) == 0
+    assert (buf == guard).all()
+    assert quicfec_mod.launch_trace(lib) == []
+    hpp = (REPO / "quic-test_amd" / "csrc" / "fec_knobs.hpp").read_text()
+    enum = re.search(r"enum class LaunchForm : int64_t \{(.*?)\};", hpp, re.S).group(1)
+    ids = {int(m.group(2)): re.sub(r"(?<!^)(?=[A-Z])", "_", m.group(1)).lower()
+           for m in re.finditer(r"^\s*k(\w+) = (\d+),", enum, re.M)}
+    assert ids == quicfec_mod.LAUNCH_FORMS
+    rec = re.search(r"struct LaunchRecord \{(.*?)\};", hpp, re.S).group(1)
+    assert tuple(re.findall(r"^\s*int64_t (\w+)", rec, re.M)) == quicfec_mod.LAUNCH_FIELDS
+
+
 def test_coalesce_stats_write_only_the_callers_struct(quicfec_mod):
     """FECCoalesceStats grew in round 5.  fec_coalesce_stats writes the 15
     words it was published with; fec_coalesce_stats_sized writes min(caller's size, this build's)

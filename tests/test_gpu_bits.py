@@ -62,7 +62,8 @@ def test_bits_tiles_and_chunks(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypatc
 def test_bits_is_the_default_for_c4(gpu_ctx, oracle_mod, torch_cuda, monkeypatch):
     """Without the switch, k=20 r=5 runs the bit-sliced form (r >= 4) and k=10 r=3 the tables;
     both exact.  The round trip through the decoder closes the check at a size the oracle
-    handles quickly."""
+    handles quickly.  Which form ran is asserted from the launch trace in
+    tests/test_gpu_forms.py::test_encode_matrix; here only the product library's bytes."""
     monkeypatch.delenv("QUICFEC_ENCODE_BITS", raising=False)
     for k, r in ((20, 5), (10, 3)):
         G, P = 4_099, 1200

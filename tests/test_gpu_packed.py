@@ -144,7 +144,9 @@ def test_packed_masks_at_odd_word(gpu_ctx, oracle_mod, torch_cuda):
 def test_chunked_launches(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypatch, api, k, r, P):
     """Launches split into chunks of QUICFEC_MAX_WAVE_BLOCKS workgroups (otherwise only past
     16.7M groups; a test-library switch): packed rows keep their global row starts in every
-    chunk, and the forms that take no record offsets get none in later chunks."""
+    chunk, and the forms that take no record offsets get none in later chunks.  (Bytes only; the
+    chunks themselves, and the wave kernel's, are read from the launch trace in
+    tests/test_gpu_forms.py.)"""
     gpu_ctx = gpu_ctx_hooks
     if k == 20 and api.startswith("packed"):
         pytest.skip("no packed form for the record-addressed shape")

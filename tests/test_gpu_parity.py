@@ -420,7 +420,9 @@ def test_full_size_c4_shard_encode(gpu_ctx, oracle_mod, torch_cuda):
 # the last column of a packet is shifted back to end at P (fec_kernels.hip header).  These
 # cases cover every encode form (compile-time k, runtime-k loop, gathered offsets) and every
 # decode form the library picks (fused with NT = 1..4 tail pieces, mask-addressed or not,
-# the runtime-k wave kernel), with sizes around the 16-B, 256-B and 1 KiB boundaries.
+# the runtime-k wave kernel), with sizes around the 16-B, 256-B and 1 KiB boundaries.  They
+# check bytes only; which form each (k, r, P) runs is asserted from the launch trace in
+# tests/test_gpu_forms.py.
 
 ANY_P = [(10, 3, 1201), (10, 3, 1350), (10, 3, 1400), (10, 3, 1452), (10, 3, 1500), (10, 3, 1023),
          (10, 3, 1025), (10, 3, 2047), (10, 3, 3001), (10, 3, 17), (10, 3, 31), (20, 5, 1399),
