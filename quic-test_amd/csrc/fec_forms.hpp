@@ -1,0 +1,467 @@
+// fec_forms.hpp — which kernel form a call runs: the launch descriptions, the lists of compiled
+// shapes and the rules that choose among them.  Host-only (no HIP include, no device code), so a
+// plain C++ program can ask for every packet size (tests/csrc/forms_dump.cpp).  The launchers of
+// fec_kernels.hip dispatch on what is decided here and expand the same lists.
+#pragma once
+
+#include <cstdint>
+
+#include "fec_knobs.hpp"
+
+namespace qfec {
+
+// Byte offsets of packets, when the data shards are not contiguous.
+// kAddr: `offsets` holds one absolute device address per packet (u64), `data` is unused --
+// the legacy-call coalescer (fec_coalesce.cpp) gathers packets from many callers' buffers.
+enum class OffsetKind : int { kNone = 0, kU32 = 1, kU64 = 2, kAddr = 3 };
+
+// Packets of any size P >= 16 at any byte address run on the 16-byte-column kernels
+// (fec_kernels.hip header); shorter ones on the byte kernels.
+struct EncodeLaunch {
+  const uint8_t* data;       // base of the data shards (device address)
+  const void* offsets;       // device u32/u64 offsets (k per group) or nullptr
+  OffsetKind off_kind;
+  uint8_t* parity;           // parity row (g, i) at (g * r + i) * P
+  uint64_t groups;
+  uint32_t k, r, P;
+  const void* tables;        // (r-1) x k CoefEntry (rows 1..r-1), device
+  int waves_per_cu = 0;      // occupancy cap of the streaming kernel (0 = tuned default)
+};
+
+struct LevelMeta {           // codebook levels e = 1..32 (see gf256.hpp)
+  uint64_t base[33];
+  uint64_t stride[33];
+  uint64_t count_r[33];      // C(r, e)
+};
+
+// Decode kernel selection (tests / probes; the library uses kDecodeAuto).
+constexpr int kDecodeAuto = 0;           // the measured best of the forms below
+constexpr int kDecodeWavePerGroup = 1;   // one wave per group, 16-B lanes only
+constexpr int kDecodeTiledPlain = 2;     // workgroup = whole groups, per-lane records
+constexpr int kDecodeTiledNt = 3;        //   same, non-temporal stores
+constexpr int kDecodeWavePlain = 4;      // one wave per group, 16-B passes + 4-B tail
+constexpr int kDecodeWaveNt = 5;         //   same, non-temporal stores (the default)
+constexpr int kDecodeWaveNoBranch = 6;   //   same, no branch on coefficient 0 / 1
+constexpr int kDecodeFused = 7;          // one wave per group, 16-B and 4-B pieces fused
+constexpr int kDecodeFusedDirect = 8;    //   same, survivor addresses from the erasure mask
+
+struct DecodeLaunch {
+  int variant = kDecodeAuto;
+  // Where rebuilt shards are stored, same layout as `data`; nullptr = in place in `data`.
+  // May be a device-visible pointer to page-locked host memory (zero-copy writes).
+  uint8_t* out = nullptr;
+  uint8_t* data;
+  const uint8_t* parity;
+  const uint64_t* masks;
+  uint32_t* rec_off;         // workspace, one u32 per group
+  uint8_t* status;           // nullable
+  const uint8_t* codebook;   // device
+  const uint64_t* binom;     // device, 65 x 65
+  LevelMeta meta;
+  uint64_t groups;
+  uint32_t k, r, P;
+  int waves_per_cu = 0;      // occupancy cap of the decode kernel (0 = tuned default)
+  bool rec_ready = false;    // rec_off already filled by the host (sparse plan): no classify
+  int xcd_swizzle = -1;      // XCD-aware group order: -1 tuned default, 0 off, 1 on
+  // Groups per wave of the mask-addressed decode (kDecodeScanGroups or 1).  One wave per
+  // group is best when most groups lost data (C3: 5.35 TB/s vs 4.92 at 8 per wave); when few
+  // did (C5, iid 1% loss: ~10% of groups) 8 per wave saves the dispatch and mask-load latency
+  // of the waves that find nothing to do (0.257 -> 0.243 ms per 1M groups,
+  // profiles/r02_probe_decode_scan.txt).  The host paths that know the masks pick it.
+  uint32_t scan = 1;
+  // `codebook` holds coefficient bytes (compact layout, gf256.hpp) rather than CoefEntry
+  // tables: set exactly when decode_form(*this).compact_tables (launch_decode checks).
+  bool compact_tables = false;
+  // Rebuilt shards go to out + (g * r + m) * P (m-th lost data shard of group g, ascending),
+  // `data` is only read (fec_recover_batch_rs_dev); else in place / at `out` like `data`.
+  bool compact_out = false;
+  // compact_out with rec_off = the packed rows' row_start (fec_recover_batch_rs_dev_packed):
+  // rows are placed by global row index, so chunked launches must not offset `out`.
+  bool packed_rows = false;
+};
+
+constexpr uint32_t kDecodeScanGroups = 8;
+// Share of groups needing a rebuild below which the host paths use the scan form.
+constexpr double kDecodeScanMaxShare = 0.25;
+
+// Packed recover in one launch (recover_runs, fec_kernels.hip): every workgroup owns 512
+// consecutive groups, finds its run's first row by decoupled look-back (no prefix launches)
+// and writes its rebuilt rows as one contiguous run, staged through an LDS image of up to
+// stage bytes.  Mask-addressed shapes only (runs_supported).
+struct RunsLaunch {
+  const uint8_t* data;
+  const uint8_t* parity;
+  const uint64_t* masks;
+  uint64_t groups;
+  uint32_t k, r, P;
+  const uint8_t* codebook;   // dense CoefEntry codebook (the mask-addressed decode's)
+  LevelMeta meta;
+  uint8_t* out;              // packed rows
+  uint32_t* row_start;       // one u32 per group (written)
+  uint64_t* total;           // nullable: all rows
+  uint8_t* status;           // nullable
+  // runs_workspace_bytes(groups) of device memory, zeroed when first allocated, kept by the
+  // caller stream: ticket counter, chunk totals, look-back words
+  void* workspace;
+  // look-back epoch of the first launch; a call takes runs_launches(groups) epochs, never
+  // reused while the workspace lives (the caller counts; < 2^30, then re-zero the workspace)
+  uint32_t epoch;
+  int stage_bytes = -1;      // LDS run image: -1 tuned default (test switch kRunsStage), 0 none
+};
+
+// Memory policy bits of the streaming kernels.
+constexpr int kNtLoad = 1;        // non-temporal loads (data read once)
+constexpr int kNtStore = 2;       // non-temporal stores
+constexpr int kNoCoefBranch = 4;  // decode: multiply by every coefficient, no 0/1 branches
+// decode_fused: coefficient tables through LDS.  A record-addressed wave reads e*K 32-B
+// table entries of its group's record.  For large codebooks (k=20 r=5: 53,130 records,
+// 143 MB) the records miss the scalar cache, and one scalar load per coefficient — a few
+// in flight at a time — stalls the wave for several memory round trips per group.  With
+// this bit the wave fetches its rows with vector loads issued next to its survivor loads
+// (one round trip) and reads them from a per-wave LDS slice.
+constexpr int kLdsTabs = 64;
+// decode_fused / decode_wave: the m-th rebuilt shard of group g (erased data shards in
+// ascending order) goes to out + (g * r + m) * P -- one contiguous run of rebuilt packets
+// per group, groups back to back, like encode's parity rows -- instead of its place among
+// the group's data shards (fec_recover_batch_rs_dev).  Measured at k=10 r=3, 2 erasures:
+// 2.32 vs 2.47 ms in place (profiles/r02_probe_decode_compact_out.txt).
+constexpr int kCompactOut = 1024;
+// decode_fused with kLdsTabs: the record holds bare coefficient bytes (compact codebook,
+// gf256.hpp) and the wave computes each coefficient's tables into its LDS slice
+// (coef_tables.hpp) instead of copying 32-byte table entries in: k=20 r=5 records shrink
+// from up to 3.3 KB to 256 B, the whole codebook from 143 MB to 12 MB.
+constexpr int kCoefBytes = 2048;
+// encode_v16: coefficients taken two at a time, so every 3-input XOR (v_bitop3) folds two
+// new table products into the accumulator: 6 v_perm + 3 v_bitop3 per pair of coefficients
+// and dword instead of 6 v_perm + 2 v_bitop3 + 2 v_xor, and one v_bitop3 per pair on the
+// XOR row instead of two v_xor.
+constexpr int kPairMac = 4096;
+// encode_v16 / encode_bits (tiled, P % 16 == 0, every row of the code in this launch): the
+// workgroup's parity rows -- one contiguous window of tile * R * P bytes in HBM -- are staged in
+// the LDS the launch already reserves for its occupancy cap and stored by consecutive lanes as
+// consecutive 16-B pieces, so only the window's two end lines are partial.  Stored by the lanes
+// that computed them, a 1200-B row starts 48 B into a 128-B line and one store instruction
+// covers the end of one group's row and the start of another's: each row's edge lines leave as
+// pieces of different instructions (PMC writes 1.046x algorithmic at k=10 r=3, 1.053x at k=20
+// r=5).
+constexpr int kStageRows = 8192;
+constexpr int kEncodeStageDefault = 1;  // on: C2 encode 2.753 -> 2.659 ms, C4 5.578 -> 5.520 (profiles/r05a)
+
+constexpr uint32_t kVecMinP = 16;  // shorter packets take the byte kernels
+// Packets of at most this size decode in the tiled form (several groups per wave).
+constexpr uint32_t kTiledMaxP = 256;
+
+// ---- the compiled shapes, each list stated once ----
+// A list macro calls M(extra..., k, r) per shape (M(extra..., nm, nt) per layout); the predicates
+// below, the launchers' dispatch and the test program's --compiled list are expansions of these.
+// Mask-addressed decode_fused and recover_runs.  r <= 3 shapes only in the mask-addressed form
+// (the one auto uses for them), r > 3 only in the record-addressed one; k=10 r=3 1200 B in both
+// (probes).
+#define QFEC_MASK_SHAPES(M, ...) M(__VA_ARGS__, 10, 3) M(__VA_ARGS__, 10, 1) M(__VA_ARGS__, 10, 2) M(__VA_ARGS__, 4, 2)
+// k=10 r=3 (the BASELINE shape) also has the scan form, for sparse loss (DecodeLaunch::scan)
+#define QFEC_SCAN_SHAPES(M, ...) M(__VA_ARGS__, 10, 3)
+// The r > 3 record-addressed forms stage their tables
+// through LDS (kLdsTabs): k=20 r=5, 5 erasures, 1200 B: 2.27 -> 4.73-4.92 TB/s
+// (profiles/r01_probe_decode_ldstabs_k20.txt); at k=10 r=3, whose 286 records stay in the
+// scalar cache, it gains nothing (profiles/r01_probe_decode_inline_k10.txt).
+#define QFEC_LDS_SHAPES(M, ...) M(__VA_ARGS__, 20, 5)
+// Record-addressed with CoefEntry records (host-built records, probes): one shape at one layout.
+#define QFEC_RECORD_FORMS(M, ...) M(__VA_ARGS__, 10, 3, 1, 1)
+#define QFEC_TILED_SHAPES(M, ...) M(__VA_ARGS__, 10, 3) M(__VA_ARGS__, 10, 1) M(__VA_ARGS__, 20, 5) M(__VA_ARGS__, 4, 2)
+// compile-time-k decode_wave (and the probes' decode_v16)
+#define QFEC_WAVE_SHAPES(M, ...) QFEC_TILED_SHAPES(M, __VA_ARGS__)
+// probes only: decode_wave without the branch on coefficients 0 / 1
+#define QFEC_WAVE_NB_SHAPES(M, ...) M(__VA_ARGS__, 10, 3) M(__VA_ARGS__, 20, 5)
+// The piece layouts of decode_fused and recover_runs.
+// Instantiated for every P in [16, 2047] of the compiled (k, r) shapes: NM = P / 1024 16-B and
+// NT = ceil((P % 1024) / 256) 4-B pieces per lane, (NM, NT) in (0,1..4), (1,0..4); P = 2048 would
+// be (2,0), which is not instantiated, so 2048 and up take the wave kernel.  P <= 256 is the one
+// 4-B piece (0,1): the shapes with a tiled form decode such packets there in both layouts, so of
+// the mask-addressed (0,1) forms only k=10 r=2's compact one is ever launched (recover layouts);
+// k=10 r=2 in place at P <= 256 goes to the runtime-k wave kernel (a known slow
+// path).
+// Measured at k=10 r=3, 2 erasures (tools/probe_decode.hip): 512 B 5.89 TB/s vs 3.12 for
+// the looped wave kernel, 768 B 5.49 vs 3.24 (profiles/r01_probe_decode_small.txt).
+#define QFEC_LAYOUTS(M, ...)                                                                      \
+  M(__VA_ARGS__, 0, 1) M(__VA_ARGS__, 0, 2) M(__VA_ARGS__, 0, 3) M(__VA_ARGS__, 0, 4) M(__VA_ARGS__, 1, 0) \
+  M(__VA_ARGS__, 1, 1) M(__VA_ARGS__, 1, 2) M(__VA_ARGS__, 1, 3) M(__VA_ARGS__, 1, 4)
+
+#define QFEC_IS_PAIR(_, A, B) || (a == A && b == B)
+constexpr bool is_mask_shape(uint32_t a, uint32_t b) { return false QFEC_MASK_SHAPES(QFEC_IS_PAIR, ~); }
+constexpr bool is_scan_shape(uint32_t a, uint32_t b) { return false QFEC_SCAN_SHAPES(QFEC_IS_PAIR, ~); }
+constexpr bool is_lds_shape(uint32_t a, uint32_t b) { return false QFEC_LDS_SHAPES(QFEC_IS_PAIR, ~); }
+constexpr bool is_tiled_shape(uint32_t a, uint32_t b) { return false QFEC_TILED_SHAPES(QFEC_IS_PAIR, ~); }
+constexpr bool is_wave_shape(uint32_t a, uint32_t b) { return false QFEC_WAVE_SHAPES(QFEC_IS_PAIR, ~); }
+constexpr bool is_wave_nb_shape(uint32_t a, uint32_t b) { return false QFEC_WAVE_NB_SHAPES(QFEC_IS_PAIR, ~); }
+constexpr bool is_layout(uint32_t a, uint32_t b) { return false QFEC_LAYOUTS(QFEC_IS_PAIR, ~); }
+#undef QFEC_IS_PAIR
+#define QFEC_IS_QUAD(_, K, R, A, B) || (k == K && r == R && nm == A && nt == B)
+constexpr bool is_record_form(uint32_t k, uint32_t r, uint32_t nm, uint32_t nt) {
+  return false QFEC_RECORD_FORMS(QFEC_IS_QUAD, ~);
+}
+#undef QFEC_IS_QUAD
+
+struct Layout {
+  uint32_t nm, nt;  // 16-B and 4-B pieces per lane
+};
+constexpr Layout layout_of(uint32_t P) { return {P / 1024u, (P % 1024u + 255u) / 256u}; }
+constexpr bool has_layout(uint32_t P) { return P >= kVecMinP && is_layout(layout_of(P).nm, layout_of(P).nt); }
+static_assert(has_layout(16) && has_layout(2047) && !has_layout(15) && !has_layout(2048) && !has_layout(4096),
+              "a layout exists for 16 <= P <= 2047");
+
+// The kernel instantiations of the product library's decode dispatch, X(kernel, K, MAXE, NM, NT,
+// POL, DIRECT, SCAN); QFEC_PROBE_DECODE_FORMS: those only the probes select (compiled with
+// QUICFEC_PROBE_FORMS); QFEC_RUNS_FORMS: recover_runs, X(K, R, NM, NT).
+// The mask-addressed forms also load non-temporally (survivors are read once): +1.2..3.2% at
+// 512 / 768 / 1200 / 1400 B in one process (profiles/r01_probe_decode_ntload.txt); loads
+// alone without NT stores lose 14%.
+#define QFEC_FORM_MASK(X, K, R, NM, NT)                        \
+  X(kFused, K, R, NM, NT, kNtStore | kNtLoad, true, 0) X(kFused, K, R, NM, NT, kNtStore | kNtLoad | kCompactOut, true, 0)
+#define QFEC_FORM_SCAN(X, K, R, NM, NT)                                \
+  X(kFused, K, R, NM, NT, kNtStore | kNtLoad, true, kDecodeScanGroups) \
+  X(kFused, K, R, NM, NT, kNtStore | kNtLoad | kCompactOut, true, kDecodeScanGroups)
+#define QFEC_FORM_LDS(X, K, R, NM, NT)                                           \
+  X(kFused, K, R, NM, NT, kNtStore | kNtLoad | kLdsTabs | kCoefBytes, false, 0) \
+  X(kFused, K, R, NM, NT, kNtStore | kNtLoad | kLdsTabs | kCoefBytes | kCompactOut, false, 0)
+#define QFEC_FORM_RECORD(X, K, R, NM, NT) X(kFused, K, R, NM, NT, kNtStore, false, 0)
+#define QFEC_FORM_TILED(X, K, R) X(kTiled, K, R, 0, 0, kNtStore, false, 0) X(kTiled, K, R, 0, 0, kNtStore | kCompactOut, false, 0)
+#define QFEC_FORM_WAVE(X, K, R) X(kWave, K, R, 0, 0, kNtStore, false, 0)
+#define QFEC_FORM_RUNS(X, K, R, NM, NT) X(K, R, NM, NT)
+#define QFEC_MASK_LAYOUTS(X, K, R) QFEC_LAYOUTS(QFEC_FORM_MASK, X, K, R)
+#define QFEC_SCAN_LAYOUTS(X, K, R) QFEC_LAYOUTS(QFEC_FORM_SCAN, X, K, R)
+#define QFEC_LDS_LAYOUTS(X, K, R) QFEC_LAYOUTS(QFEC_FORM_LDS, X, K, R)
+#define QFEC_RUNS_LAYOUTS(X, K, R) QFEC_LAYOUTS(QFEC_FORM_RUNS, X, K, R)
+#define QFEC_DECODE_FORMS(X)                                                                      \
+  QFEC_MASK_SHAPES(QFEC_MASK_LAYOUTS, X) QFEC_SCAN_SHAPES(QFEC_SCAN_LAYOUTS, X)                   \
+  QFEC_LDS_SHAPES(QFEC_LDS_LAYOUTS, X) QFEC_RECORD_FORMS(QFEC_FORM_RECORD, X)                     \
+  QFEC_TILED_SHAPES(QFEC_FORM_TILED, X) QFEC_WAVE_SHAPES(QFEC_FORM_WAVE, X)                       \
+  X(kWave, 0, 8, 0, 0, kNtStore | kNoCoefBranch, false, 0)                                        \
+  X(kWave, 0, 8, 0, 0, kNtStore | kNoCoefBranch | kCompactOut, false, 0)                          \
+  X(kBytes, 0, 0, 0, 0, 0, false, 0) X(kBytes, 0, 0, 0, 0, kCompactOut, false, 0)
+#define QFEC_RUNS_FORMS(X) QFEC_MASK_SHAPES(QFEC_RUNS_LAYOUTS, X)
+#define QFEC_FORM_TILED_PLAIN(X, K, R) X(kTiled, K, R, 0, 0, 0, false, 0)
+#define QFEC_FORM_WAVE_PLAIN(X, K, R) X(kWave, K, R, 0, 0, 0, false, 0) X(kV16, K, R, 0, 0, 0, false, 0)
+#define QFEC_FORM_WAVE_NB(X, K, R) X(kWave, K, R, 0, 0, kNtStore | kNoCoefBranch, false, 0)
+#define QFEC_PROBE_DECODE_FORMS(X)                                                                \
+  QFEC_TILED_SHAPES(QFEC_FORM_TILED_PLAIN, X) QFEC_WAVE_SHAPES(QFEC_FORM_WAVE_PLAIN, X)           \
+  QFEC_WAVE_NB_SHAPES(QFEC_FORM_WAVE_NB, X) X(kWave, 0, 8, 0, 0, 0, false, 0) X(kV16, 0, 8, 0, 0, 0, false, 0)
+// The compile-time encodes, X(K, R, OFF, POL) (the runtime-k passes and the byte kernel are the
+// launcher's): encode_v16 and encode_bits (W = 4).
+#define QFEC_ENCODE_V16_FORMS(X)                                                                  \
+  X(10, 3, 0, kNtStore | kPairMac) X(10, 3, 0, kNtStore | kPairMac | kStageRows) X(10, 2, 0, kNtStore | kPairMac) \
+  X(10, 2, 0, kNtStore | kPairMac | kStageRows) X(20, 5, 0, kNtStore | kPairMac) X(10, 1, 0, kNtStore)            \
+  X(4, 2, 0, kNtStore) X(10, 1, 1, kNtStore) X(10, 1, 3, kNtStore)
+#define QFEC_ENCODE_BITS_FORMS(X) \
+  X(20, 5, 0, kNtStore) X(20, 5, 0, kNtStore | kStageRows) X(10, 3, 0, kNtStore) X(10, 3, 0, kNtStore | kStageRows)
+
+// Groups per workgroup for the tiled mapping: the fewest idle lanes (workgroup = whole
+// waves), preferring tiles whose byte size is a multiple of 128 (tile starts stay
+// cache-line aligned).  0 = use the flat mapping (columns per packet > 512).
+inline uint32_t pick_tile(uint32_t cpp, uint32_t k, uint32_t P) {
+  if (cpp == 0 || cpp > 512) return 0;
+  const uint32_t tmax = 512 / cpp;
+  uint32_t best = 1;
+  double best_score = 1e9;
+  for (uint32_t t = 1; t <= tmax; ++t) {
+    const uint32_t lanes = t * cpp, bs = (lanes + 63) / 64 * 64;
+    double score = double(bs - lanes) / bs;
+    if ((uint64_t(t) * k * P) % 128 != 0) score += 0.05;
+    if (bs < 256) score += 0.02;
+    if (score < best_score - 1e-9) {
+      best_score = score;
+      best = t;
+    }
+  }
+  return best;
+}
+
+// ---- decode ----
+enum class DecodeKernel : int { kNone = 0, kBytes, kTiled, kFused, kWave, kV16 };
+
+// Everything launch_decode and its caller need to know about one call.
+struct DecodeForm {
+  DecodeKernel kernel = DecodeKernel::kNone;  // kNone: no groups, nothing to launch
+  int K = 0, MAXE = 0;          // template shape; runtime k as K = 0, MAXE = 8
+  int NM = 0, NT = 0;           // decode_fused: piece layout
+  int POL = 0;
+  bool DIRECT = false;          // decode_fused: mask-addressed, classifies inline
+  int SCAN = 0;                 // decode_fused: groups per wave of the scan form, 0 = one wave per group
+  uint32_t tile = 0;            // decode_tiled: groups per workgroup
+  bool classify = false;        // a classify launch precedes the kernel
+  bool rec_off = false;         // reads the rec_off workspace (every form but the mask-addressed
+                                // one): the caller then provides a workspace private to the call
+  bool compact_tables = false;  // reads a compact codebook (coefficient bytes)
+};
+
+// The form launch_decode(a) runs.  A form that is compiled only with QUICFEC_PROBE_FORMS (a
+// probe's variant; the library never sets one) is named here too: the product library's
+// dispatch answers it with hipErrorNotSupported.
+inline DecodeForm decode_form(const DecodeLaunch& a) {
+  using DK = DecodeKernel;
+  DecodeForm f;
+  if (a.groups == 0) return f;
+  const int compact = a.compact_out ? kCompactOut : 0;
+  const auto pick = [&f](DK kernel, uint32_t k, uint32_t maxe, int pol) {
+    f.kernel = kernel, f.K = static_cast<int>(k), f.MAXE = static_cast<int>(maxe), f.POL = pol;
+    return f;
+  };
+  f.classify = !a.rec_ready;
+  f.rec_off = true;
+  if (a.P < kVecMinP) return pick(DK::kBytes, 0, 0, compact);
+  const Layout lay = layout_of(a.P);
+  f.tile = pick_tile((a.P + 15u) / 16u, a.k, a.P);
+  // The tiled route: the compact recover layout only where a tiled form is compiled; elsewhere
+  // the fused or wave forms write it.  In place, a shape without a tiled form still takes this
+  // route and falls through to its wave kernel below (k=10 r=2 at P <= 256, the known slow path).
+  // auto leaves k=20 r=5 to the LDS-table fused form (P=200: 4.6 vs 2.8 TB/s, same box)
+  const bool auto_tiled = a.variant == kDecodeAuto && a.P <= kTiledMaxP && !is_lds_shape(a.k, a.r);
+  const bool tiled = !(a.compact_out && !is_tiled_shape(a.k, a.r)) && f.tile > 0 &&
+                     (auto_tiled || a.variant == kDecodeTiledPlain || a.variant == kDecodeTiledNt);
+  // Mask-addressed fused form (r <= 3): +1.2% at k=10 r=3 (tools/probe_decode.hip,
+  // r01_probe_decode_direct.txt); at k=20 r=5 its extra VGPRs cost a wave per SIMD (-30%), so
+  // auto takes it for r <= 3 only.  It classifies inline: one launch, no classify kernel.
+  if (!tiled && a.masks != nullptr && !a.rec_ready &&
+      (a.variant == kDecodeFusedDirect || (a.variant == kDecodeAuto && a.r <= 3)) && is_mask_shape(a.k, a.r) &&
+      has_layout(a.P)) {
+    f.classify = f.rec_off = false;
+    f.NM = static_cast<int>(lay.nm), f.NT = static_cast<int>(lay.nt), f.DIRECT = true;
+    f.SCAN = is_scan_shape(a.k, a.r) && a.scan == kDecodeScanGroups ? static_cast<int>(kDecodeScanGroups) : 0;
+    return pick(DK::kFused, a.k, a.r, kNtStore | kNtLoad | compact);
+  }
+  // packets <= 256 B: the tiled form (several groups per wave); plain stores are probe-only
+  if (tiled && is_tiled_shape(a.k, a.r))
+    return pick(DK::kTiled, a.k, a.r, (a.compact_out || a.variant != kDecodeTiledPlain ? kNtStore : 0) | compact);
+  // Fused passes win where many rows share each survivor (k=20 r=5, 5 losses: +21%); with
+  // the XCD-aware order they also win at r = 3 (+2.6%; tools/probe_decode.hip), so auto
+  // takes them wherever they are instantiated.
+  if ((a.variant == kDecodeFused || a.variant == kDecodeAuto || a.variant == kDecodeFusedDirect) && has_layout(a.P)) {
+    f.NM = static_cast<int>(lay.nm), f.NT = static_cast<int>(lay.nt);
+    if (!a.compact_out && is_record_form(a.k, a.r, lay.nm, lay.nt)) return pick(DK::kFused, a.k, a.r, kNtStore);
+    if (is_lds_shape(a.k, a.r)) {
+      f.compact_tables = !a.rec_ready;  // host-built records are CoefEntry tables
+      return pick(DK::kFused, a.k, a.r, kNtStore | kNtLoad | kLdsTabs | kCoefBytes | compact);
+    }
+    f.NM = f.NT = 0;
+  }
+  // everything else: the wave kernel; compact only at runtime k
+  if (a.compact_out) return pick(DK::kWave, 0, 8, kNtStore | kNoCoefBranch | kCompactOut);
+  // Probe-only forms (tools/probe_decode.hip sets DecodeLaunch::variant; the library never does):
+  // no branch on coefficients 0 / 1, the plain-store wave kernel, 16-B lanes only (decode_v16).
+  const bool separate_out = a.out != nullptr && a.out != a.data;  // decode_v16 lacks it
+  if (a.variant == kDecodeWaveNoBranch && !separate_out && is_wave_nb_shape(a.k, a.r))
+    return pick(DK::kWave, a.k, a.r, kNtStore | kNoCoefBranch);
+  if (a.variant == kDecodeWavePerGroup && !separate_out)
+    return is_wave_shape(a.k, a.r) ? pick(DK::kV16, a.k, a.r, 0) : pick(DK::kV16, 0, 8, 0);
+  const bool nt = a.variant != kDecodeWavePlain;
+  if (is_wave_shape(a.k, a.r)) return pick(DK::kWave, a.k, a.r, nt ? kNtStore : 0);
+  // Runtime k: multiplying by every coefficient (no branches on 0 / 1) wins at every shape
+  // measured (tools/probe_decode.hip, profiles/r01_probe_decode_runtime_k.txt): k=10 r=2
+  // 4.13 -> 4.79 TB/s, 12+6 2.62 -> 3.20, 16+4 2.67 -> 3.40.  Its tables staged through
+  // LDS (kLdsTabs) lose here (2.2-2.8 TB/s): the records of these codebooks are hit often
+  // enough in the scalar cache, and the wait for the tables precedes the survivor loads.
+  return pick(DK::kWave, 0, 8, nt ? kNtStore | kNoCoefBranch : 0);
+}
+
+// (k, r, P) shapes with a compiled recover_runs: the mask-addressed decode's, 256 < P <= 2047
+// or 16 <= P <= 256 with one 4-B piece (the packed call reaches the latter only for k=10 r=2:
+// the other shapes' short packets are refused, their slot layout being the tiled form's).
+constexpr bool runs_supported(uint32_t k, uint32_t r, uint32_t P) { return is_mask_shape(k, r) && has_layout(P); }
+
+// What fec_recover_batch_rs_dev_packed does with call `a` (compact_out and the scan setting
+// set, rec_off and packed_rows not yet) of form f = decode_form(a); `runs_switch` is the test
+// library's TestKnob::kPackedRuns (-1 unset).
+enum class PackedForm : int { kRefused, kRuns, kPrefixFused };
+inline PackedForm packed_form(const DecodeLaunch& a, const DecodeForm& f, long runs_switch) {
+  // packed rows: only the mask-addressed (inline-classify) forms place rows by row_start,
+  // which they read from rec_off
+  if (a.rec_ready || f.rec_off) return PackedForm::kRefused;
+  // Sparse loss (the scan form's share): one launch, recover_runs --
+  // each workgroup finds its rows' place by decoupled look-back and writes them as one run
+  // (C5: 0.229-0.235 vs 0.242-0.268 ms for the slot rows; profiles/r04_probe_runs_*.txt).
+  // Dense loss keeps the prefix launches + decode_fused (the runs form rebuilds a workgroup's
+  // groups wave by wave: 2.7-2.8 vs 2.2-2.45 ms at C3).  The test library's
+  // TestKnob::kPackedRuns forces it on (1) or off (0).
+  if (runs_switch != 0 && (runs_switch == 1 || a.scan == kDecodeScanGroups) && runs_supported(a.k, a.r, a.P))
+    return PackedForm::kRuns;
+  return PackedForm::kPrefixFused;
+}
+
+// ---- encode ----
+enum class EncodeKernel : int { kBytes, kV16, kBits };
+
+struct EncodeForm {
+  EncodeKernel kernel;
+  int K, R;       // template shape; K = 0: runtime k (the launcher's passes of up to 8 rows), R unused
+  int OFF;        // OffsetKind of the instantiation
+  int POL;
+  uint32_t tile;  // groups per workgroup (encode_bits: per half), 0 = flat mapping
+};
+
+// Groups per workgroup of the tiled encodes (encode_bits: per half): pick_tile (the test
+// library's TestKnob::kEncodeTile overrides it when the tile fits 512 lanes).
+inline uint32_t encode_tile(const EncodeLaunch& a) {
+  const uint32_t cpp = (a.P + 15u) / 16u;
+  const long tile_env = test_knob(TestKnob::kEncodeTile, 0);
+  return tile_env > 0 && cpp > 0 && uint32_t(tile_env) * cpp <= 512 ? uint32_t(tile_env) : pick_tile(cpp, a.k, a.P);
+}
+
+// Bit-sliced encode for a compile-time shape where it is faster than the tables (r >= 4: the
+// table form is VALU-bound there); the test library's TestKnob::kEncodeBits forces it on (1,
+// every compiled shape) or off (0).
+inline bool use_encode_bits(uint32_t r) {
+  const long mode = test_knob(TestKnob::kEncodeBits, -1);
+  return mode == 1 || (mode < 0 && r >= 4);
+}
+
+// kStageRows for a launch whose workgroup window (groups_per_block * r * P bytes) fits the LDS a
+// workgroup may take (the test library's TestKnob::kEncodeStage: 1 on, 0 off).  A flat launch
+// (P > 8192, groups_per_block 0) passes too: it runs the kStageRows instantiation, whose kernel
+// stages only when tiled and otherwise stores directly.
+inline bool use_stage_rows(const EncodeLaunch& a, uint32_t groups_per_block) {
+  const long mode = test_knob(TestKnob::kEncodeStage, kEncodeStageDefault);
+  return mode == 1 && a.P % 16 == 0 && uint64_t(groups_per_block) * a.r * a.P <= 64u * 1024u;
+}
+
+// The form launch_encode(a) runs.
+inline EncodeForm encode_form(const EncodeLaunch& a) {
+  EncodeForm f{EncodeKernel::kBytes, 0, 0, static_cast<int>(a.off_kind), 0, 0};
+  if (a.P < kVecMinP) return f;
+  f.kernel = EncodeKernel::kV16, f.POL = kNtStore, f.tile = encode_tile(a);
+  const auto shape = [&a](uint32_t k, uint32_t r) { return a.k == k && a.r == r; };
+  const auto pick = [&f, &a](int pol) {
+    f.K = static_cast<int>(a.k), f.R = static_cast<int>(a.r), f.POL = pol;
+    return f;
+  };
+  // A compile-time encode in its staged form (kStageRows) where the workgroup's window fits
+  // (use_stage_rows), else with POL's direct stores.
+  const auto staged = [&a](uint32_t groups_per_block) { return use_stage_rows(a, groups_per_block) ? kStageRows : 0; };
+  if (a.off_kind == OffsetKind::kNone) {
+    // The paired-coefficient arithmetic (kPairMac): +0.9% at k=20 r=5 (5.53 vs 5.58 ms),
+    // +1.0% at k=10 r=3 (2.65 vs 2.68 ms), same box, alternating runs
+    // (profiles/r02_ab_encode_pair.txt).  Staged rows keep the default cache policy, NT stores
+    // with cached loads (C2 2.590 ms vs 2.606-2.702, C4 4.991 vs 5.062-5.345 for the other
+    // three; profiles/r05k/sweep_mempol.jsonl).
+    // Bit-sliced form (bitslice.hpp) while a workgroup holds whole groups.  k=20 r=5 (VALU-
+    // bound with the tables): 5.24-5.41 vs 5.37-5.54 ms over six boxes; k=10 r=3 (HBM-bound
+    // with the tables) 2.74-2.76 vs 2.63-2.66 ms, so not chosen there.  4 packets in flight per
+    // lane (2: 5.70 ms, 8: 5.28, 20: 5.91-6.03; profiles/r03_ab_bits.txt).
+    if (a.P <= 8192 && use_encode_bits(a.r) && (shape(20, 5) || shape(10, 3))) {
+      f.kernel = EncodeKernel::kBits;
+      return pick(kNtStore | staged(2 * f.tile));
+    }
+    if (shape(10, 3)) return pick(kNtStore | kPairMac | staged(f.tile));
+    // staged rows measured per shape (scripts/ab_stage_rows.py, profiles/r05k): k=10 r=1 level
+    // (2.383 vs 2.378 ms), k=10 r=2 -1.5% (2.537 vs 2.575), k=4 r=2 +8.9% (1.351 vs 1.241): the
+    // XOR row and k=4 keep their direct stores
+    if (shape(10, 1) || shape(4, 2)) return pick(kNtStore);
+    if (shape(20, 5)) return pick(kNtStore | kPairMac);
+    // k=10 r=2 (the campaign's 20% FEC rate): compile-time k (2.50 vs 2.56 ms for the runtime-k
+    // loop, profiles/r02_ab_encode_r1r2_defaults.txt)
+    if (shape(10, 2)) return pick(kNtStore | kPairMac | staged(f.tile));
+  } else if ((a.off_kind == OffsetKind::kU32 || a.off_kind == OffsetKind::kAddr) && shape(10, 1)) {
+    return pick(kNtStore);  // the legacy call's and the coalescer's instantiations
+  }
+  return f;  // runtime k
+}
+
+}  // namespace qfec

@@ -32,14 +32,6 @@
 #include "fec_kernels.hpp"
 #include "fec_knobs.hpp"
 
-// Forms only the probes (tools/probe_*.hip, built with -DQUICFEC_PROBE_FORMS) select: the
-// library's own choice never reaches them, so the product library does not carry them.
-#ifdef QUICFEC_PROBE_FORMS
-#define QFEC_PROBE_ONLY(...) (__VA_ARGS__)
-#else
-#define QFEC_PROBE_ONLY(...) hipErrorNotSupported
-#endif
-
 namespace qfec {
 namespace {
 
@@ -53,43 +45,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
 typedef uint32_t u32u __attribute__((aligned(1)));
 
-// Memory policy bits of the streaming kernels.
-constexpr int kNtLoad = 1;        // non-temporal loads (data read once)
-constexpr int kNtStore = 2;       // non-temporal stores
-constexpr int kNoCoefBranch = 4;  // decode: multiply by every coefficient, no 0/1 branches
-// decode_fused: coefficient tables through LDS.  A record-addressed wave reads e*K 32-B
-// table entries of its group's record.  For large codebooks (k=20 r=5: 53,130 records,
-// 143 MB) the records miss the scalar cache, and one scalar load per coefficient — a few
-// in flight at a time — stalls the wave for several memory round trips per group.  With
-// this bit the wave fetches its rows with vector loads issued next to its survivor loads
-// (one round trip) and reads them from a per-wave LDS slice.
-constexpr int kLdsTabs = 64;
-// decode_fused / decode_wave: the m-th rebuilt shard of group g (erased data shards in
-// ascending order) goes to out + (g * r + m) * P -- one contiguous run of rebuilt packets
-// per group, groups back to back, like encode's parity rows -- instead of its place among
-// the group's data shards (fec_recover_batch_rs_dev).  Measured at k=10 r=3, 2 erasures:
-// 2.32 vs 2.47 ms in place (profiles/r02_probe_decode_compact_out.txt).
-constexpr int kCompactOut = 1024;
-// decode_fused with kLdsTabs: the record holds bare coefficient bytes (compact codebook,
-// gf256.hpp) and the wave computes each coefficient's tables into its LDS slice
-// (coef_tables.hpp) instead of copying 32-byte table entries in: k=20 r=5 records shrink
-// from up to 3.3 KB to 256 B, the whole codebook from 143 MB to 12 MB.
-constexpr int kCoefBytes = 2048;
-// encode_v16: coefficients taken two at a time, so every 3-input XOR (v_bitop3) folds two
-// new table products into the accumulator: 6 v_perm + 3 v_bitop3 per pair of coefficients
-// and dword instead of 6 v_perm + 2 v_bitop3 + 2 v_xor, and one v_bitop3 per pair on the
-// XOR row instead of two v_xor.
-constexpr int kPairMac = 4096;
-// encode_v16 / encode_bits (tiled, P % 16 == 0, every row of the code in this launch): the
-// workgroup's parity rows -- one contiguous window of tile * R * P bytes in HBM -- are staged in
-// the LDS the launch already reserves for its occupancy cap and stored by consecutive lanes as
-// consecutive 16-B pieces, so only the window's two end lines are partial.  Stored by the lanes
-// that computed them, a 1200-B row starts 48 B into a 128-B line and one store instruction
-// covers the end of one group's row and the start of another's: each row's edge lines leave as
-// pieces of different instructions (PMC writes 1.046x algorithmic at k=10 r=3, 1.053x at k=20
-// r=5).
-constexpr int kStageRows = 8192;
-constexpr int kEncodeStageDefault = 1;  // on: C2 encode 2.753 -> 2.659 ms, C4 5.578 -> 5.520 (profiles/r05a)
+// The memory policy / form bits of the kernels' POL parameter (kNtLoad .. kStageRows): fec_forms.hpp.
 
 template <int POL>
 __device__ __forceinline__ u32x4 ld16(const uint8_t* p) {
@@ -2268,7 +2224,6 @@ uint64_t groups_per_launch(uint32_t per_group) {
   const uint64_t n = max_launch_threads() / (per_group ? per_group : 1u);
   return n ? n : 1;
 }
-constexpr uint32_t kVecMinP = 16;  // shorter packets take the byte kernels
 
 inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + 255) / 256); }
 
@@ -2283,10 +2238,22 @@ LaunchRecord launch_record(LaunchForm form, uint64_t grid, uint32_t block, uint6
   return t;
 }
 
+// Walks `n` items in pieces of at most `per`: launch(first, count) traces and launches one
+// piece; stops at the first launch error.
+template <typename F>
+hipError_t for_chunks(uint64_t n, uint64_t per, F launch) {
+  for (uint64_t i0 = 0; i0 < n; i0 += per) {
+    launch(i0, n - i0 < per ? n - i0 : per);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------
-// Launchers
+// Launchers: which form a call takes is decided in fec_forms.hpp; these only launch it.
 // ---------------------------------------------------------------------------------
 namespace {
 
@@ -2299,44 +2266,12 @@ uint32_t decode_swizzle(const DecodeLaunch& a, int tuned) {
   return static_cast<uint32_t>(a.xcd_swizzle >= 0 ? a.xcd_swizzle : tuned);
 }
 
-
-// Groups per workgroup for the tiled mapping: the fewest idle lanes (workgroup = whole
-// waves), preferring tiles whose byte size is a multiple of 128 (tile starts stay
-// cache-line aligned).  0 = use the flat mapping (columns per packet > 512).
-uint32_t pick_tile(uint32_t cpp, uint32_t k, uint32_t P) {
-  if (cpp == 0 || cpp > 512) return 0;
-  const uint32_t tmax = 512 / cpp;
-  uint32_t best = 1;
-  double best_score = 1e9;
-  for (uint32_t t = 1; t <= tmax; ++t) {
-    const uint32_t lanes = t * cpp, bs = (lanes + 63) / 64 * 64;
-    double score = double(bs - lanes) / bs;
-    if ((uint64_t(t) * k * P) % 128 != 0) score += 0.05;
-    if (bs < 256) score += 0.02;
-    if (score < best_score - 1e-9) {
-      best_score = score;
-      best = t;
-    }
-  }
-  return best;
-}
-
-// Groups per workgroup of the tiled encodes (encode_bits: per half): pick_tile (the test
-// library's TestKnob::kEncodeTile overrides it when the tile fits 512 lanes).
-uint32_t encode_tile(const EncodeLaunch& a) {
-  const uint32_t cpp = (a.P + 15u) / 16u;
-  const int tile_env = knob(TestKnob::kEncodeTile, 0);
-  return tile_env > 0 && cpp > 0 && uint32_t(tile_env) * cpp <= 512 ? uint32_t(tile_env) : pick_tile(cpp, a.k, a.P);
-}
-
 // POL: parity is written once and not re-read by this kernel (non-temporal stores).
 template <int K, int R, int OFF, bool FIRST, int POL = kNtStore>
 hipError_t run_encode_v16(const EncodeLaunch& a, uint32_t row0, hipStream_t s) {
   const uint32_t cpp = (a.P + 15u) / 16u;
   const uint32_t tile = encode_tile(a);
-  const uint64_t gchunk = groups_per_launch(cpp);
-  for (uint64_t g0 = 0; g0 < a.groups; g0 += gchunk) {
-    const uint64_t gn = (a.groups - g0 < gchunk) ? a.groups - g0 : gchunk;
+  return for_chunks(a.groups, groups_per_launch(cpp), [&](uint64_t g0, uint64_t gn) {
     const uint32_t n = static_cast<uint32_t>(gn * cpp);
     {
       const uint32_t bs = tile > 0 ? (tile * cpp + 63) / 64 * 64 : 256u;
@@ -2372,10 +2307,7 @@ hipError_t run_encode_v16(const EncodeLaunch& a, uint32_t row0, hipStream_t s) {
                          a.offsets, a.parity, g0, n, cpp, a.P, a.k, a.r, row0,
                          static_cast<const Tab*>(a.tables), 0u, gn, 0u);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 template <int K, int R, int W, int POL = kNtStore>
@@ -2384,9 +2316,7 @@ hipError_t run_encode_bits(const EncodeLaunch& a, hipStream_t s) {
   const uint32_t tile = encode_tile(a);
   if (tile == 0) return hipErrorInvalidValue;  // callers route P > 8,192 elsewhere
   const uint32_t bs = (tile * cpp + 63) / 64 * 64;
-  const uint64_t gchunk = max_wave_blocks() * 2 * tile;
-  for (uint64_t g0 = 0; g0 < a.groups; g0 += gchunk) {
-    const uint64_t gn = (a.groups - g0 < gchunk) ? a.groups - g0 : gchunk;
+  return for_chunks(a.groups, max_wave_blocks() * 2 * tile, [&](uint64_t g0, uint64_t gn) {
     const uint32_t blocks = static_cast<uint32_t>((gn + 2 * tile - 1) / (2 * tile));
     // Unstaged: uncapped (k=20 r=5 at 12 / 18 / 24 waves per CU within 0.2%, 3 waves per SIMD by
     // VGPRs).  Staged rows (kStageRows): 2 workgroups per CU, 5.163 vs 5.246 ms uncapped on two
@@ -2395,54 +2325,26 @@ hipError_t run_encode_bits(const EncodeLaunch& a, hipStream_t s) {
     const int waves = a.waves_per_cu ? a.waves_per_cu : knob(TestKnob::kEncodeWaves, kDefWaves);
     uint32_t smem = occupancy_cap_lds(waves, bs / 64);
     if constexpr ((POL & kStageRows) != 0) smem = std::max<uint32_t>(smem, 2 * tile * R * a.P);
-    {
-      LaunchRecord t = launch_record(LaunchForm::kEncodeBits, blocks, bs, g0, gn);
-      t.k = K, t.r = R, t.off = 0, t.pol = POL, t.tile = tile, t.aux = W;
-      trace_launch(t);
-    }
+    LaunchRecord t = launch_record(LaunchForm::kEncodeBits, blocks, bs, g0, gn);
+    t.k = K, t.r = R, t.off = 0, t.pol = POL, t.tile = tile, t.aux = W;
+    trace_launch(t);
     hipLaunchKernelGGL((encode_bits<K, R, W, POL>), dim3(blocks), dim3(bs), smem, s, a.data, a.parity, g0, cpp, a.P,
                        tile, gn, 0u);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
-// Bit-sliced encode for a compile-time shape where it is faster than the tables (r >= 4: the
-// table form is VALU-bound there); the test library's TestKnob::kEncodeBits forces it on (1,
-// every compiled shape) or off (0).
-bool use_encode_bits(uint32_t r) {
-  const int mode = knob(TestKnob::kEncodeBits, -1);
-  return mode == 1 || (mode < 0 && r >= 4);
-}
-
-// kStageRows for a launch whose workgroup window (groups_per_block * r * P bytes) fits the LDS a
-// workgroup may take (the test library's TestKnob::kEncodeStage: 1 on, 0 off).  A flat launch
-// (P > 8192, groups_per_block 0) passes too: it runs the kStageRows instantiation, whose kernel
-// stages only when tiled and otherwise stores directly.
-bool use_stage_rows(const EncodeLaunch& a, uint32_t groups_per_block) {
-  const int mode = knob(TestKnob::kEncodeStage, kEncodeStageDefault);
-  return mode == 1 && a.P % 16 == 0 && uint64_t(groups_per_block) * a.r * a.P <= 64u * 1024u;
-}
-
+// Runtime k, or packets shorter than 16 B.
 template <int OFF>
 hipError_t run_encode_generic(const EncodeLaunch& a, hipStream_t s) {
   if (a.P < kVecMinP) {
-    const uint64_t gchunk = groups_per_launch(a.P);
-    for (uint64_t g0 = 0; g0 < a.groups; g0 += gchunk) {
-      const uint64_t gn = (a.groups - g0 < gchunk) ? a.groups - g0 : gchunk;
+    return for_chunks(a.groups, groups_per_launch(a.P), [&](uint64_t g0, uint64_t gn) {
       const uint32_t n = static_cast<uint32_t>(gn * a.P);
-      {
-        LaunchRecord t = launch_record(LaunchForm::kEncodeBytes, blocks_for(n), 256, g0, gn);
-        t.k = 0, t.off = OFF;
-        trace_launch(t);
-      }
+      LaunchRecord t = launch_record(LaunchForm::kEncodeBytes, blocks_for(n), 256, g0, gn);
+      t.k = 0, t.off = OFF;
+      trace_launch(t);
       hipLaunchKernelGGL(encode_bytes<OFF>, dim3(blocks_for(n)), dim3(256), 0, s, a.data, a.offsets,
                          a.parity, g0, n, a.P, a.k, a.r, static_cast<const Tab*>(a.tables));
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    });
   }
   // Runtime k: passes of up to 8 parity rows; the first pass owns the XOR row.
   for (uint32_t row0 = 0; row0 < a.r; row0 += 8) {
@@ -2471,89 +2373,75 @@ hipError_t run_encode_generic(const EncodeLaunch& a, hipStream_t s) {
   return hipSuccess;
 }
 
-// A compile-time encode in its staged form (kStageRows) where the workgroup's window fits
-// (use_stage_rows), else with POL's direct stores.
-template <int K, int R, int OFF, int POL = kNtStore>
-hipError_t run_encode_v16_staged(const EncodeLaunch& a, hipStream_t s) {
-  if (use_stage_rows(a, encode_tile(a))) return run_encode_v16<K, R, OFF, true, POL | kStageRows>(a, 0, s);
-  return run_encode_v16<K, R, OFF, true, POL>(a, 0, s);
-}
-
 }  // namespace
 
 hipError_t launch_encode(const EncodeLaunch& a, hipStream_t s) {
   if (a.groups == 0) return hipSuccess;
-  if (a.P >= kVecMinP) {
-    if (a.off_kind == OffsetKind::kNone) {
-      // The paired-coefficient arithmetic (kPairMac): +0.9% at k=20 r=5 (5.53 vs 5.58 ms),
-      // +1.0% at k=10 r=3 (2.65 vs 2.68 ms), same box, alternating runs
-      // (profiles/r02_ab_encode_pair.txt).  Staged rows keep the default cache policy, NT stores
-      // with cached loads (C2 2.590 ms vs 2.606-2.702, C4 4.991 vs 5.062-5.345 for the other
-      // three; profiles/r05k/sweep_mempol.jsonl).
-      // Bit-sliced form (bitslice.hpp) while a workgroup holds whole groups.  k=20 r=5 (VALU-
-      // bound with the tables): 5.24-5.41 vs 5.37-5.54 ms over six boxes; k=10 r=3 (HBM-bound
-      // with the tables) 2.74-2.76 vs 2.63-2.66 ms, so not chosen there.  4 packets in flight per
-      // lane (2: 5.70 ms, 8: 5.28, 20: 5.91-6.03; profiles/r03_ab_bits.txt).
-      if (a.P <= 8192 && use_encode_bits(a.r)) {
-        const bool stg = use_stage_rows(a, 2 * encode_tile(a));
-        if (a.k == 20 && a.r == 5)
-          return stg ? run_encode_bits<20, 5, 4, kNtStore | kStageRows>(a, s) : run_encode_bits<20, 5, 4>(a, s);
-        if (a.k == 10 && a.r == 3) return stg ? run_encode_bits<10, 3, 4, kNtStore | kStageRows>(a, s) : run_encode_bits<10, 3, 4>(a, s);
-      }
-      if (a.k == 10 && a.r == 3) return run_encode_v16_staged<10, 3, 0, kNtStore | kPairMac>(a, s);
-      // staged rows measured per shape (scripts/ab_stage_rows.py, profiles/r05k): k=10 r=1 level
-      // (2.383 vs 2.378 ms), k=10 r=2 -1.5% (2.537 vs 2.575), k=4 r=2 +8.9% (1.351 vs 1.241): the
-      // XOR row and k=4 keep their direct stores
-      if (a.k == 10 && a.r == 1) return run_encode_v16<10, 1, 0, true>(a, 0, s);
-      if (a.k == 20 && a.r == 5) return run_encode_v16<20, 5, 0, true, kNtStore | kPairMac>(a, 0, s);
-      if (a.k == 4 && a.r == 2) return run_encode_v16<4, 2, 0, true>(a, 0, s);
-      // k=10 r=2 (the campaign's 20% FEC rate): compile-time k (2.50 vs 2.56 ms for the runtime-k
-      // loop, profiles/r02_ab_encode_r1r2_defaults.txt)
-      if (a.k == 10 && a.r == 2) return run_encode_v16_staged<10, 2, 0, kNtStore | kPairMac>(a, s);
-    } else if (a.off_kind == OffsetKind::kU32) {
-      if (a.k == 10 && a.r == 1) return run_encode_v16<10, 1, 1, true>(a, 0, s);
-    } else if (a.off_kind == OffsetKind::kAddr) {
-      if (a.k == 10 && a.r == 1) return run_encode_v16<10, 1, 3, true>(a, 0, s);
-    }
-  }
-  switch (a.off_kind) {
-    case OffsetKind::kNone:
-      return run_encode_generic<0>(a, s);
-    case OffsetKind::kU32:
-      return run_encode_generic<1>(a, s);
-    case OffsetKind::kU64:
-      return run_encode_generic<2>(a, s);
-    default:
-      return run_encode_generic<3>(a, s);
-  }
+  const EncodeForm f = encode_form(a);
+  if (f.K == 0)  // runtime k or the byte kernel, per kind of offsets
+    return f.OFF == 0 ? run_encode_generic<0>(a, s) : f.OFF == 1 ? run_encode_generic<1>(a, s)
+         : f.OFF == 2 ? run_encode_generic<2>(a, s) : run_encode_generic<3>(a, s);
+#define QFEC_V16(KK, RR, OO, PP)                                                              \
+  if (f.kernel == EncodeKernel::kV16 && f.K == KK && f.R == RR && f.OFF == OO && f.POL == (PP)) \
+    return run_encode_v16<KK, RR, OO, true, PP>(a, 0, s);
+#define QFEC_BITS(KK, RR, OO, PP)                                                              \
+  if (f.kernel == EncodeKernel::kBits && f.K == KK && f.R == RR && f.OFF == OO && f.POL == (PP)) \
+    return run_encode_bits<KK, RR, 4, PP>(a, s);
+  QFEC_ENCODE_V16_FORMS(QFEC_V16)
+  QFEC_ENCODE_BITS_FORMS(QFEC_BITS)
+#undef QFEC_BITS
+#undef QFEC_V16
+  return hipErrorNotSupported;
 }
 
 namespace {
 
+// Levels 1..3 of the codebook, all the mask-addressed kernels rank.
+RankMeta rank_meta(const LevelMeta& m) {
+  RankMeta rm{};
+  for (int e = 1; e <= 3; ++e) rm.base[e] = m.base[e], rm.stride[e] = m.stride[e], rm.count_r[e] = m.count_r[e];
+  return rm;
+}
+
+hipError_t run_classify(const DecodeLaunch& a, hipStream_t s) {
+  return for_chunks(a.groups, max_launch_threads(), [&](uint64_t g0, uint64_t gn) {
+    trace_launch(launch_record(LaunchForm::kClassify, blocks_for(gn), 256, g0, gn));
+    hipLaunchKernelGGL(classify, dim3(blocks_for(gn)), dim3(256), 0, s, a.masks + g0, gn, a.k, a.r,
+                       a.binom, a.meta, a.rec_off ? a.rec_off + g0 : nullptr, a.status ? a.status + g0 : nullptr);
+  });
+}
+
+hipError_t run_decode_bytes(const DecodeLaunch& a, hipStream_t s) {
+  return for_chunks(a.groups, groups_per_launch(a.P), [&](uint64_t g0, uint64_t gn) {
+    const uint32_t n = static_cast<uint32_t>(gn * a.P);
+    LaunchRecord t = launch_record(LaunchForm::kDecodeBytes, blocks_for(n), 256, g0, gn);
+    t.k = 0, t.pol = a.compact_out ? kCompactOut : 0;
+    trace_launch(t);
+    hipLaunchKernelGGL(decode_bytes, dim3(blocks_for(n)), dim3(256), 0, s, a.data, a.parity,
+                       a.rec_off, a.codebook, g0, n, a.P, a.k, a.r, a.out ? a.out : a.data,
+                       a.compact_out ? 1u : 0u);
+  });
+}
+
+// The wave-per-group decodes (4 groups per workgroup, decode_fused's scan form more) chunk
+// their groups by whole workgroups: at most max_wave_blocks() of them per launch.
 template <int K, int MAXE>
 hipError_t run_decode_v16(const DecodeLaunch& a, hipStream_t s) {
   const uint32_t cpp = (a.P + 15u) / 16u;
   const uint32_t passes = (a.r + MAXE - 1) / MAXE;  // e <= r
   for (uint32_t p = 0; p < passes; ++p) {
     const uint32_t m0 = p * MAXE;
-    const uint64_t blocks = (a.groups + 3) / 4;
-    const uint64_t max_blocks = max_wave_blocks();
-    for (uint64_t b0 = 0; b0 < blocks; b0 += max_blocks) {
-      const uint64_t bn = (blocks - b0 < max_blocks) ? blocks - b0 : max_blocks;
-      const uint64_t g0 = b0 * 4;
-      const uint64_t gn = (a.groups - g0 < bn * 4) ? a.groups - g0 : bn * 4;
-      {
-        LaunchRecord t = launch_record(LaunchForm::kDecodeV16, bn, 256, g0, gn);
-        t.k = K, t.r = MAXE, t.aux = m0;
-        trace_launch(t);
-      }
+    const hipError_t e = for_chunks(a.groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
+      const uint64_t bn = (gn + 3) / 4;
+      LaunchRecord t = launch_record(LaunchForm::kDecodeV16, bn, 256, g0, gn);
+      t.k = K, t.r = MAXE, t.aux = m0;
+      trace_launch(t);
       hipLaunchKernelGGL((decode_v16<K, MAXE>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
                          a.data + g0 * a.k * static_cast<uint64_t>(a.P),
                          a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook,
                          gn, cpp, a.P, a.k, a.r, m0);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
+    });
+    if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
@@ -2568,25 +2456,18 @@ hipError_t run_decode_wave(const DecodeLaunch& a, hipStream_t s) {
     const uint32_t rows = a.r - m0 < MAXE ? a.r - m0 : MAXE;
     const uint32_t slice = (POL & kLdsTabs) != 0 ? (rows * a.k * 2u + 63u) / 64u * 1024u : 0u;
     const uint32_t smem = cap > 4 * slice ? cap : 4 * slice;
-    const uint64_t blocks = (a.groups + 3) / 4;
-    const uint64_t max_blocks = max_wave_blocks();
-    for (uint64_t b0 = 0; b0 < blocks; b0 += max_blocks) {
-      const uint64_t bn = (blocks - b0 < max_blocks) ? blocks - b0 : max_blocks;
-      const uint64_t g0 = b0 * 4;
-      const uint64_t gn = (a.groups - g0 < bn * 4) ? a.groups - g0 : bn * 4;
-      {
-        LaunchRecord t = launch_record(LaunchForm::kDecodeWave, bn, 256, g0, gn);
-        t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
-        trace_launch(t);
-      }
+    const hipError_t e = for_chunks(a.groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
+      const uint64_t bn = (gn + 3) / 4;
+      LaunchRecord t = launch_record(LaunchForm::kDecodeWave, bn, 256, g0, gn);
+      t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
+      trace_launch(t);
       hipLaunchKernelGGL((decode_wave<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), smem, s,
                          a.data + g0 * a.k * static_cast<uint64_t>(a.P),
                          a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook, gn, a.P,
                          a.k, a.r, m0, (a.out ? a.out : a.data) + g0 * ((POL & kCompactOut) != 0 ? a.r : a.k) * static_cast<uint64_t>(a.P), 0u,
                          decode_swizzle(a, kDecodeWaveXcdSwizzle), slice);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
+    });
+    if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
@@ -2596,12 +2477,7 @@ hipError_t run_decode_fused(const DecodeLaunch& a, hipStream_t s) {
   constexpr uint64_t kGroupsPerBlock = SCAN > 64 ? SCAN : 4u * (SCAN > 0 ? SCAN : 1);
   const uint32_t passes = (a.r + MAXE - 1) / MAXE;
   const uint32_t smem = occupancy_cap_lds(a.waves_per_cu ? a.waves_per_cu : knob(TestKnob::kDecodeWaves, kDecodeWavesPerCU), 4);
-  RankMeta rm{};
-  for (int e = 1; e <= 3; ++e) {
-    rm.base[e] = a.meta.base[e];
-    rm.stride[e] = a.meta.stride[e];
-    rm.count_r[e] = a.meta.count_r[e];
-  }
+  const RankMeta rm = rank_meta(a.meta);
   // Output of the chunk starting at group g0: packed rows are placed by their global row
   // start (rec_off), so every chunk gets the base; the other layouts are offset per chunk.
   auto out_at = [&](uint64_t g0) -> uint8_t* {
@@ -2610,157 +2486,51 @@ hipError_t run_decode_fused(const DecodeLaunch& a, hipStream_t s) {
   };
   for (uint32_t p = 0; p < passes; ++p) {
     const uint32_t m0 = p * MAXE;
-    const uint64_t blocks = (a.groups + kGroupsPerBlock - 1) / kGroupsPerBlock;
-    const uint64_t max_blocks = max_wave_blocks();
-    for (uint64_t b0 = 0; b0 < blocks; b0 += max_blocks) {
-      const uint64_t bn = (blocks - b0 < max_blocks) ? blocks - b0 : max_blocks;
-      const uint64_t g0 = b0 * kGroupsPerBlock;
-      const uint64_t gn = (a.groups - g0 < bn * kGroupsPerBlock) ? a.groups - g0 : bn * kGroupsPerBlock;
-      {
-        LaunchRecord t = launch_record(LaunchForm::kDecodeFused, bn, 256, g0, gn);
-        t.k = K, t.r = MAXE, t.nm = NM, t.nt = NT, t.pol = POL, t.direct = DIRECT, t.scan = SCAN, t.aux = m0;
-        trace_launch(t);
-      }
+    const hipError_t e = for_chunks(a.groups, max_wave_blocks() * kGroupsPerBlock, [&](uint64_t g0, uint64_t gn) {
+      const uint64_t bn = (gn + kGroupsPerBlock - 1) / kGroupsPerBlock;
+      LaunchRecord t = launch_record(LaunchForm::kDecodeFused, bn, 256, g0, gn);
+      t.k = K, t.r = MAXE, t.nm = NM, t.nt = NT, t.pol = POL, t.direct = DIRECT, t.scan = SCAN, t.aux = m0;
+      trace_launch(t);
       hipLaunchKernelGGL((decode_fused<K, MAXE, POL, NM, NT, DIRECT, INLINE, SCAN>), dim3(static_cast<uint32_t>(bn)), dim3(256), smem, s,
                          a.data + g0 * a.k * static_cast<uint64_t>(a.P),
                          a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook, gn, a.P,
                          a.r, m0, out_at(g0), 0u, decode_swizzle(a, kDecodeFusedXcdSwizzle), DIRECT ? a.masks + g0 : nullptr, rm,
                          INLINE && a.status ? a.status + g0 : nullptr);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-  }
-  return hipSuccess;
-}
-
-// The fused form for this (k, r, P), if instantiated; hipErrorNotSupported otherwise.
-// Instantiated for every P in [16, 2047] of the compiled (k, r) shapes: NM = P / 1024 16-B and
-// NT = ceil((P % 1024) / 256) 4-B pieces per lane, (NM, NT) in (0,1..4), (1,0..4); P = 2048 would
-// be (2,0), which is not instantiated, so 2048 and up take the wave kernel.  P <= 256 is the one
-// 4-B piece (0,1): the shapes with a tiled form decode such packets there in both layouts, so of
-// the mask-addressed (0,1) forms only k=10 r=2's compact one is ever launched (recover layouts);
-// k=10 r=2 in place at P <= 256 goes to the runtime-k wave kernel (a known slow
-// path).  r <= 3 shapes only in the mask-addressed form (the one auto uses for
-// them), r > 3 only in the record-addressed one; k=10 r=3 1200 B in both (probes).
-// Measured at k=10 r=3, 2 erasures (tools/probe_decode.hip): 512 B 5.89 TB/s vs 3.12 for
-// the looped wave kernel, 768 B 5.49 vs 3.24 (profiles/r01_probe_decode_small.txt).  The
-// mask-addressed forms also load non-temporally (survivors are read once): +1.2..3.2% at
-// 512 / 768 / 1200 / 1400 B in one process (profiles/r01_probe_decode_ntload.txt); loads
-// alone without NT stores lose 14%.  The r > 3 record-addressed forms stage their tables
-// through LDS (kLdsTabs): k=20 r=5, 5 erasures, 1200 B: 2.27 -> 4.73-4.92 TB/s
-// (profiles/r01_probe_decode_ldstabs_k20.txt); at k=10 r=3, whose 286 records stay in the
-// scalar cache, it gains nothing (profiles/r01_probe_decode_inline_k10.txt).
-// dry: only report whether a form exists (hipSuccess) without launching it.
-hipError_t try_decode_fused(const DecodeLaunch& a, hipStream_t s, bool direct, bool dry = false) {
-  const uint32_t nm = a.P / 1024u, nt = (a.P % 1024u + 255u) / 256u;
-#define QFEC_FUSED_D(KK, RR, NMM, NTT)                                                        \
-  if (direct && a.k == KK && a.r == RR && nm == NMM && nt == NTT)                             \
-    return dry ? hipSuccess                                                                   \
-           : a.compact_out ? run_decode_fused<KK, RR, kNtStore | kNtLoad | kCompactOut, NMM, NTT, true>(a, s) \
-                           : run_decode_fused<KK, RR, kNtStore | kNtLoad, NMM, NTT, true>(a, s);
-  // k=10 r=3 (the BASELINE shape) also has the scan form, for sparse loss (DecodeLaunch::scan),
-  // and the compact-output form (DecodeLaunch::compact_out)
-#define QFEC_FUSED_DS(KK, RR, NMM, NTT)                                                       \
-  if (direct && a.k == KK && a.r == RR && nm == NMM && nt == NTT) {                           \
-    if (dry) return hipSuccess;                                                               \
-    if (a.compact_out)                                                                        \
-      return a.scan == kDecodeScanGroups                                                      \
-                 ? run_decode_fused<KK, RR, kNtStore | kNtLoad | kCompactOut, NMM, NTT, true, true, kDecodeScanGroups>(a, s) \
-                 : run_decode_fused<KK, RR, kNtStore | kNtLoad | kCompactOut, NMM, NTT, true>(a, s); \
-    if (a.scan == kDecodeScanGroups)                                                          \
-      return run_decode_fused<KK, RR, kNtStore | kNtLoad, NMM, NTT, true, true, kDecodeScanGroups>(a, s); \
-    return run_decode_fused<KK, RR, kNtStore | kNtLoad, NMM, NTT, true>(a, s);                \
-  }
-#define QFEC_FUSED_R(KK, RR, NMM, NTT)                                                        \
-  if (!direct && !a.compact_out && a.k == KK && a.r == RR && nm == NMM && nt == NTT)          \
-    return dry ? hipSuccess : run_decode_fused<KK, RR, kNtStore, NMM, NTT, false>(a, s);
-#define QFEC_FUSED_L(KK, RR, NMM, NTT)                                                        \
-  if (!direct && a.k == KK && a.r == RR && nm == NMM && nt == NTT)                            \
-    return dry ? hipSuccess                                                                   \
-           : a.compact_out ? run_decode_fused<KK, RR, kNtStore | kNtLoad | kLdsTabs | kCoefBytes | kCompactOut, NMM, NTT, false>(a, s) \
-                           : run_decode_fused<KK, RR, kNtStore | kNtLoad | kLdsTabs | kCoefBytes, NMM, NTT, false>(a, s);
-#define QFEC_FUSED_P(M, KK, RR)                                                               \
-  M(KK, RR, 0, 1) M(KK, RR, 0, 2) M(KK, RR, 0, 3) M(KK, RR, 0, 4) M(KK, RR, 1, 0) M(KK, RR, 1, 1) \
-  M(KK, RR, 1, 2) M(KK, RR, 1, 3) M(KK, RR, 1, 4)
-  QFEC_FUSED_P(QFEC_FUSED_DS, 10, 3)
-  QFEC_FUSED_R(10, 3, 1, 1)
-  QFEC_FUSED_P(QFEC_FUSED_L, 20, 5)
-  QFEC_FUSED_P(QFEC_FUSED_D, 10, 1)
-  QFEC_FUSED_P(QFEC_FUSED_D, 10, 2)
-  QFEC_FUSED_P(QFEC_FUSED_D, 4, 2)
-#undef QFEC_FUSED_P
-#undef QFEC_FUSED_DS
-#undef QFEC_FUSED_L
-#undef QFEC_FUSED_R
-#undef QFEC_FUSED_D
-  return hipErrorNotSupported;
-}
-
-// Packets of at most this size decode in the tiled form (several groups per wave).
-constexpr uint32_t kTiledMaxP = 256;
-
-template <int K, int MAXE, int POL>
-hipError_t run_decode_tiled(const DecodeLaunch& a, uint32_t tile, hipStream_t s) {
-  const uint32_t cpp = (a.P + 15u) / 16u;
-  const uint32_t bs = (tile * cpp + 63) / 64 * 64;
-  const uint64_t blocks = (a.groups + tile - 1) / tile;
-  const uint64_t max_blocks = groups_per_launch(bs);  // blocks * bs stays a 32-bit grid
-  for (uint64_t b0 = 0; b0 < blocks; b0 += max_blocks) {
-    const uint64_t bn = (blocks - b0 < max_blocks) ? blocks - b0 : max_blocks;
-    const uint64_t g0 = b0 * tile;
-    const uint64_t gn = (a.groups - g0 < bn * tile) ? a.groups - g0 : bn * tile;
-    {
-      LaunchRecord t = launch_record(LaunchForm::kDecodeTiled, bn, bs, g0, gn);
-      t.k = K, t.r = MAXE, t.pol = POL, t.tile = tile;
-      trace_launch(t);
-    }
-    hipLaunchKernelGGL((decode_tiled<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(bs), 0, s,
-                       a.data + g0 * a.k * static_cast<uint64_t>(a.P),
-                       a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook, gn, cpp,
-                       a.P, a.r, tile,
-                       (a.out ? a.out : a.data) + g0 * ((POL & kCompactOut) != 0 ? a.r : a.k) * static_cast<uint64_t>(a.P));
-    const hipError_t e = hipGetLastError();
+    });
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-// (k, r) shapes with a compiled tiled form (launch_decode's QFEC_TILED list)
-bool has_tiled(uint32_t k, uint32_t r) {
-  return (k == 10 && (r == 3 || r == 1)) || (k == 20 && r == 5) || (k == 4 && r == 2);
+template <int K, int MAXE, int POL>
+hipError_t run_decode_tiled(const DecodeLaunch& a, uint32_t tile, hipStream_t s) {
+  const uint32_t cpp = (a.P + 15u) / 16u;
+  const uint32_t bs = (tile * cpp + 63) / 64 * 64;
+  // whole workgroups per launch: blocks * bs stays a 32-bit grid
+  return for_chunks(a.groups, groups_per_launch(bs) * tile, [&](uint64_t g0, uint64_t gn) {
+    const uint64_t bn = (gn + tile - 1) / tile;
+    LaunchRecord t = launch_record(LaunchForm::kDecodeTiled, bn, bs, g0, gn);
+    t.k = K, t.r = MAXE, t.pol = POL, t.tile = tile;
+    trace_launch(t);
+    hipLaunchKernelGGL((decode_tiled<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(bs), 0, s,
+                       a.data + g0 * a.k * static_cast<uint64_t>(a.P),
+                       a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook, gn, cpp,
+                       a.P, a.r, tile,
+                       (a.out ? a.out : a.data) + g0 * ((POL & kCompactOut) != 0 ? a.r : a.k) * static_cast<uint64_t>(a.P));
+  });
 }
 
-bool decode_tiled_form(const DecodeLaunch& a) {
-  // the compact recover layout only where a tiled form is compiled; elsewhere the fused or
-  // wave forms write it
-  if (a.compact_out && !has_tiled(a.k, a.r)) return false;
-  const uint32_t tile = a.P >= kVecMinP ? pick_tile((a.P + 15u) / 16u, a.k, a.P) : 0u;
-  // auto leaves k=20 r=5 to the LDS-table fused form (P=200: 4.6 vs 2.8 TB/s, same box)
-  const bool auto_tiled = a.variant == kDecodeAuto && a.P <= kTiledMaxP && !(a.k == 20 && a.r == 5);
-  return tile > 0 && (auto_tiled || a.variant == kDecodeTiledPlain || a.variant == kDecodeTiledNt);
-}
-
-// Mask-addressed fused form (r <= 3): +1.2% at k=10 r=3 (tools/probe_decode.hip,
-// r01_probe_decode_direct.txt); at k=20 r=5 its extra VGPRs cost a wave per SIMD (-30%), so
-// auto takes it for r <= 3 only.  It classifies inline: one launch, no classify kernel.
-bool decode_direct_form(const DecodeLaunch& a) {
-  return a.P >= kVecMinP && !decode_tiled_form(a) && a.masks != nullptr && !a.rec_ready &&
-         (a.variant == kDecodeFusedDirect || (a.variant == kDecodeAuto && a.r <= 3)) &&
-         try_decode_fused(a, nullptr, true, /*dry=*/true) == hipSuccess;
+// One entry of the form lists (fec_forms.hpp QFEC_DECODE_FORMS) to its instantiation.
+template <DecodeKernel KERNEL, int K, int MAXE, int NM, int NT, int POL, bool DIRECT, int SCAN>
+hipError_t run_decode_form(const DecodeLaunch& a, uint32_t tile, hipStream_t s) {
+  if constexpr (KERNEL == DecodeKernel::kFused) return run_decode_fused<K, MAXE, POL, NM, NT, DIRECT, DIRECT, SCAN>(a, s);
+  else if constexpr (KERNEL == DecodeKernel::kTiled) return run_decode_tiled<K, MAXE, POL>(a, tile, s);
+  else if constexpr (KERNEL == DecodeKernel::kWave) return run_decode_wave<K, MAXE, POL>(a, s);
+  else if constexpr (KERNEL == DecodeKernel::kV16) return run_decode_v16<K, MAXE>(a, s);
+  else return run_decode_bytes(a, s);
 }
 
 }  // namespace
-
-bool decode_needs_rec_off(const DecodeLaunch& a) { return a.groups > 0 && !decode_direct_form(a); }
-
-// The record-addressed LDS-table forms (QFEC_FUSED_L: k=20 r=5, 16 <= P < 2048) read compact
-// codebooks; every other form reads CoefEntry records.
-bool decode_compact_tables(const DecodeLaunch& a) {
-  if (a.groups == 0 || a.P < kVecMinP || a.rec_ready || decode_tiled_form(a) || decode_direct_form(a)) return false;
-  if (a.variant != kDecodeFused && a.variant != kDecodeAuto && a.variant != kDecodeFusedDirect) return false;
-  const uint32_t nm = a.P / 1024u, nt = (a.P % 1024u + 255u) / 256u;
-  return a.k == 20 && a.r == 5 && ((nm == 0 && nt >= 1) || nm == 1);  // QFEC_FUSED_P's (nm, nt)
-}
 
 uint64_t rows_prefix_workspace_bytes(uint64_t groups) {
   return ((groups + kRowsPerBlock - 1) / kRowsPerBlock) * sizeof(uint32_t);
@@ -2815,55 +2585,24 @@ uint64_t runs_blocks_per_launch(uint64_t groups) {
 // profiles/r05j/ab_legs.jsonl).
 template <int K, int R, int NM, int NT, int POL = kNtLoad | kNtStore>
 hipError_t run_recover_runs(const RunsLaunch& a, uint32_t stage, hipStream_t s) {
-  RankMeta rm{};
-  for (int e = 1; e <= 3; ++e) {
-    rm.base[e] = a.meta.base[e];
-    rm.stride[e] = a.meta.stride[e];
-    rm.count_r[e] = a.meta.count_r[e];
-  }
+  const RankMeta rm = rank_meta(a.meta);
   uint8_t* ws = static_cast<uint8_t*>(a.workspace);
   uint32_t* ticket = reinterpret_cast<uint32_t*>(ws);
   const uint64_t per = runs_blocks_per_launch(a.groups) * kRunGroups;
   const uint32_t launches = runs_launches(a.groups);
   uint64_t* totals = reinterpret_cast<uint64_t*>(ws + 64);
   uint64_t* lb = reinterpret_cast<uint64_t*>(ws + 64 + 8 * static_cast<uint64_t>(launches));
-  for (uint32_t c = 0; c < launches; ++c) {
-    const uint64_t g0 = c * per;
-    const uint64_t gn = a.groups - g0 < per ? a.groups - g0 : per;
+  return for_chunks(a.groups, per, [&](uint64_t g0, uint64_t gn) {
+    const uint32_t c = static_cast<uint32_t>(g0 / per);  // this launch of `launches`
     const uint32_t nb = static_cast<uint32_t>((gn + kRunGroups - 1) / kRunGroups);
-    {
-      LaunchRecord t = launch_record(LaunchForm::kRecoverRuns, nb, 64 * kRunWaves, g0, gn);
-      t.k = K, t.r = R, t.nm = NM, t.nt = NT, t.pol = POL, t.tile = kRunGroups, t.aux = stage;
-      trace_launch(t);
-    }
+    LaunchRecord t = launch_record(LaunchForm::kRecoverRuns, nb, 64 * kRunWaves, g0, gn);
+    t.k = K, t.r = R, t.nm = NM, t.nt = NT, t.pol = POL, t.tile = kRunGroups, t.aux = stage;
+    trace_launch(t);
     hipLaunchKernelGGL((recover_runs<K, R, NM, NT, POL, kRunWaves>), dim3(nb), dim3(64 * kRunWaves), stage, s, a.data + g0 * K * static_cast<uint64_t>(a.P),
                        a.parity + g0 * R * static_cast<uint64_t>(a.P), a.masks + g0, gn, a.P, a.codebook, rm, a.out,
                        a.row_start + g0, a.status ? a.status + g0 : nullptr, lb, ticket, a.epoch + c, stage,
                        c > 0 ? totals + (c - 1) : nullptr, totals + c, c + 1 == launches ? a.total : nullptr, 0u);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// (k, r, P) shapes with a compiled recover_runs: the mask-addressed decode's (try_decode_fused
-// QFEC_FUSED_DS / _D lists), 256 < P <= 2047 or 16 <= P <= 256 with one 4-B piece (the packed call
-// reaches the latter only for k=10 r=2: the other shapes' short packets are refused, their slot
-// layout being the tiled form's).
-hipError_t try_recover_runs(const RunsLaunch& a, uint32_t stage, hipStream_t s, bool dry) {
-  const uint32_t nm = a.P / 1024u, nt = (a.P % 1024u + 255u) / 256u;
-#define QFEC_RUNS(KK, RR, NMM, NTT) \
-  if (a.k == KK && a.r == RR && nm == NMM && nt == NTT) return dry ? hipSuccess : run_recover_runs<KK, RR, NMM, NTT>(a, stage, s);
-#define QFEC_RUNS_P(KK, RR)                                                                                    \
-  QFEC_RUNS(KK, RR, 0, 1) QFEC_RUNS(KK, RR, 0, 2) QFEC_RUNS(KK, RR, 0, 3) QFEC_RUNS(KK, RR, 0, 4)            \
-  QFEC_RUNS(KK, RR, 1, 0) QFEC_RUNS(KK, RR, 1, 1) QFEC_RUNS(KK, RR, 1, 2) QFEC_RUNS(KK, RR, 1, 3) QFEC_RUNS(KK, RR, 1, 4)
-  QFEC_RUNS_P(10, 3)
-  QFEC_RUNS_P(10, 1)
-  QFEC_RUNS_P(10, 2)
-  QFEC_RUNS_P(4, 2)
-#undef QFEC_RUNS_P
-#undef QFEC_RUNS
-  return hipErrorNotSupported;
+  });
 }
 
 }  // namespace
@@ -2878,14 +2617,6 @@ uint64_t runs_workspace_bytes(uint64_t groups) {
   return 64 + 8 * static_cast<uint64_t>(runs_launches(groups)) + 8 * runs_blocks_per_launch(groups);
 }
 
-bool runs_supported(uint32_t k, uint32_t r, uint32_t P) {
-  RunsLaunch a{};
-  a.k = k;
-  a.r = r;
-  a.P = P;
-  return P >= kVecMinP && try_recover_runs(a, 0, nullptr, true) == hipSuccess;
-}
-
 uint32_t runs_stage_bytes(const RunsLaunch& a) {
   // the run image needs 16-B aligned row starts in LDS and in HBM
   if (a.P % 16u != 0 || reinterpret_cast<uintptr_t>(a.out) % 16u != 0) return 0;
@@ -2898,160 +2629,61 @@ uint32_t runs_stage_bytes(const RunsLaunch& a) {
 hipError_t launch_recover_runs(const RunsLaunch& a, hipStream_t s) {
   if (a.groups == 0) return hipSuccess;
   if (a.workspace == nullptr || a.row_start == nullptr || a.out == nullptr || a.masks == nullptr) return hipErrorInvalidValue;
-  return try_recover_runs(a, runs_stage_bytes(a), s, false);
+  if (!runs_supported(a.k, a.r, a.P)) return hipErrorNotSupported;
+  const Layout lay = layout_of(a.P);
+#define QFEC_RUNS(KK, RR, NMM, NTT) \
+  if (a.k == KK && a.r == RR && lay.nm == NMM && lay.nt == NTT) return run_recover_runs<KK, RR, NMM, NTT>(a, runs_stage_bytes(a), s);
+  QFEC_RUNS_FORMS(QFEC_RUNS)
+#undef QFEC_RUNS
+  return hipErrorNotSupported;
 }
 
 hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s) {
-  if (a.groups == 0) return hipSuccess;
+  const DecodeForm f = decode_form(a);
+  if (f.kernel == DecodeKernel::kNone) return hipSuccess;
   // the codebook's format must be the one the chosen form reads
-  if (a.compact_tables != decode_compact_tables(a)) return hipErrorInvalidValue;
-  const uint32_t tile = a.P >= kVecMinP ? pick_tile((a.P + 15u) / 16u, a.k, a.P) : 0u;
-  const bool tiled = decode_tiled_form(a);
-  if (decode_direct_form(a)) return try_decode_fused(a, s, true);
-  if (a.rec_off == nullptr) return hipErrorInvalidValue;  // every other form reads rec_off
-  const uint64_t max_threads = max_launch_threads();
-  for (uint64_t g0 = 0; !a.rec_ready && g0 < a.groups; g0 += max_threads) {
-    const uint64_t gn = (a.groups - g0 < max_threads) ? a.groups - g0 : max_threads;
-    trace_launch(launch_record(LaunchForm::kClassify, blocks_for(gn), 256, g0, gn));
-    hipLaunchKernelGGL(classify, dim3(blocks_for(gn)), dim3(256), 0, s, a.masks + g0, gn, a.k, a.r,
-                       a.binom, a.meta, a.rec_off ? a.rec_off + g0 : nullptr, a.status ? a.status + g0 : nullptr);
-    const hipError_t e = hipGetLastError();
+  if (a.compact_tables != f.compact_tables) return hipErrorInvalidValue;
+  if (f.rec_off && a.rec_off == nullptr) return hipErrorInvalidValue;
+  if (f.classify) {
+    const hipError_t e = run_classify(a, s);
     if (e != hipSuccess) return e;
   }
-  if (a.P < kVecMinP) {
-    const uint64_t gchunk = groups_per_launch(a.P);
-    for (uint64_t g0 = 0; g0 < a.groups; g0 += gchunk) {
-      const uint64_t gn = (a.groups - g0 < gchunk) ? a.groups - g0 : gchunk;
-      const uint32_t n = static_cast<uint32_t>(gn * a.P);
-      {
-        LaunchRecord t = launch_record(LaunchForm::kDecodeBytes, blocks_for(n), 256, g0, gn);
-        t.k = 0, t.pol = a.compact_out ? kCompactOut : 0;
-        trace_launch(t);
-      }
-      hipLaunchKernelGGL(decode_bytes, dim3(blocks_for(n)), dim3(256), 0, s, a.data, a.parity,
-                         a.rec_off, a.codebook, g0, n, a.P, a.k, a.r, a.out ? a.out : a.data,
-                         a.compact_out ? 1u : 0u);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
-  if (a.compact_out) {
-    // packets <= 256 B: the tiled form (several groups per wave), compact
-    if (tiled) {
-#define QFEC_TILED_C(KK, RR) \
-  if (a.k == KK && a.r == RR) return run_decode_tiled<KK, RR, kNtStore | kCompactOut>(a, tile, s);
-      QFEC_TILED_C(10, 3)
-      QFEC_TILED_C(10, 1)
-      QFEC_TILED_C(20, 5)
-      QFEC_TILED_C(4, 2)
-#undef QFEC_TILED_C
-    }
-    // fused forms were tried above; everything else: the runtime-k wave kernel, compact
-    if (a.variant == kDecodeFused || a.variant == kDecodeAuto || a.variant == kDecodeFusedDirect) {
-      const hipError_t e = try_decode_fused(a, s, false);
-      if (e != hipErrorNotSupported) return e;
-    }
-    return run_decode_wave<0, 8, kNtStore | kNoCoefBranch | kCompactOut>(a, s);
-  }
-  if (tiled) {
+  // the lists that name what is compiled are the ones decode_form's predicates come from; the
+  // probes' forms are not in the product library
+#define QFEC_FORM(KERNEL, KK, MM, NMM, NTT, PP, DD, SS)                                                             \
+  if (f.kernel == DecodeKernel::KERNEL && f.K == KK && f.MAXE == MM && f.NM == NMM && f.NT == NTT && f.POL == (PP) && \
+      f.DIRECT == DD && f.SCAN == static_cast<int>(SS))                                                             \
+    return run_decode_form<DecodeKernel::KERNEL, KK, MM, NMM, NTT, PP, DD, SS>(a, f.tile, s);
+  QFEC_DECODE_FORMS(QFEC_FORM)
 #ifdef QUICFEC_PROBE_FORMS
-    const bool nt = a.variant != kDecodeTiledPlain;
-#else
-    constexpr bool nt = true;  // the library never sets a variant (the plain forms are probe-only)
+  QFEC_PROBE_DECODE_FORMS(QFEC_FORM)
 #endif
-#define QFEC_TILED(KK, RR)                                                                   \
-  if (a.k == KK && a.r == RR)                                                                \
-    return nt ? run_decode_tiled<KK, RR, kNtStore>(a, tile, s) : QFEC_PROBE_ONLY(run_decode_tiled<KK, RR, 0>(a, tile, s));
-    QFEC_TILED(10, 3)
-    QFEC_TILED(10, 1)
-    QFEC_TILED(20, 5)
-    QFEC_TILED(4, 2)
-#undef QFEC_TILED
-  }
-  // Fused passes win where many rows share each survivor (k=20 r=5, 5 losses: +21%); with
-  // the XCD-aware order they also win at r = 3 (+2.6%; tools/probe_decode.hip), so auto
-  // takes them wherever they are instantiated.
-  // (the mask-addressed forms were tried above, before classify)
-  if (a.variant == kDecodeFused || a.variant == kDecodeAuto || a.variant == kDecodeFusedDirect) {
-    const hipError_t e = try_decode_fused(a, s, false);
-    if (e != hipErrorNotSupported) return e;
-  }
-#ifdef QUICFEC_PROBE_FORMS
-  // Probe-only forms (tools/probe_decode.hip sets DecodeLaunch::variant; the library never does):
-  // no branch on coefficients 0 / 1, the plain-store wave kernel, 16-B lanes only (decode_v16).
-  const bool separate_out = a.out != nullptr && a.out != a.data;  // decode_v16 lacks it
-  if (a.variant == kDecodeWaveNoBranch && !separate_out) {
-#define QFEC_WAVE_NB(KK, RR) \
-  if (a.k == KK && a.r == RR) return run_decode_wave<KK, RR, kNtStore | kNoCoefBranch>(a, s);
-    QFEC_WAVE_NB(10, 3)
-    QFEC_WAVE_NB(20, 5)
-#undef QFEC_WAVE_NB
-  }
-  if (a.variant == kDecodeWavePerGroup && !separate_out) {
-    if (a.k == 10 && a.r == 3) return run_decode_v16<10, 3>(a, s);
-    if (a.k == 10 && a.r == 1) return run_decode_v16<10, 1>(a, s);
-    if (a.k == 20 && a.r == 5) return run_decode_v16<20, 5>(a, s);
-    if (a.k == 4 && a.r == 2) return run_decode_v16<4, 2>(a, s);
-    return run_decode_v16<0, 8>(a, s);
-  }
-  const bool nt = a.variant != kDecodeWavePlain;
-#else
-  constexpr bool nt = true;
-#endif
-  {
-#define QFEC_WAVE(KK, RR)                                                                    \
-  if (a.k == KK && a.r == RR)                                                                \
-    return nt ? run_decode_wave<KK, RR, kNtStore>(a, s) : QFEC_PROBE_ONLY(run_decode_wave<KK, RR, 0>(a, s));
-    QFEC_WAVE(10, 3)
-    QFEC_WAVE(10, 1)
-    QFEC_WAVE(20, 5)
-    QFEC_WAVE(4, 2)
-#undef QFEC_WAVE
-    // Runtime k: multiplying by every coefficient (no branches on 0 / 1) wins at every shape
-    // measured (tools/probe_decode.hip, profiles/r01_probe_decode_runtime_k.txt): k=10 r=2
-    // 4.13 -> 4.79 TB/s, 12+6 2.62 -> 3.20, 16+4 2.67 -> 3.40.  Its tables staged through
-    // LDS (kLdsTabs) lose here (2.2-2.8 TB/s): the records of these codebooks are hit often
-    // enough in the scalar cache, and the wait for the tables precedes the survivor loads.
-    return nt ? run_decode_wave<0, 8, kNtStore | kNoCoefBranch>(a, s) : QFEC_PROBE_ONLY(run_decode_wave<0, 8, 0>(a, s));
-  }
+#undef QFEC_FORM
+  return hipErrorNotSupported;
 }
 
 hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t nbytes, uint64_t seed, uint64_t byte_offset,
                                 hipStream_t s) {
   if (nbytes == 0) return hipSuccess;
   const bool fast = (byte_offset % 8 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0);
-  uint64_t done = 0;
-  const uint64_t max_threads = max_launch_threads();
-  if (fast) {
-    const uint64_t n16 = nbytes / 16;
-    for (uint64_t c0 = 0; c0 < n16; c0 += max_threads) {
-      const uint64_t cn = (n16 - c0 < max_threads) ? n16 - c0 : max_threads;
-      {
-        LaunchRecord t = launch_record(LaunchForm::kFill, blocks_for(cn), 256, c0, cn);
-        t.aux = 16;
-        trace_launch(t);
-      }
-      hipLaunchKernelGGL(fill_words, dim3(blocks_for(cn)), dim3(256), 0, s, dst + c0 * 16,
-                         static_cast<uint32_t>(cn), seed, (byte_offset / 8) + 2 * c0);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-    done = n16 * 16;
-  }
-  for (uint64_t c0 = done; c0 < nbytes; c0 += max_threads) {
-    const uint64_t cn = (nbytes - c0 < max_threads) ? nbytes - c0 : max_threads;
-    {
-      LaunchRecord t = launch_record(LaunchForm::kFill, blocks_for(cn), 256, c0, cn);
-      t.aux = 1;
-      trace_launch(t);
-    }
+  const uint64_t n16 = fast ? nbytes / 16 : 0;
+  const hipError_t e = for_chunks(n16, max_launch_threads(), [&](uint64_t c0, uint64_t cn) {
+    LaunchRecord t = launch_record(LaunchForm::kFill, blocks_for(cn), 256, c0, cn);
+    t.aux = 16;
+    trace_launch(t);
+    hipLaunchKernelGGL(fill_words, dim3(blocks_for(cn)), dim3(256), 0, s, dst + c0 * 16,
+                       static_cast<uint32_t>(cn), seed, (byte_offset / 8) + 2 * c0);
+  });
+  if (e != hipSuccess) return e;
+  const uint64_t done = n16 * 16;
+  return for_chunks(nbytes - done, max_launch_threads(), [&](uint64_t b0, uint64_t cn) {
+    const uint64_t c0 = done + b0;
+    LaunchRecord t = launch_record(LaunchForm::kFill, blocks_for(cn), 256, c0, cn);
+    t.aux = 1;
+    trace_launch(t);
     hipLaunchKernelGGL(fill_bytes, dim3(blocks_for(cn)), dim3(256), 0, s, dst + c0,
                        static_cast<uint32_t>(cn), seed, byte_offset + c0);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 hipError_t launch_legacy_server(ServerSlot* ring, uint8_t* inl, uint64_t* done, ServerControl* ctl,
@@ -3071,22 +2703,14 @@ hipError_t launch_legacy_server(ServerSlot* ring, uint8_t* inl, uint64_t* done, 
 }
 
 hipError_t launch_copy_words(const uint8_t* src, uint8_t* dst, uint64_t nbytes, hipStream_t s) {
-  const uint64_t n16 = nbytes / 16;
-  const uint64_t max_threads = max_launch_threads();
-  for (uint64_t c0 = 0; c0 < n16; c0 += max_threads) {
-    const uint64_t cn = (n16 - c0 < max_threads) ? n16 - c0 : max_threads;
-    {
-      LaunchRecord t = launch_record(LaunchForm::kCopy, blocks_for(cn), 256, c0, cn);
-      t.aux = 16;
-      trace_launch(t);
-    }
+  return for_chunks(nbytes / 16, max_launch_threads(), [&](uint64_t c0, uint64_t cn) {
+    LaunchRecord t = launch_record(LaunchForm::kCopy, blocks_for(cn), 256, c0, cn);
+    t.aux = 16;
+    trace_launch(t);
     hipLaunchKernelGGL(copy_words, dim3(blocks_for(cn)), dim3(256), 0, s,
                        reinterpret_cast<const uint4*>(src + c0 * 16), reinterpret_cast<uint4*>(dst + c0 * 16),
                        static_cast<uint32_t>(cn));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 }  // namespace qfec

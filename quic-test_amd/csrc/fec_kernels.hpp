@@ -6,25 +6,9 @@
 
 #include <cstdint>
 
+#include "fec_forms.hpp"  // launch descriptions and the choice of kernel form
+
 namespace qfec {
-
-// Byte offsets of packets, when the data shards are not contiguous.
-// kAddr: `offsets` holds one absolute device address per packet (u64), `data` is unused --
-// the legacy-call coalescer (fec_coalesce.cpp) gathers packets from many callers' buffers.
-enum class OffsetKind : int { kNone = 0, kU32 = 1, kU64 = 2, kAddr = 3 };
-
-// Packets of any size P >= 16 at any byte address run on the 16-byte-column kernels
-// (fec_kernels.hip header); shorter ones on the byte kernels.
-struct EncodeLaunch {
-  const uint8_t* data;       // base of the data shards (device address)
-  const void* offsets;       // device u32/u64 offsets (k per group) or nullptr
-  OffsetKind off_kind;
-  uint8_t* parity;           // parity row (g, i) at (g * r + i) * P
-  uint64_t groups;
-  uint32_t k, r, P;
-  const void* tables;        // (r-1) x k CoefEntry (rows 1..r-1), device
-  int waves_per_cu = 0;      // occupancy cap of the streaming kernel (0 = tuned default)
-};
 
 // Tuned occupancy caps (waves per CU) of the streaming kernels: fewer concurrent waves
 // than the hardware allows keep the HBM request stream more local and measured faster
@@ -48,62 +32,6 @@ inline uint32_t occupancy_cap_lds(int waves_per_cu, uint32_t waves_per_block) {
   return 160u * 1024u / (blocks + 1) + 16u;
 }
 
-struct LevelMeta {           // codebook levels e = 1..32 (see gf256.hpp)
-  uint64_t base[33];
-  uint64_t stride[33];
-  uint64_t count_r[33];      // C(r, e)
-};
-
-// Decode kernel selection (tests / probes; the library uses kDecodeAuto).
-constexpr int kDecodeAuto = 0;           // the measured best of the forms below
-constexpr int kDecodeWavePerGroup = 1;   // one wave per group, 16-B lanes only
-constexpr int kDecodeTiledPlain = 2;     // workgroup = whole groups, per-lane records
-constexpr int kDecodeTiledNt = 3;        //   same, non-temporal stores
-constexpr int kDecodeWavePlain = 4;      // one wave per group, 16-B passes + 4-B tail
-constexpr int kDecodeWaveNt = 5;         //   same, non-temporal stores (the default)
-constexpr int kDecodeWaveNoBranch = 6;   //   same, no branch on coefficient 0 / 1
-constexpr int kDecodeFused = 7;          // one wave per group, 16-B and 4-B pieces fused
-constexpr int kDecodeFusedDirect = 8;    //   same, survivor addresses from the erasure mask
-
-struct DecodeLaunch {
-  int variant = kDecodeAuto;
-  // Where rebuilt shards are stored, same layout as `data`; nullptr = in place in `data`.
-  // May be a device-visible pointer to page-locked host memory (zero-copy writes).
-  uint8_t* out = nullptr;
-  uint8_t* data;
-  const uint8_t* parity;
-  const uint64_t* masks;
-  uint32_t* rec_off;         // workspace, one u32 per group
-  uint8_t* status;           // nullable
-  const uint8_t* codebook;   // device
-  const uint64_t* binom;     // device, 65 x 65
-  LevelMeta meta;
-  uint64_t groups;
-  uint32_t k, r, P;
-  int waves_per_cu = 0;      // occupancy cap of the decode kernel (0 = tuned default)
-  bool rec_ready = false;    // rec_off already filled by the host (sparse plan): no classify
-  int xcd_swizzle = -1;      // XCD-aware group order: -1 tuned default, 0 off, 1 on
-  // Groups per wave of the mask-addressed decode (kDecodeScanGroups or 1).  One wave per
-  // group is best when most groups lost data (C3: 5.35 TB/s vs 4.92 at 8 per wave); when few
-  // did (C5, iid 1% loss: ~10% of groups) 8 per wave saves the dispatch and mask-load latency
-  // of the waves that find nothing to do (0.257 -> 0.243 ms per 1M groups,
-  // profiles/r02_probe_decode_scan.txt).  The host paths that know the masks pick it.
-  uint32_t scan = 1;
-  // `codebook` holds coefficient bytes (compact layout, gf256.hpp) rather than CoefEntry
-  // tables: set exactly when decode_compact_tables(*this) (launch_decode checks).
-  bool compact_tables = false;
-  // Rebuilt shards go to out + (g * r + m) * P (m-th lost data shard of group g, ascending),
-  // `data` is only read (fec_recover_batch_rs_dev); else in place / at `out` like `data`.
-  bool compact_out = false;
-  // compact_out with rec_off = the packed rows' row_start (fec_recover_batch_rs_dev_packed):
-  // rows are placed by global row index, so chunked launches must not offset `out`.
-  bool packed_rows = false;
-};
-
-constexpr uint32_t kDecodeScanGroups = 8;
-// Share of groups needing a rebuild below which the host paths use the scan form.
-constexpr double kDecodeScanMaxShare = 0.25;
-
 constexpr int kDecodeFusedXcdSwizzle = 1;  // tuned per kernel (fec_kernels.hip decode_swizzle)
 constexpr int kDecodeWaveXcdSwizzle = 1;
 
@@ -115,44 +43,14 @@ hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s);
 uint64_t rows_prefix_workspace_bytes(uint64_t groups);
 hipError_t launch_rows_prefix(const uint64_t* masks, uint64_t groups, uint32_t k, uint32_t r, uint32_t* row_start,
                               uint32_t* block_sums, uint64_t* total, hipStream_t s);
-// Packed recover in one launch (recover_runs, fec_kernels.hip): every workgroup owns 512
-// consecutive groups, finds its run's first row by decoupled look-back (no prefix launches)
-// and writes its rebuilt rows as one contiguous run, staged through an LDS image of up to
-// stage bytes.  Mask-addressed shapes only (runs_supported).
-struct RunsLaunch {
-  const uint8_t* data;
-  const uint8_t* parity;
-  const uint64_t* masks;
-  uint64_t groups;
-  uint32_t k, r, P;
-  const uint8_t* codebook;   // dense CoefEntry codebook (the mask-addressed decode's)
-  LevelMeta meta;
-  uint8_t* out;              // packed rows
-  uint32_t* row_start;       // one u32 per group (written)
-  uint64_t* total;           // nullable: all rows
-  uint8_t* status;           // nullable
-  // runs_workspace_bytes(groups) of device memory, zeroed when first allocated, kept by the
-  // caller stream: ticket counter, chunk totals, look-back words
-  void* workspace;
-  // look-back epoch of the first launch; a call takes runs_launches(groups) epochs, never
-  // reused while the workspace lives (the caller counts; < 2^30, then re-zero the workspace)
-  uint32_t epoch;
-  int stage_bytes = -1;      // LDS run image: -1 tuned default (test switch kRunsStage), 0 none
-};
 // LDS run image per workgroup of 512 groups (tools/probe_runs.hip; DESIGN_HISTORY.md §5 round 4): C5's
 // ~59 rows per tile fit 48 KB (40 rows) mostly; two workgroups per CU.
 // recover_runs' run image per workgroup.
 constexpr int kRunsStageBytes = 48 * 1024;
-bool runs_supported(uint32_t k, uint32_t r, uint32_t P);
 uint32_t runs_launches(uint64_t groups);
 uint64_t runs_workspace_bytes(uint64_t groups);
 uint32_t runs_stage_bytes(const RunsLaunch& a);
 hipError_t launch_recover_runs(const RunsLaunch& a, hipStream_t s);
-// Whether launch_decode(a) uses the rec_off workspace (every form but the mask-addressed
-// one, which classifies inline).  The caller then provides a workspace private to the call.
-bool decode_needs_rec_off(const DecodeLaunch& a);
-// Whether launch_decode(a) runs a form that reads a compact codebook (coefficient bytes).
-bool decode_compact_tables(const DecodeLaunch& a);
 // ---- resident legacy encoder (fec_coalesce.cpp "resident server") ----
 // A ring of submission slots (page-locked coherent host memory, or VRAM written through the BAR).
 // The host fills slot seq % kServerSlots with a legacy call's groups: every 8-B word of a slot

@@ -84,7 +84,7 @@ struct LaunchRecord {
   int64_t nt = -1;       //  4-B pieces per lane
   int64_t off = -1;      // encode: OffsetKind of the instantiation
   int64_t first = -1;    // encode_v16: this pass owns the XOR row
-  int64_t pol = -1;      // memory policy / form bits (fec_kernels.hip kNtLoad .. kStageRows)
+  int64_t pol = -1;      // memory policy / form bits (fec_forms.hpp kNtLoad .. kStageRows)
   int64_t direct = -1;   // decode_fused: mask-addressed; rows_write: writes the total itself
   int64_t scan = -1;     // decode_fused: groups per wave of the scan form (0: one wave per group)
   int64_t tile = -1;     // groups per workgroup of the tiled mappings, 0 = flat mapping

@@ -622,7 +622,16 @@ int decode_dev_locked(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_pari
   a.r = r;
   a.P = P;
   a.rec_ready = !plan->dense;
-  if (plan->dense && qfec::decode_compact_tables(a)) {
+  // Groups per wave of the mask-addressed form: the scan form when the caller knows that
+  // few groups need a rebuild (need_share, from a host scan of the masks); device-resident
+  // callers get one wave per group (the test library's TestKnob::kDecodeScan overrides it).
+  if (need_share < 0.0) need_share = ctx->decode_need_share;
+  if (need_share >= 0.0 && need_share < qfec::kDecodeScanMaxShare) a.scan = qfec::kDecodeScanGroups;
+  a.scan = static_cast<uint32_t>(qfec::test_knob(qfec::TestKnob::kDecodeScan, a.scan));
+  // The kernel form of this call (fec_forms.hpp); what is attached to `a` below -- codebook,
+  // workspace, row starts -- does not change it.
+  const qfec::DecodeForm form = qfec::decode_form(a);
+  if (form.compact_tables) {
     // the form reads bare coefficient bytes: the compact book of the same patterns
     if (!plan->cbook.ptr) {
       std::vector<uint8_t> book;
@@ -641,27 +650,14 @@ int decode_dev_locked(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_pari
       a.meta.stride[e] = plan->clayout.level_stride[e];
     }
   }
-  // Groups per wave of the mask-addressed form: the scan form when the caller knows that
-  // few groups need a rebuild (need_share, from a host scan of the masks); device-resident
-  // callers get one wave per group (the test library's TestKnob::kDecodeScan overrides it).
-  if (need_share < 0.0) need_share = ctx->decode_need_share;
-  if (need_share >= 0.0 && need_share < qfec::kDecodeScanMaxShare) a.scan = qfec::kDecodeScanGroups;
-  a.scan = static_cast<uint32_t>(qfec::test_knob(qfec::TestKnob::kDecodeScan, a.scan));
   if (row_start != nullptr) {
-    // packed rows: only the mask-addressed (inline-classify) forms place rows by row_start,
-    // which they read from rec_off
-    if (!plan->dense || qfec::decode_needs_rec_off(a)) {
+    // refused, one recover_runs launch, or the row prefix + the mask-addressed decode_fused
+    const qfec::PackedForm packed = qfec::packed_form(a, form, qfec::test_knob(qfec::TestKnob::kPackedRuns, -1));
+    if (packed == qfec::PackedForm::kRefused) {
       set_error("packed recover: no mask-addressed form for k=%u r=%u P=%u (use fec_recover_batch_rs_dev)", k, r, P);
       return FEC_ERR_RANGE;
     }
-    // Sparse loss (the scan form's share): one launch, recover_runs --
-    // each workgroup finds its rows' place by decoupled look-back and writes them as one run
-    // (C5: 0.229-0.235 vs 0.242-0.268 ms for the slot rows; profiles/r04_probe_runs_*.txt).
-    // Dense loss keeps the prefix launches + decode_fused (the runs form rebuilds a workgroup's
-    // groups wave by wave: 2.7-2.8 vs 2.2-2.45 ms at C3).  The test library's
-    // TestKnob::kPackedRuns forces it on (1) or off (0).
-    const long runs_env = qfec::test_knob(qfec::TestKnob::kPackedRuns, -1);
-    if (runs_env != 0 && (runs_env == 1 || a.scan == qfec::kDecodeScanGroups) && qfec::runs_supported(k, r, P)) {
+    if (packed == qfec::PackedForm::kRuns) {
       qfec::RunsLaunch ra{};
       ra.data = d_data;
       ra.parity = d_parity;
@@ -690,7 +686,7 @@ int decode_dev_locked(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_pari
   }
   // Workspace: the caller's slot buffer (pipeline slots: private stream, calls serialised
   // by the context lock), else one private to this call.
-  if (row_start == nullptr && (!plan->dense || qfec::decode_needs_rec_off(a))) {
+  if (row_start == nullptr && form.rec_off) {
     if (rec) {
       QFEC_HIP(rec->ensure(G * sizeof(uint32_t)));
       a.rec_off = rec->as<uint32_t>();

@@ -374,7 +374,7 @@ int main(int argc, char** argv) {
     dl.waves_per_cu = v.waves;
     dl.xcd_swizzle = v.swz;
     poison<<<uint32_t((nd + 255) / 256), 256>>>(data, masks, G, k, P);
-    CK(v.fn ? v.fn(dl) : launch_decode(with_book(dl, decode_compact_tables(dl)), nullptr));
+    CK(v.fn ? v.fn(dl) : launch_decode(with_book(dl, decode_form(dl).compact_tables), nullptr));
     CK(hipDeviceSynchronize());
     std::vector<uint8_t> a(nd), b(nd);
     CK(hipMemcpy(a.data(), data, nd, hipMemcpyDeviceToHost));
@@ -390,7 +390,7 @@ int main(int argc, char** argv) {
       dl.waves_per_cu = v.waves;
       dl.xcd_swizzle = v.swz;
       CK(hipEventRecord(e0));
-      CK(v.fn ? v.fn(dl) : launch_decode(with_book(dl, decode_compact_tables(dl)), nullptr));
+      CK(v.fn ? v.fn(dl) : launch_decode(with_book(dl, decode_form(dl).compact_tables), nullptr));
       CK(hipEventRecord(e1));
       CK(hipEventSynchronize(e1));
       float ms;

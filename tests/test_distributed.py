@@ -172,7 +172,7 @@ def test_shard_range_single():
 
 def test_bench_decode_api_shapes():
     """bench.py's packed-recover shape rule mirrors the library's mask-addressed forms
-    (fec_kernels.hip try_decode_fused QFEC_FUSED_DS / _D; tests/test_gpu_packed.py checks the
+    (fec_forms.hpp QFEC_MASK_SHAPES and QFEC_LAYOUTS; tests/test_gpu_packed.py checks the
     library refuses the rest)."""
     import bench
     assert bench.packed_supported(10, 3, 1200) and bench.packed_supported(10, 1, 700)

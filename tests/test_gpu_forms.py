@@ -8,16 +8,20 @@ lost shards, 0x5A in unwritten output, 7 in unwritten status), and the launches 
 below.
 
 The table (expected_decode / expected_encode) is written from the dispatch rules as documented --
-DESIGN.md §5b, include/fec_hip.h and the comments of launch_encode / launch_decode /
-try_decode_fused / try_recover_runs in csrc/fec_kernels.hip -- not from what the code was seen
-to do.  A trace that differs from it means either the dispatch or its documentation changed.
+DESIGN.md §5b, include/fec_hip.h and the comments of the lists and rules in csrc/fec_forms.hpp
+-- not from what the code was seen to do.  A trace that differs from it means either the
+dispatch or its documentation changed.  The CPU tests at the end check the same table against
+the deciding code itself (fec_forms.hpp, through tests/csrc/forms_dump.cpp) at every packet size.
 
 Masks are permutation(k + r)[:0..r+1] per group (untouched and unrecoverable groups and lost
 parity in every case) unless a test says otherwise.
 """
 import itertools
+import os
+import subprocess
 from functools import lru_cache
 from math import comb
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -26,10 +30,10 @@ gpu = pytest.mark.gpu
 
 SEED = 0x5EEDF000
 
-# `pol` bits of a launch record (csrc/fec_kernels.hip)
+# `pol` bits of a launch record (csrc/fec_forms.hpp)
 NT_LOAD, NT_STORE, NO_BRANCH, LDS_TABS, COMPACT, COEF_BYTES, PAIR_MAC, STAGE = 1, 2, 4, 64, 1024, 2048, 4096, 8192
 
-# Shapes with compiled decode forms (fec_kernels.hip try_decode_fused / launch_decode lists)
+# Shapes with compiled decode forms (the lists of csrc/fec_forms.hpp, restated independently)
 MASK_SHAPES = {(10, 3), (10, 1), (10, 2), (4, 2)}      # mask-addressed decode_fused + recover_runs
 TILED_SHAPES = {(10, 3), (10, 1), (4, 2)}              # decode_tiled that auto takes (P <= 256)
 WAVE_SHAPES = {(10, 3), (10, 1), (20, 5), (4, 2)}      # compile-time-k decode_wave
@@ -618,29 +622,43 @@ def test_every_mask(gpu_ctx_hooks, quicfec_mod, oracle_mod, torch_cuda, monkeypa
 
 
 # ---- the table against the list of compiled instantiations (no GPU) -----------------------------
-def compiled_instantiations():
-    """The kernel instantiations libfec_hip.so carries, from the lists in fec_kernels.hip
-    (try_decode_fused, try_recover_runs, launch_decode, launch_encode, run_encode_generic)."""
-    out = set()
-    for (k, r) in MASK_SHAPES:
-        for nm, nt in LAYOUTS:
-            for c in (0, COMPACT):
-                out.add(form("decode_fused", k=k, r=r, nm=nm, nt=nt, direct=1, scan=0, pol=NT_STORE | NT_LOAD | c))
-                if (k, r) == (10, 3):
-                    out.add(form("decode_fused", k=k, r=r, nm=nm, nt=nt, direct=1, scan=SCAN, pol=NT_STORE | NT_LOAD | c))
-            out.add(form("recover_runs", k=k, r=r, nm=nm, nt=nt, pol=NT_LOAD | NT_STORE))
-    for nm, nt in LAYOUTS:
-        for c in (0, COMPACT):
-            out.add(form("decode_fused", k=20, r=5, nm=nm, nt=nt, direct=0, scan=0,
-                         pol=NT_STORE | NT_LOAD | LDS_TABS | COEF_BYTES | c))
-    out.add(form("decode_fused", k=10, r=3, nm=1, nt=1, direct=0, scan=0, pol=NT_STORE))   # record-addressed
-    for (k, r) in TILED_SHAPES | {(20, 5)}:
-        for c in (0, COMPACT):
-            out.add(form("decode_tiled", k=k, r=r, pol=NT_STORE | c))
-    for (k, r) in WAVE_SHAPES:
-        out.add(form("decode_wave", k=k, r=r, pol=NT_STORE, aux=0))
-    for c in (0, COMPACT):
-        out.add(form("decode_wave", k=0, r=8, pol=NT_STORE | NO_BRANCH | c, aux=0))
+CSRC = Path(__file__).resolve().parent.parent / "quic-test_amd" / "csrc"
+
+
+@pytest.fixture(scope="module")
+def forms_dump(tmp_path_factory):
+    """tests/csrc/forms_dump.cpp, which asks csrc/fec_forms.hpp -- the code that decides the forms
+    -- with no GPU: run(*args, **env) -> its output lines.  Built twice like the libraries: plain
+    (every switch at its default) and with -DQUICFEC_TEST_HOOKS (switches read from the
+    environment); a call with env runs the latter."""
+    d = tmp_path_factory.mktemp("forms_dump")
+    for exe, flags in (("plain", []), ("hooks", ["-DQUICFEC_TEST_HOOKS"])):
+        subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", *flags, "-I", str(CSRC),
+                        str(Path(__file__).parent / "csrc" / "forms_dump.cpp"), str(CSRC / "fec_knobs.cpp"),
+                        "-o", str(d / exe)], check=True)
+
+    def run(*args, **env):
+        clean = {k: v for k, v in os.environ.items() if not k.startswith("QUICFEC_")}
+        out = subprocess.run([str(d / ("hooks" if env else "plain")), *args], capture_output=True, text=True,
+                             check=True, timeout=120, env=dict(clean, **env))
+        return out.stdout.splitlines()
+    return run
+
+
+def _parse_launch(text):
+    """'decode_fused k=10 r=3 ...' -> a launch record like quicfec.launch_trace's (-1 = not set)."""
+    name, *fields = text.split()
+    rec = dict({f: -1 for f in _FIELDS + ("tile",)}, form=name)
+    rec.update((key, int(val)) for key, val in (f.split("=") for f in fields))
+    return rec
+
+
+def compiled_instantiations(forms_dump):
+    """The kernel instantiations libfec_hip.so carries: the decode forms and recover_runs as
+    forms_dump --compiled expands them from the lists of csrc/fec_forms.hpp that launch_decode and
+    launch_recover_runs dispatch on; the encodes and the rest from the lists in fec_forms.hpp /
+    fec_kernels.hip (QFEC_ENCODE_*_FORMS, run_encode_generic)."""
+    out = {sig_of(_parse_launch(line)) for line in forms_dump("--compiled")}
     for off in range(4):
         out.add(form("encode_bytes", k=0, off=off))
         for rows in range(1, 9):
@@ -659,8 +677,6 @@ def compiled_instantiations():
             out.add(form("encode_bits", k=k, r=r, off=0, pol=NT_STORE | s))
     for name in ("classify", "rows_block_sums", "rows_scan_blocks", "fill", "copy", "legacy_server"):
         out.add(form(name))
-    for c in (0, COMPACT):      # one kernel, the layout a runtime argument
-        out.add(form("decode_bytes", k=0, pol=c))
     out.add(form("rows_write", direct=0))
     out.add(form("rows_write", direct=1))
     return out
@@ -711,12 +727,64 @@ NOT_LAUNCHED_HERE = {
 }
 
 
-def test_table_covers_the_compiled_dispatch_forms():
+DUMP_P = list(range(1, 2101)) + [4096, 8192, 8193, 9000]
+DUMP_SHAPES = DECODE_SHAPES + [(6, 3), (7, 4), (12, 6), (12, 9), (16, 4)]
+
+
+def _dump_queries(lines, kind):
+    """(query fields, launches or None) of the dump's lines of one kind."""
+    for line in lines:
+        query, _, launches = line.partition(" | ")
+        if query.split()[0] == kind:
+            q = dict(f.split("=") for f in query.split()[1:])
+            yield q, (None if launches == "refused" else [t.strip() for t in launches.split(";")])
+
+
+def _check_decode_lines(lines, runs):
+    prefix = [form("rows_block_sums"), form("rows_write", direct=1)]     # the packed prefix the table names
+    seen = set()
+    for q, launches in _dump_queries(lines, "decode"):
+        api, k, r, P, scan = q["api"], int(q["k"]), int(q["r"]), int(q["P"]), int(q["scan"])
+        assert int(q["runs"]) == (1 if runs else -1)
+        exp = expected_decode(api, k, r, P, scan=scan == SCAN, runs=runs)
+        if launches is not None:
+            launches = [s for t in launches for s in (prefix if t == "rows_prefix" else [sig_of(_parse_launch(t))])]
+        assert launches == exp, (q, launches, exp)
+        seen.add((api, k, r, P, scan))
+    return seen
+
+
+def test_decided_decode_forms_equal_the_table(forms_dump):
+    """The deciding code (csrc/fec_forms.hpp decode_form / packed_form, asked by forms_dump)
+    against the table, for every packet size 1..2100 and four larger ones, the compiled shapes and
+    five runtime-k ones, every API, scan 1 and 8; the packed call also with QUICFEC_PACKED_RUNS=1."""
+    lines = forms_dump()
+    seen = _check_decode_lines(lines, runs=False)
+    assert seen == {(api, k, r, P, scan) for api in ("in_place", "slots", "packed") for (k, r) in DUMP_SHAPES
+                    for P in DUMP_P for scan in (1, SCAN)}
+    seen = _check_decode_lines(forms_dump("--packed", QUICFEC_PACKED_RUNS="1"), runs=True)
+    assert seen == {("packed", k, r, P, scan) for (k, r) in DUMP_SHAPES for P in DUMP_P for scan in (1, SCAN)}
+
+
+def test_decided_encode_forms_equal_the_table(forms_dump):
+    """csrc/fec_forms.hpp encode_form (and the launcher's passes of 8 rows) against the table: the
+    same sizes and shapes, contiguous packets, u32 and u64 offsets."""
+    seen = set()
+    for q, launches in _dump_queries(forms_dump(), "encode"):
+        k, r, P, off = int(q["k"]), int(q["r"]), int(q["P"]), int(q["off"])
+        recs = [_parse_launch(t) for t in launches]
+        got = [(sig_of(t), None if t["tile"] < 0 else "tile" if t["tile"] > 0 else "flat") for t in recs]
+        assert got == expected_encode(k, r, P, off=off), (q, got)
+        seen.add((k, r, P, off))
+    assert seen == {(k, r, P, off) for (k, r) in DUMP_SHAPES for P in DUMP_P for off in (0, 1, 2)}
+
+
+def test_table_covers_the_compiled_dispatch_forms(forms_dump):
     """The cases of this file, by the table, launch every instantiation of the decode forms that
     the library's own choice can reach -- 81 of the 90 mask-addressed decode_fused, all 18
     LDS-table ones, 33 of the 36 recover_runs, the 6 tiled and 6 wave ones -- and name nothing
     that is not compiled; what is left is listed with its reason (NOT_LAUNCHED_HERE)."""
-    compiled = {_strip_aux(s) for s in compiled_instantiations()}
+    compiled = {_strip_aux(s) for s in compiled_instantiations(forms_dump)}
     launched = launched_by_this_file()
     assert launched <= compiled, sorted(launched - compiled)
     missing = compiled - launched
