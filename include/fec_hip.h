@@ -86,7 +86,12 @@ int fec_decode_batch_rs(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* parity
                         uint64_t* unrecoverable_out);
 
 /* ---- device-resident API: device pointers only, asynchronous on `stream`
- * (a hipStream_t; NULL = the context's own stream).  Contiguous layout only. ---- */
+ * (a hipStream_t; NULL = the context's own stream).  Contiguous layout only.
+ * A call returns once its kernels are queued; they read the context's tables and workspaces
+ * until they have run.  fec_encoder_free waits for the context's calls queued on caller
+ * streams (it drains the device when any call took one) and on its own stream before it
+ * frees them, so a context may be freed with work in flight; the caller's own buffers must
+ * outlive that work as usual. ---- */
 int fec_encode_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, uint64_t num_groups,
                             uint32_t k, uint32_t r, uint32_t packet_size, uint8_t* d_parity,
                             void* stream);

@@ -109,6 +109,22 @@ struct RunsLaunch {
   int stage_bytes = -1;      // LDS run image: -1 tuned default (test switch kRunsStage), 0 none
 };
 
+// The look-back epochs of a call of n launches on a workspace whose last launch used epoch
+// `last` (0: none since the workspace was zeroed): first .. first + n - 1, each non-zero and
+// below `limit`, none handed out twice while the workspace's words live.  When they would reach
+// the limit the workspace must be zeroed first (`rezero`) and the count starts again at 1.
+// Needs n < limit.  The epoch is the 30 bits above bit 34 of a look-back word (fec_kernels.hip
+// kRunEpochShift), so the limit is 2^30 (the test library's TestKnob::kRunsEpochLimit lowers it).
+constexpr uint32_t kRunsEpochLimit = 1u << 30;
+struct RunsEpochs {
+  uint32_t first;
+  bool rezero;
+};
+constexpr RunsEpochs runs_epochs(uint32_t last, uint32_t n, uint32_t limit) {
+  const bool rezero = static_cast<uint64_t>(last) + n >= limit;
+  return {(rezero ? 0u : last) + 1u, rezero};
+}
+
 // Memory policy bits of the streaming kernels.
 constexpr int kNtLoad = 1;        // non-temporal loads (data read once)
 constexpr int kNtStore = 2;       // non-temporal stores

@@ -20,6 +20,7 @@ const char* const kNames[] = {
     "QUICFEC_ENCODE_BLOCKS",       "QUICFEC_ENCODE_WAVES",         "QUICFEC_ENCODE_BITS",
     "QUICFEC_ENCODE_STAGE",        "QUICFEC_DECODE_WAVES",         "QUICFEC_ROWS_DIRECT_BLOCKS",
     "QUICFEC_RUNS_STAGE",          "QUICFEC_DECODE_SCAN",          "QUICFEC_PACKED_RUNS",
+    "QUICFEC_RUNS_EPOCH_LIMIT",
     "QUICFEC_RESIDENT_TEST_NOLAUNCH", "QUICFEC_RESIDENT_TEST_EPOCH", "QUICFEC_RESIDENT_TEST_TEAR",
     "QUICFEC_RESIDENT_TEST_FAIL_AT", "QUICFEC_RESIDENT_SPREAD",    "QUICFEC_RESIDENT_STAMPS",
     "QUICFEC_RESIDENT_SLOW_US",    "QUICFEC_COALESCE_STAMPS",      "QUICFEC_COALESCE_SPIN_PAUSE",

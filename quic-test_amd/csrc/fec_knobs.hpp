@@ -30,6 +30,7 @@ enum class TestKnob : int {
   kRunsStage,         // run-image bytes of recover_runs (rows past it go straight to HBM)
   kDecodeScan,        // groups per wave of the mask-addressed decode
   kPackedRuns,        // 1: packed recover in one launch (recover_runs) whatever the loss, 0: never
+  kRunsEpochLimit,    // look-back epochs of recover_runs before its workspace is re-zeroed (2^30)
   kResidentNoLaunch,  // resident encoder: record launches without launching (never serves)
   kResidentEpoch,     // resident encoder: tag epoch (short: scrubs within a few thousand calls)
   kResidentTear,      // resident encoder: store one chunk / later address words ~100 us late
@@ -73,6 +74,7 @@ enum class LaunchForm : int64_t {
   kCopy = 14,
   kLegacyServer = 15,
   kDecodeV16 = 16,  // probe builds only
+  kRunsRezero = 17,  // no kernel: recover_runs' workspace zeroed again because its epochs wrapped
 };
 
 // One launch: 16 words, -1 where a field does not apply to the form.

@@ -336,13 +336,17 @@ struct FECEncoderCtx {
   // per-stream record-offset workspaces of the device-resident decodes (stream_workspace)
   std::vector<std::unique_ptr<StreamWorkspace>> stream_ws;
   uint64_t ws_clock = 0;
+  // a call took a caller's stream (pick_stream): its kernels may still be queued there when the
+  // context is freed, reading the plans' tables and the workspaces
+  bool caller_streams = false;
 
   ~FECEncoderCtx() {
     DeviceGuard g(device);
-    if (!stream_ws.empty()) {  // caller streams may still run decodes that read them
-      (void)hipDeviceSynchronize();
-      stream_ws.clear();
-    }
+    // Freeing waits for the calls queued on caller streams (include/fec_hip.h): their streams are
+    // not known here any more (or gone), so the device drains.  Also the mask-addressed decodes
+    // and the encodes, which take no workspace but read the plan's codebook and tables.
+    if (caller_streams || !stream_ws.empty()) (void)hipDeviceSynchronize();
+    stream_ws.clear();
     if (stream) (void)hipStreamSynchronize(stream);
     for (auto& p : pipe)
       if (p.s) (void)hipStreamSynchronize(p.s);
@@ -490,7 +494,9 @@ int get_decode_plan(FECEncoderCtx* ctx, uint32_t k, uint32_t r, DecodePlan** out
   return FEC_OK;
 }
 
+// Caller holds ctx->mu.
 hipStream_t pick_stream(FECEncoderCtx* ctx, void* stream) {
+  if (stream) ctx->caller_streams = true;
   return stream ? static_cast<hipStream_t>(stream) : ctx->stream;
 }
 
@@ -547,25 +553,40 @@ hipError_t stream_workspace(FECEncoderCtx* ctx, hipStream_t s, size_t bytes, voi
 
 // The recover_runs workspace of caller stream s and the first look-back epoch of a call of G
 // groups.  Epochs are never reused while the buffer lives (words of earlier launches on this
-// stream cannot match); the buffer is zeroed when allocated and when the epochs wrap.
+// stream cannot match); the buffer is zeroed when allocated and when the epochs wrap (on the
+// stream, so after the launches already queued on it).
 hipError_t runs_workspace(FECEncoderCtx* ctx, hipStream_t s, uint64_t G, void** out, uint32_t* epoch) {
   StreamWorkspace* w = nullptr;
   hipError_t e = find_stream_ws(ctx, s, &w);
   if (e != hipSuccess) return e;
   const uint64_t bytes = qfec::runs_workspace_bytes(G);
   const uint32_t n = qfec::runs_launches(G);
+  const long lim = qfec::test_knob(qfec::TestKnob::kRunsEpochLimit, qfec::kRunsEpochLimit);
+  const uint32_t limit = lim >= 2 && lim < static_cast<long>(qfec::kRunsEpochLimit) ? static_cast<uint32_t>(lim)
+                                                                                     : qfec::kRunsEpochLimit;
+  if (n >= limit) return hipErrorInvalidValue;  // never at 2^30: a call has at most 2^32 / 512 launches
+  bool fresh = false;
   if (bytes > w->runs.cap) {
     if (w->runs.ptr && (e = hipStreamSynchronize(s)) != hipSuccess) return e;
     if ((e = w->runs.ensure(bytes)) != hipSuccess) return e;
     w->epoch = 0;
+    fresh = true;
+  }
+  // the epoch accounting (fec_forms.hpp runs_epochs; tests/csrc/runs_epoch_test.cpp)
+  const qfec::RunsEpochs ep = qfec::runs_epochs(w->epoch, n, limit);
+  if (fresh || ep.rezero) {
     if ((e = hipMemsetAsync(w->runs.ptr, 0, w->runs.cap, s)) != hipSuccess) return e;
-  } else if (w->epoch + n >= (1u << 30)) {
-    w->epoch = 0;
-    if ((e = hipMemsetAsync(w->runs.ptr, 0, w->runs.cap, s)) != hipSuccess) return e;
+    if (!fresh) {  // the wrap alone is traced (test library): not the first allocation, not growth
+      qfec::LaunchRecord t;
+      t.form = static_cast<int64_t>(qfec::LaunchForm::kRunsRezero);
+      t.items = static_cast<int64_t>(w->runs.cap);  // bytes zeroed
+      t.aux = static_cast<int64_t>(w->epoch);       // the last epoch used before the wrap
+      qfec::trace_launch(t);
+    }
   }
   *out = w->runs.ptr;
-  *epoch = w->epoch + 1;
-  w->epoch += n;
+  *epoch = ep.first;
+  w->epoch = ep.first + n - 1;
   return hipSuccess;
 }
 

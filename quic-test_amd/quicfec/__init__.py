@@ -539,7 +539,8 @@ def coalesce_stats(reset: bool = False) -> dict:
 # ---- launch trace (csrc/fec_knobs.hpp LaunchRecord; live in libfec_hip_test.so only) ----
 LAUNCH_FORMS = {1: "encode_v16", 2: "encode_bits", 3: "encode_bytes", 4: "classify", 5: "decode_fused",
                 6: "decode_tiled", 7: "decode_wave", 8: "decode_bytes", 9: "rows_block_sums", 10: "rows_scan_blocks",
-                11: "rows_write", 12: "recover_runs", 13: "fill", 14: "copy", 15: "legacy_server", 16: "decode_v16"}
+                11: "rows_write", 12: "recover_runs", 13: "fill", 14: "copy", 15: "legacy_server", 16: "decode_v16",
+                17: "runs_rezero"}     # no kernel: recover_runs' workspace re-zeroed at an epoch wrap (items = bytes)
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16

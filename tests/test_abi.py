@@ -74,7 +74,7 @@ def test_product_library_has_no_test_switches(quicfec_mod):
     test = _knob_names(quicfec_mod.TEST_LIB_PATH)
     assert PRODUCT_KNOBS < test
     assert {"QUICFEC_RESIDENT_TEST_FAIL_AT", "QUICFEC_RESIDENT_TEST_TEAR", "QUICFEC_MAX_WAVE_BLOCKS",
-            "QUICFEC_ENCODE_BITS", "QUICFEC_PACKED_RUNS"} <= test
+            "QUICFEC_ENCODE_BITS", "QUICFEC_PACKED_RUNS", "QUICFEC_RUNS_EPOCH_LIMIT"} <= test
     syms = []
     for lib in (quicfec_mod.LIB_PATH, quicfec_mod.TEST_LIB_PATH):
         out = subprocess.run(["nm", "-D", "--defined-only", str(lib)], capture_output=True, text=True,
@@ -107,6 +107,7 @@ def test_product_library_keeps_no_launch_trace(quicfec_mod):
     ids = {int(m.group(2)): re.sub(r"(?<!^)(?=[A-Z])", "_", m.group(1)).lower()
            for m in re.finditer(r"^\s*k(\w+) = (\d+),", enum, re.M)}
     assert ids == quicfec_mod.LAUNCH_FORMS
+    assert ids[17] == "runs_rezero" and len(ids) == 17      # the epoch wrap's record (tests/test_gpu_streams.py)
     rec = re.search(r"struct LaunchRecord \{(.*?)\};", hpp, re.S).group(1)
     assert tuple(re.findall(r"^\s*int64_t (\w+)", rec, re.M)) == quicfec_mod.LAUNCH_FIELDS
 
@@ -375,6 +376,24 @@ def test_test_switch_names_match_their_enum():
         return "QUICFEC_" + snake
 
     assert [env_of(k) for k in keys] == names
+    assert dict(zip(keys, names))["RunsEpochLimit"] == "QUICFEC_RUNS_EPOCH_LIMIT"
+
+
+def test_runs_epoch_accounting(tmp_path):
+    """The look-back epochs of the one-launch packed recover (csrc/fec_forms.hpp runs_epochs, which
+    fec_shim.cpp runs_workspace calls), over long random call sequences at the real limit -- the
+    counter started just below 2^30, a point a receiver reaches after days -- and at small limits:
+    every epoch non-zero and below 2^30, a call's epochs consecutive, none handed out twice between
+    two re-zeroes, a re-zero exactly when the rule asks for one (tests/csrc/runs_epoch_test.cpp)."""
+    csrc = REPO / "quic-test_amd" / "csrc"
+    exe = tmp_path / "runs_epoch_test"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-I", str(csrc),
+                    str(REPO / "tests" / "csrc" / "runs_epoch_test.cpp"), str(csrc / "fec_knobs.cpp"), "-o", str(exe)],
+                   check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout + out.stderr
+    calls, rezeroes = int(out.stdout.split()[1]), int(out.stdout.split()[3])
+    assert calls > 1_000_000 and rezeroes > 100_000, out.stdout
 
 
 def test_headers_are_plain_c_and_link_from_c(tmp_path, quicfec_mod):
