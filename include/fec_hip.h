@@ -138,6 +138,36 @@ int fec_recover_batch_rs_dev_packed(FECEncoderCtx* ctx, const uint8_t* d_data, c
                                     uint32_t packet_size, uint8_t* d_rebuilt, uint32_t* d_row_start,
                                     uint64_t* d_total, uint8_t* d_status, void* stream);
 
+/* ---- address tables: shards and packets wherever they are in device memory ----
+ * A receiver that keeps its packets in device memory, in arrival order in a ring or an arena,
+ * hands over a table of their addresses instead of copying them into the contiguous layout.
+ *   - A shard may have any byte alignment; its packet_size bytes must be readable.
+ *   - Shards may lie in any number of allocations on the context's device.
+ *   - The output buffer must not overlap any shard.
+ *   - The decode rule is unchanged: every surviving data shard plus the lowest-indexed surviving
+ *     parity rows.  A lost shard's entry, and a parity row the rule does not use, is never read.
+ *   - Both calls are asynchronous on `stream` like the other _dev calls, and fec_encoder_free
+ *     drains them the same way.
+ * Refused with nothing launched or written (fec_hip_last_error says which case applied):
+ * FEC_ERR_NULL for a NULL context or required pointer; FEC_ERR_RANGE for k + r > 64, for
+ * packet_size < 16 (QUIC packets are never that short), for num_groups == 0 or >= 2^32, and, for
+ * the recover, for a shape whose decode codebook exceeds the 2 GiB cap (fec_decode_prepare: the
+ * sparse plan reads masks back on the host, which this call does not do). */
+
+/* Recover from shards wherever they are.  d_shard_addrs: num_groups*(k+r) absolute device
+ * addresses (u64), group g's shard s at [g*(k+r) + s], data shards 0..k-1 then parity rows
+ * 0..r-1; 0 = lost (the convention of fec_batcher_submit_shards).  Output and status exactly as
+ * fec_recover_batch_rs_dev (slots (g*r + m)*P, slots m >= e and unrecoverable groups unwritten).
+ * d_masks_out (nullable): the erasure mask derived for each group. */
+int fec_recover_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t num_groups,
+                              uint32_t k, uint32_t r, uint32_t packet_size, uint8_t* d_rebuilt,
+                              uint8_t* d_status, uint64_t* d_masks_out, void* stream);
+
+/* Encode k packets per group from absolute device addresses (num_groups*k of them, all valid);
+ * parity contiguous as in fec_encode_batch_rs_dev. */
+int fec_encode_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs, uint64_t num_groups,
+                             uint32_t k, uint32_t r, uint32_t packet_size, uint8_t* d_parity, void* stream);
+
 /* Expected share (0..1) of groups that lost data shards in this context's device-resident
  * decode calls, e.g. 1 - (1 - p)^k for iid loss p (the receiver knows its network profile;
  * satellite p = 0.01, k = 10: ~0.10).  Below 0.25 the decode checks several groups per

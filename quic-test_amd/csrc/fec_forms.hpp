@@ -402,6 +402,55 @@ inline PackedForm packed_form(const DecodeLaunch& a, const DecodeForm& f, long r
   return PackedForm::kPrefixFused;
 }
 
+// ---- recover from an address table (fec_recover_gather_rs_dev, fec_gather.hip) ----
+struct GatherLaunch {
+  const uint64_t* addrs;     // groups * (k + r) absolute device addresses, 0 = lost
+  uint64_t groups;
+  uint32_t k, r, P;
+  uint8_t* out;              // rebuilt row (g, m) at (g * r + m) * P
+  uint8_t* status;           // nullable
+  uint64_t* masks_out;       // nullable: the erasure mask derived for each group
+  uint32_t* rec_off;         // workspace, one u32 per group
+  const uint8_t* codebook;   // dense CoefEntry codebook (the one `classify` addresses), device
+  const uint64_t* binom;     // device, 65 x 65
+  LevelMeta meta;
+};
+
+// The compiled shapes of recover_gather, M(k, r), and its instantiations, X(K, MAXE, POL): a list
+// of their own, apart from the decode lists above.  Every form loads and stores non-temporally and
+// writes the compact slot layout, like the slot recover's mask-addressed form; runtime k takes
+// passes of 8 rows and multiplies by every coefficient (as the runtime-k decode_wave does).
+#define QFEC_GATHER_SHAPES(M, ...) \
+  M(__VA_ARGS__, 10, 3) M(__VA_ARGS__, 10, 2) M(__VA_ARGS__, 10, 1) M(__VA_ARGS__, 4, 2) M(__VA_ARGS__, 20, 5)
+constexpr int kGatherPol = kNtStore | kNtLoad | kCompactOut;
+#define QFEC_GATHER_FIXED(X, K, R) X(K, R, kGatherPol)
+#define QFEC_GATHER_FORMS(X) QFEC_GATHER_SHAPES(QFEC_GATHER_FIXED, X) X(0, 8, kGatherPol | kNoCoefBranch)
+#define QFEC_IS_PAIR(_, A, B) || (a == A && b == B)
+constexpr bool is_gather_shape(uint32_t a, uint32_t b) { return false QFEC_GATHER_SHAPES(QFEC_IS_PAIR, ~); }
+#undef QFEC_IS_PAIR
+
+struct GatherForm {
+  bool supported = false;  // false: P < 16, the call is refused
+  int K = 0, MAXE = 0;     // template shape; runtime k as K = 0, MAXE = 8
+  int POL = 0;
+};
+
+// The form fec_recover_gather_rs_dev runs for (k, r, P): a classify_gather launch, then
+// recover_gather<K, MAXE, POL> in ceil(r / MAXE) passes.  The kernel walks the pieces of any
+// P >= 16 itself, so the size only decides whether the call is served.  Every form takes its
+// records from the dense CoefEntry codebook; k=20 r=5 too (no compact-codebook / LDS-table form).
+inline GatherForm gather_form(uint32_t k, uint32_t r, uint32_t P) {
+  GatherForm f;
+  if (P < kVecMinP) return f;
+  f.supported = true;
+  if (is_gather_shape(k, r)) {
+    f.K = static_cast<int>(k), f.MAXE = static_cast<int>(r), f.POL = kGatherPol;
+  } else {
+    f.K = 0, f.MAXE = 8, f.POL = kGatherPol | kNoCoefBranch;
+  }
+  return f;
+}
+
 // ---- encode ----
 enum class EncodeKernel : int { kBytes, kV16, kBits };
 

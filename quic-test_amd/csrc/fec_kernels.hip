@@ -29,39 +29,13 @@
 
 #include "bitslice.hpp"
 #include "coef_tables.hpp"
+#include "fec_device.hpp"  // Tab, ld16 / st16, gmul, ldw / stw, decode_block
 #include "fec_kernels.hpp"
 #include "fec_knobs.hpp"
+#include "fec_launch.hpp"  // launch limits, for_chunks, launch_record
 
 namespace qfec {
 namespace {
-
-struct Tab {
-  uint32_t t0lo, t0hi, t1lo, t1hi, t2, coef, p0, p1;
-};
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// Byte-aligned views for packet memory (any P, any packet address): same dwordx4 / dword
-// instructions as the aligned types.
-typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-typedef uint32_t u32u __attribute__((aligned(1)));
-
-// The memory policy / form bits of the kernels' POL parameter (kNtLoad .. kStageRows): fec_forms.hpp.
-
-template <int POL>
-__device__ __forceinline__ u32x4 ld16(const uint8_t* p) {
-  if constexpr ((POL & kNtLoad) != 0) return __builtin_nontemporal_load(reinterpret_cast<const u32x4u*>(p));
-  else return *reinterpret_cast<const u32x4u*>(p);
-}
-
-template <int POL>
-__device__ __forceinline__ void st16(uint8_t* p, u32x4 v) {
-  if constexpr ((POL & kNtStore) != 0) __builtin_nontemporal_store(v, reinterpret_cast<u32x4u*>(p));
-  else *reinterpret_cast<u32x4u*>(p) = v;
-}
-
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
 
 // Selector bytes for the three pieces of every byte of a dword.
 struct Sel {
@@ -76,12 +50,6 @@ __device__ __forceinline__ void prep(const u32x4& x, Sel& s) {
     s.s1[q] = (w[q] >> 3) & 0x07070707u;
     s.s2[q] = (w[q] >> 6) & 0x03030303u;
   }
-}
-
-// GF(2^8) product of four bytes with the table's constant.
-__device__ __forceinline__ uint32_t gmul(uint32_t s0, uint32_t s1, uint32_t s2, const Tab& t) {
-  return xor3(__builtin_amdgcn_perm(t.t0hi, t.t0lo, s0), __builtin_amdgcn_perm(t.t1hi, t.t1lo, s1),
-              __builtin_amdgcn_perm(t.t2, t.t2, s2));
 }
 
 __device__ __forceinline__ void mac(u32x4& acc, const Sel& s, const Tab& t) {
@@ -121,23 +89,6 @@ __device__ __forceinline__ void xor2_into(u32x4& acc, const u32x4& x, const u32x
 
 __device__ __forceinline__ uint8_t gmul_byte(uint32_t x, const Tab& t) {
   return static_cast<uint8_t>(gmul(x & 7u, (x >> 3) & 7u, (x >> 6) & 3u, t));
-}
-
-// XCD-aware order of the workgroups' tiles.  Workgroups are dealt round-robin to the 8
-// XCDs (b and b + 8 share one; MI355X_MICROARCH.md "Workgroup dispatch"), so mapping
-// b -> (b % 8) * (n / 8) + b / 8 hands every XCD one contiguous eighth of the batch
-// instead of every eighth tile.  Placement only changes speed, never results (any
-// bijection of tiles is correct).  Measured +4..8% on encode (tools/probe_encode.hip).
-__device__ __forceinline__ uint32_t xcd_tile(uint32_t b, uint32_t n) {
-  const uint32_t per = n >> 3;
-  return b < (per << 3) ? (b & 7u) * per + (b >> 3) : b;
-}
-
-// Tile of a decode workgroup by the launch's `swz`: bit 0 the XCD-aware order (xcd_tile),
-// bit 1 the groups from last to first.
-__device__ __forceinline__ uint32_t decode_block(uint32_t swz) {
-  const uint32_t b = (swz & 2u) ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
-  return (swz & 1u) ? xcd_tile(b, gridDim.x) : b;
 }
 
 // Byte offset of 16-byte column `col` inside a packet of P >= 16 bytes: the last column
@@ -472,34 +423,6 @@ __device__ __forceinline__ void for_row_count(uint32_t n, F& f) {
 struct RankMeta {
   uint64_t base[4], stride[4], count_r[4];
 };
-
-__device__ __forceinline__ uint32_t rec_byte(const uint32_t* __restrict__ w, uint32_t i) {
-  return (w[i >> 2] >> (8u * (i & 3u))) & 0xFFu;
-}
-
-// NW-dword (NW = 4: 16 B, NW = 1: 4 B) load/store of one lane's piece.
-template <int NW, int POL>
-__device__ __forceinline__ void ldw(const uint8_t* p, uint32_t (&v)[NW]) {
-  if constexpr (NW == 4) {
-    const u32x4 t = ld16<POL>(p);
-    v[0] = t.x;
-    v[1] = t.y;
-    v[2] = t.z;
-    v[3] = t.w;
-  } else {
-    v[0] = *reinterpret_cast<const u32u*>(p);
-  }
-}
-
-template <int NW, int POL>
-__device__ __forceinline__ void stw(uint8_t* p, const uint32_t (&v)[NW]) {
-  if constexpr (NW == 4) {
-    st16<POL>(p, u32x4{v[0], v[1], v[2], v[3]});
-  } else {
-    if constexpr ((POL & kNtStore) != 0) __builtin_nontemporal_store(v[0], reinterpret_cast<u32u*>(p));
-    else *reinterpret_cast<u32u*>(p) = v[0];
-  }
-}
 
 // Rebuild rows [m0, m0 + MAXE) of one group's record at byte offset `off` of every
 // packet, NW dwords per lane.  The record (survivors, tables) is wave-uniform: SGPRs.
@@ -2199,55 +2122,6 @@ __global__ __launch_bounds__(kServerThreads) void legacy_server(ServerSlot* __re
     }
     if (last) sys_store_release(&ctl->exited, gen);
   }
-}
-
-constexpr uint32_t kMaxThreadsPerLaunch = 1u << 30;
-// Wave-per-group decode launches: 256-thread workgroups, so at most 2^22 of them keep the
-// grid's work-item count (blocks * 256) inside 32 bits with room to spare.
-constexpr uint64_t kMaxWaveBlocks = kMaxThreadsPerLaunch / 256u;
-// Blocks per wave-per-group decode launch: kMaxWaveBlocks (the test library's
-// TestKnob::kMaxWaveBlocks forces the chunked launches, which otherwise start only past 16.7M
-// groups).
-uint64_t max_wave_blocks() {
-  const long n = test_knob(TestKnob::kMaxWaveBlocks, 0);
-  return n > 0 && static_cast<uint64_t>(n) < kMaxWaveBlocks ? static_cast<uint64_t>(n) : kMaxWaveBlocks;
-}
-// Work items per launch of the kernels that map one item to a lane: kMaxThreadsPerLaunch (the
-// test library's TestKnob::kMaxLaunchThreads lowers it, so the chunk loops below, which otherwise
-// start only past 2^30 items, run at a few thousand).
-uint32_t max_launch_threads() {
-  const long n = test_knob(TestKnob::kMaxLaunchThreads, 0);
-  return n > 0 && static_cast<uint64_t>(n) < kMaxThreadsPerLaunch ? static_cast<uint32_t>(n) : kMaxThreadsPerLaunch;
-}
-// Groups per launch when each takes `per_group` work items (at least one group).
-uint64_t groups_per_launch(uint32_t per_group) {
-  const uint64_t n = max_launch_threads() / (per_group ? per_group : 1u);
-  return n ? n : 1;
-}
-
-inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + 255) / 256); }
-
-// The launch trace's record (fec_knobs.hpp; trace_launch() is empty in the product library).
-LaunchRecord launch_record(LaunchForm form, uint64_t grid, uint32_t block, uint64_t first_item, uint64_t items) {
-  LaunchRecord t{};
-  t.form = static_cast<int64_t>(form);
-  t.grid = static_cast<int64_t>(grid);
-  t.block = block;
-  t.first_item = static_cast<int64_t>(first_item);
-  t.items = static_cast<int64_t>(items);
-  return t;
-}
-
-// Walks `n` items in pieces of at most `per`: launch(first, count) traces and launches one
-// piece; stops at the first launch error.
-template <typename F>
-hipError_t for_chunks(uint64_t n, uint64_t per, F launch) {
-  for (uint64_t i0 = 0; i0 < n; i0 += per) {
-    launch(i0, n - i0 < per ? n - i0 : per);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
 }
 
 }  // namespace

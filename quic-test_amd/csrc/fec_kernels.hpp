@@ -37,6 +37,8 @@ constexpr int kDecodeWaveXcdSwizzle = 1;
 
 hipError_t launch_encode(const EncodeLaunch& a, hipStream_t s);
 hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s);
+// Recover from an address table (fec_gather.hip): classify_gather, then gather_form's recover_gather.
+hipError_t launch_recover_gather(const GatherLaunch& a, hipStream_t s);
 // Packed recover rows: row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.

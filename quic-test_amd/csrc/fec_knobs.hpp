@@ -76,6 +76,12 @@ enum class LaunchForm : int64_t {
   kDecodeV16 = 16,  // probe builds only
   kRunsRezero = 17,  // no kernel: recover_runs' workspace zeroed again because its epochs wrapped
 };
+// The address-table kernels (fec_gather.hip), numbered on from LaunchForm in a list of their own,
+// as their forms are (fec_forms.hpp QFEC_GATHER_FORMS); named by quicfec.GATHER_LAUNCH_FORMS.
+enum class GatherLaunchForm : int64_t {
+  kClassifyGather = 18,
+  kRecoverGather = 19,
+};
 
 // One launch: 16 words, -1 where a field does not apply to the form.
 struct LaunchRecord {
@@ -94,7 +100,7 @@ struct LaunchRecord {
   int64_t block = 0;     // work items per workgroup
   int64_t first_item = 0;  // first group (fill / copy: first 16-B word or byte) of this launch
   int64_t items = 0;     // groups (fill / copy: words or bytes) of this launch
-  int64_t aux = -1;      // encode_v16: first parity row; decodes: first rebuilt row of the pass;
+  int64_t aux = -1;      // encode_v16: first parity row; decodes, recover_gather: first rebuilt row of the pass;
                          // encode_bits: W; recover_runs: run-image bytes; fill / copy: bytes per
                          // work item
 };

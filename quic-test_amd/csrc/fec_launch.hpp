@@ -1,0 +1,66 @@
+// fec_launch.hpp — what the host launchers of the kernel translation units (fec_kernels.hip,
+// fec_gather.hip) share: the per-launch limits with their test switches, the chunk walk and the
+// launch trace's record.  Host code only.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "fec_knobs.hpp"
+
+namespace qfec {
+
+constexpr uint32_t kMaxThreadsPerLaunch = 1u << 30;
+// Wave-per-group decode launches: 256-thread workgroups, so at most 2^22 of them keep the
+// grid's work-item count (blocks * 256) inside 32 bits with room to spare.
+constexpr uint64_t kMaxWaveBlocks = kMaxThreadsPerLaunch / 256u;
+// Blocks per wave-per-group decode launch: kMaxWaveBlocks (the test library's
+// TestKnob::kMaxWaveBlocks forces the chunked launches, which otherwise start only past 16.7M
+// groups).
+inline uint64_t max_wave_blocks() {
+  const long n = test_knob(TestKnob::kMaxWaveBlocks, 0);
+  return n > 0 && static_cast<uint64_t>(n) < kMaxWaveBlocks ? static_cast<uint64_t>(n) : kMaxWaveBlocks;
+}
+// Work items per launch of the kernels that map one item to a lane: kMaxThreadsPerLaunch (the
+// test library's TestKnob::kMaxLaunchThreads lowers it, so the chunk loops, which otherwise
+// start only past 2^30 items, run at a few thousand).
+inline uint32_t max_launch_threads() {
+  const long n = test_knob(TestKnob::kMaxLaunchThreads, 0);
+  return n > 0 && static_cast<uint64_t>(n) < kMaxThreadsPerLaunch ? static_cast<uint32_t>(n) : kMaxThreadsPerLaunch;
+}
+// Groups per launch when each takes `per_group` work items (at least one group).
+inline uint64_t groups_per_launch(uint32_t per_group) {
+  const uint64_t n = max_launch_threads() / (per_group ? per_group : 1u);
+  return n ? n : 1;
+}
+
+inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + 255) / 256); }
+
+// The launch trace's record (fec_knobs.hpp; trace_launch() is empty in the product library).
+inline LaunchRecord launch_record(int64_t form, uint64_t grid, uint32_t block, uint64_t first_item, uint64_t items) {
+  LaunchRecord t{};
+  t.form = form;
+  t.grid = static_cast<int64_t>(grid);
+  t.block = block;
+  t.first_item = static_cast<int64_t>(first_item);
+  t.items = static_cast<int64_t>(items);
+  return t;
+}
+inline LaunchRecord launch_record(LaunchForm form, uint64_t grid, uint32_t block, uint64_t first_item, uint64_t items) {
+  return launch_record(static_cast<int64_t>(form), grid, block, first_item, items);
+}
+
+// Walks `n` items in pieces of at most `per`: launch(first, count) traces and launches one
+// piece; stops at the first launch error.
+template <typename F>
+hipError_t for_chunks(uint64_t n, uint64_t per, F launch) {
+  for (uint64_t i0 = 0; i0 < n; i0 += per) {
+    launch(i0, n - i0 < per ? n - i0 : per);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace qfec

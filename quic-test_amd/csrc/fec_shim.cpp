@@ -1653,6 +1653,112 @@ QFEC_EXPORT int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_da
                                                              d_status, stream));
 }
 
+// ---- address-table calls: shards / packets wherever they are in device memory ----
+namespace {
+
+// What both gather calls refuse before anything is launched or written; `what` names the call.
+int check_gather_shape(const char* what, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  if (k == 0 || r == 0) {
+    set_error("%s: unsupported k=%u r=%u (need k>0, r>0)", what, k, r);
+    return FEC_ERR_RANGE;
+  }
+  if (static_cast<uint64_t>(k) + r > qfec::kMaxDecodeShards) {
+    set_error("%s: k=%u r=%u: k + r exceeds %u shards per group", what, k, r, qfec::kMaxDecodeShards);
+    return FEC_ERR_RANGE;
+  }
+  if (P < qfec::kVecMinP) {
+    set_error("%s: packet_size %u is below %u bytes", what, P, qfec::kVecMinP);
+    return FEC_ERR_RANGE;
+  }
+  if (G == 0) {
+    set_error("%s: num_groups is 0", what);
+    return FEC_ERR_RANGE;
+  }
+  if (G >= (1ull << 32)) {
+    set_error("%s: %llu groups exceed 32-bit group indices", what, static_cast<unsigned long long>(G));
+    return FEC_ERR_RANGE;
+  }
+  return FEC_OK;
+}
+
+}  // namespace
+
+static int fec_recover_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
+                                          uint32_t r, uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
+                                          uint64_t* d_masks_out, void* stream) {
+  if (!ctx || !d_shard_addrs || !d_rebuilt) {
+    set_error("gather recover: %s is NULL", !ctx ? "the context" : !d_shard_addrs ? "d_shard_addrs" : "d_rebuilt");
+    return FEC_ERR_NULL;
+  }
+  int rc = check_gather_shape("gather recover", G, k, r, P);
+  if (rc != FEC_OK) return rc;
+  // the sparse plan reads masks back on the host; judged before a plan (and its codebook) is built
+  qfec::CodebookLayout layout;
+  if (!qfec::codebook_layout(k, r, kCodebookCap, layout)) {
+    set_error("gather recover: the codebook of k=%u r=%u exceeds the %llu-byte cap (sparse-plan shape: use "
+              "fec_recover_batch_rs_dev)", k, r, static_cast<unsigned long long>(kCodebookCap));
+    return FEC_ERR_RANGE;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard dg(ctx->device);
+  if (!dg.ok) return FEC_ERR_NODEV;
+  DecodePlan* plan = nullptr;
+  rc = get_decode_plan(ctx, k, r, &plan);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = pick_stream(ctx, stream);
+  qfec::GatherLaunch a{};
+  a.addrs = d_shard_addrs;
+  a.groups = G;
+  a.k = k;
+  a.r = r;
+  a.P = P;
+  a.out = d_rebuilt;
+  a.status = d_status;
+  a.masks_out = d_masks_out;
+  a.codebook = plan->codebook.as<uint8_t>();
+  a.binom = ctx->d_binom.as<uint64_t>();
+  for (uint32_t e = 1; e <= 32; ++e) {
+    a.meta.base[e] = plan->layout.level_base[e];
+    a.meta.stride[e] = plan->layout.level_stride[e];
+    a.meta.count_r[e] = qfec::binom().c[r][e];
+  }
+  // record offsets: the caller stream's workspace, shared in stream order with the other decodes
+  void* ws = nullptr;
+  QFEC_HIP(stream_workspace(ctx, s, G * sizeof(uint32_t), &ws));
+  a.rec_off = static_cast<uint32_t*>(ws);
+  QFEC_HIP(qfec::launch_recover_gather(a, s));
+  return FEC_OK;
+}
+
+QFEC_EXPORT int fec_recover_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
+                                          uint32_t r, uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
+                                          uint64_t* d_masks_out, void* stream) {
+  g_last_error.clear();
+  return record_ctx_error(ctx, fec_recover_gather_rs_dev_impl(ctx, d_shard_addrs, G, k, r, P, d_rebuilt, d_status,
+                                                              d_masks_out, stream));
+}
+
+static int fec_encode_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs, uint64_t G, uint32_t k,
+                                         uint32_t r, uint32_t P, uint8_t* d_parity, void* stream) {
+  if (!ctx || !d_packet_addrs || !d_parity) {
+    set_error("gather encode: %s is NULL", !ctx ? "the context" : !d_packet_addrs ? "d_packet_addrs" : "d_parity");
+    return FEC_ERR_NULL;
+  }
+  int rc = check_gather_shape("gather encode", G, k, r, P);
+  if (rc != FEC_OK) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard dg(ctx->device);
+  if (!dg.ok) return FEC_ERR_NODEV;
+  return encode_dev_locked(ctx, nullptr, d_packet_addrs, qfec::OffsetKind::kAddr, G, k, r, P, d_parity,
+                           pick_stream(ctx, stream));
+}
+
+QFEC_EXPORT int fec_encode_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs, uint64_t G, uint32_t k,
+                                         uint32_t r, uint32_t P, uint8_t* d_parity, void* stream) {
+  g_last_error.clear();
+  return record_ctx_error(ctx, fec_encode_gather_rs_dev_impl(ctx, d_packet_addrs, G, k, r, P, d_parity, stream));
+}
+
 static int fec_decode_prepare_impl(FECEncoderCtx* ctx, uint32_t k, uint32_t r, uint64_t* bytes_out) {
   if (!ctx) return FEC_ERR_NULL;
   int rc = check_shape(1, k, r, 1, true);

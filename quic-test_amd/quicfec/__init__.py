@@ -54,6 +54,7 @@ HIP_SYMBOLS = (
     "fec_batcher_new_decoder", "fec_batcher_submit_shards", "fec_batcher_wait_rebuilt",
     "fec_batcher_new_multi", "fec_batcher_new_decoder_multi", "fec_batcher_devices",
     "fec_recover_batch_rs_dev_packed", "fec_coalesce_stats", "fec_coalesce_stats_sized",
+    "fec_recover_gather_rs_dev", "fec_encode_gather_rs_dev",
 )
 
 
@@ -146,6 +147,8 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
         "fec_coalesce_stats_sized": (_int, [_vp, _sz, _int]),
         "fec_recover_batch_rs_dev_packed": (_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _u32, _u32, _u32, _vp, _vp,
                                                    _vp, _vp, _vp]),
+        "fec_recover_gather_rs_dev": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+        "fec_encode_gather_rs_dev": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -303,6 +306,24 @@ class Context:
                                                       _ptr(d_total) if d_total is not None else None,
                                                       _ptr(d_status) if d_status is not None else None, stream)
         _check(rc, "fec_recover_batch_rs_dev_packed", self.lib)
+
+    def recover_gather_dev(self, d_shard_addrs, num_groups: int, k: int, r: int, packet_size: int, d_rebuilt,
+                           d_status=None, d_masks_out=None, stream: Optional[int] = None) -> None:
+        """recover_dev from shards wherever they are: d_shard_addrs holds num_groups*(k+r) absolute
+        device addresses (u64; data shards, then parity rows; 0 = lost).  d_masks_out (nullable): the
+        erasure mask derived for each group."""
+        rc = self.lib.fec_recover_gather_rs_dev(self.handle, _ptr(d_shard_addrs) if d_shard_addrs is not None else None,
+                                                num_groups, k, r, packet_size, _ptr(d_rebuilt),
+                                                _ptr(d_status) if d_status is not None else None,
+                                                _ptr(d_masks_out) if d_masks_out is not None else None, stream)
+        _check(rc, "fec_recover_gather_rs_dev", self.lib)
+
+    def encode_gather_dev(self, d_packet_addrs, num_groups: int, k: int, r: int, packet_size: int, d_parity,
+                          stream: Optional[int] = None) -> None:
+        """encode_dev from packets wherever they are: num_groups*k absolute device addresses (u64)."""
+        rc = self.lib.fec_encode_gather_rs_dev(self.handle, _ptr(d_packet_addrs) if d_packet_addrs is not None else None,
+                                               num_groups, k, r, packet_size, _ptr(d_parity), stream)
+        _check(rc, "fec_encode_gather_rs_dev", self.lib)
 
     def decode_prepare(self, k: int, r: int) -> int:
         n = ctypes.c_uint64(0)
@@ -541,6 +562,8 @@ LAUNCH_FORMS = {1: "encode_v16", 2: "encode_bits", 3: "encode_bytes", 4: "classi
                 6: "decode_tiled", 7: "decode_wave", 8: "decode_bytes", 9: "rows_block_sums", 10: "rows_scan_blocks",
                 11: "rows_write", 12: "recover_runs", 13: "fill", 14: "copy", 15: "legacy_server", 16: "decode_v16",
                 17: "runs_rezero"}     # no kernel: recover_runs' workspace re-zeroed at an epoch wrap (items = bytes)
+# the address-table kernels (csrc/fec_gather.hip; fec_knobs.hpp GatherLaunchForm), a list of their own
+GATHER_LAUNCH_FORMS = {18: "classify_gather", 19: "recover_gather"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -567,6 +590,6 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
     out = []
     for row in buf[:seen]:
         rec = dict(zip(LAUNCH_FIELDS, (int(x) for x in row)))
-        rec["form"] = LAUNCH_FORMS.get(rec["form"], rec["form"])
+        rec["form"] = LAUNCH_FORMS.get(rec["form"], GATHER_LAUNCH_FORMS.get(rec["form"], rec["form"]))
         out.append(rec)
     return out
