@@ -1,15 +1,25 @@
-// fec_device.hpp — device helpers shared by the kernel translation units (fec_kernels.hip,
-// fec_gather.hip): the coefficient table entry, byte-aligned packet loads and stores under a
-// memory policy, the GF(2^8) product of a dword, record bytes and the workgroup order.
-// Everything is internal to its translation unit (unnamed namespace), as it was when
-// fec_kernels.hip was the only one.
+// fec_device.hpp — the device code shared by the kernel translation units (fec_kernels.hip,
+// fec_gather.hip).  First the small pieces: the coefficient table entry, byte-aligned packet loads
+// and stores under a memory policy, the GF(2^8) product of a dword, the selector split of a
+// dword (SelN / sel_split), record bytes and the workgroup order.  Then the record-addressed
+// decode, stated once:
+//  * classify_mask: erasure mask -> codebook record and status (the classify rule);
+//  * RecHead / rec_head: a record's header (row count, XOR flag, coefficient tables);
+//  * decode_piece: the rebuild of one lane's piece of every lost row.  The survivors' bases come
+//    from the record and the group's contiguous data / parity (RecordBases, the default), or
+//    from a caller's functor (the address-table recover);
+//  * decode_walk: the walk of a wave over a packet, piece by piece.
+// Everything is internal to its translation unit (unnamed namespace).  The helpers keep the
+// statement order of the kernels they were taken from: the kernels' instruction order follows it.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
-#include "fec_forms.hpp"  // the POL bits (kNtLoad .. kStageRows)
+#include "fec_forms.hpp"    // the POL bits (kNtLoad .. kStageRows), LevelMeta
+#include "fec_kernels.hpp"  // kRecNone, kRecBad
 
 namespace qfec {
 namespace {
@@ -90,6 +100,208 @@ __device__ __forceinline__ void stw(uint8_t* p, const uint32_t (&v)[NW]) {
   } else {
     if constexpr ((POL & kNtStore) != 0) __builtin_nontemporal_store(v[0], reinterpret_cast<u32u*>(p));
     else *reinterpret_cast<u32u*>(p) = v[0];
+  }
+}
+
+// Selector bytes for the three pieces of every byte of NW dwords.
+template <int NW>
+struct SelN {
+  uint32_t s0[NW], s1[NW], s2[NW];
+};
+
+template <int NW>
+__device__ __forceinline__ void sel_split(const uint32_t (&v)[NW], SelN<NW>& s) {
+#pragma unroll
+  for (int q = 0; q < NW; ++q) {
+    s.s0[q] = v[q] & 0x07070707u;
+    s.s1[q] = (v[q] >> 3) & 0x07070707u;
+    s.s2[q] = (v[q] >> 6) & 0x03030303u;
+  }
+}
+
+// The classify rule: erasure mask (bit s set where shard s of the k data + r parity shards is
+// lost) -> codebook record (in 32-B units) and status.  Nothing lost: kRecNone.  More data
+// shards lost than parity rows alive: kRecBad, status 1.  Else the record of the colex ranks of
+// the erased data set and of the e lowest surviving parity rows (`binom`: rows of 65).
+struct Classified {
+  uint32_t rec;
+  uint8_t status;
+};
+
+__device__ __forceinline__ Classified classify_mask(uint64_t m, uint32_t k, uint32_t r,
+                                                    const uint64_t* __restrict__ binom, const LevelMeta& meta) {
+  const uint64_t kmask = k >= 64 ? ~0ull : ((1ull << k) - 1);
+  const uint64_t rmask = r >= 64 ? ~0ull : ((1ull << r) - 1);
+  uint64_t dm = m & kmask;
+  const uint64_t pm = (k >= 64) ? 0 : ((m >> k) & rmask);
+  const uint32_t e = __popcll(dm);
+  uint32_t rec = kRecNone;
+  uint8_t st = 0;
+  if (e > 0) {
+    const uint32_t alive = r - __popcll(pm);
+    if (e > alive) {
+      rec = kRecBad;
+      st = 1;
+    } else {
+      uint64_t rank_e = 0, rank_r = 0;
+      for (uint32_t t = 0; dm; ++t) {
+        const uint32_t j = __ffsll(static_cast<unsigned long long>(dm)) - 1;
+        rank_e += binom[j * 65 + t + 1];
+        dm &= dm - 1;
+      }
+      uint64_t sp = ~pm & rmask;
+      for (uint32_t t = 0; t < e; ++t) {
+        const uint32_t i = __ffsll(static_cast<unsigned long long>(sp)) - 1;
+        rank_r += binom[i * 65 + t + 1];
+        sp &= sp - 1;
+      }
+      const uint64_t idx = rank_e * meta.count_r[e] + rank_r;
+      rec = static_cast<uint32_t>((meta.base[e] + idx * meta.stride[e]) >> 5);
+    }
+  }
+  return {rec, st};
+}
+
+// A record's header (gf256.hpp build_record): survivor ids from byte 0, erased ids from byte 64,
+// e and the XOR flag in word 24, the coefficient tables (row m, survivor s at tabs[m * k + s])
+// from byte 128.
+struct RecHead {
+  const uint32_t* rw;  // the record as words
+  // rows to rebuild
+  __device__ uint32_t e() const { return rw[24] & 0xFFu; }
+  // one data shard lost and parity row 0 alive: the plain XOR
+  __device__ bool xor_only() const { return ((rw[24] >> 8) & 0xFFu) != 0; }
+  __device__ const Tab* tabs() const { return reinterpret_cast<const Tab*>(reinterpret_cast<const uint8_t*>(rw) + 128); }
+};
+
+__device__ __forceinline__ RecHead rec_head(const uint8_t* recp) { return {reinterpret_cast<const uint32_t*>(recp)}; }
+
+// `rec` as classify_mask gives it (< kRecBad).
+__device__ __forceinline__ RecHead rec_head(const uint8_t* codebook, uint32_t rec) {
+  return rec_head(codebook + static_cast<uint64_t>(rec) * 32u);
+}
+
+// decode_piece's default address mode: survivor s is shard rec_byte(rw, s) of the group's
+// contiguous data (dg) or parity (pg).  Any other SRC is a functor s -> base of survivor s.
+struct RecordBases {};
+
+// Rebuild rows [m0, m0 + MAXE) of one group's record at byte offset `off` of every
+// packet, NW dwords per lane.  The record (survivors, tables) is wave-uniform: SGPRs.
+template <int K, int MAXE, int POL, int NW, typename SRC = RecordBases>
+__device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, const Tab* __restrict__ tabs,
+                                             const uint8_t* __restrict__ dg, const uint8_t* __restrict__ pg,
+                                             uint8_t* __restrict__ og, uint32_t k, uint32_t P, uint32_t off,
+                                             uint32_t e, uint32_t m0, bool xor_only, SRC src = SRC{}) {
+  auto src_of = [&](uint32_t s) -> const uint8_t* {
+    if constexpr (std::is_same_v<SRC, RecordBases>) {
+      const uint32_t sid = rec_byte(rw, s);
+      return sid < k ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - k) * static_cast<uint64_t>(P);
+    } else {
+      return src(s);
+    }
+  };
+  // Runtime k: survivors in batches of kBatch loads in flight (slots past k re-load
+  // survivor 0, a valid address, and are not used).
+  constexpr uint32_t kBatch = 8;
+  if (xor_only) {  // single data loss rebuilt from parity row 0: the reference XOR
+    uint32_t acc[NW] = {};
+    if constexpr (K > 0 && !std::is_same_v<SRC, RecordBases>) {
+      // functor bases, compile-time k: exactly K loads, all in flight
+      uint32_t x[K][NW];
+#pragma unroll
+      for (int s = 0; s < K; ++s) ldw<NW, POL>(src(s) + off, x[s]);
+#pragma unroll
+      for (int s = 0; s < K; ++s)
+#pragma unroll
+        for (int q = 0; q < NW; ++q) acc[q] ^= x[s][q];
+    } else {
+      for (uint32_t s0 = 0; s0 < k; s0 += kBatch) {
+        uint32_t v[kBatch][NW];
+#pragma unroll
+        for (uint32_t b = 0; b < kBatch; ++b) ldw<NW, POL>(src_of(s0 + b < k ? s0 + b : 0) + off, v[b]);
+#pragma unroll
+        for (uint32_t b = 0; b < kBatch; ++b)
+          if (s0 + b < k)
+#pragma unroll
+            for (int q = 0; q < NW; ++q) acc[q] ^= v[b][q];
+      }
+    }
+    stw<NW, POL>(og + ((POL & kCompactOut) != 0 ? 0u : rec_byte(rw, 64)) * static_cast<uint64_t>(P) + off, acc);
+    return;
+  }
+  uint32_t acc[MAXE][NW];
+#pragma unroll
+  for (int m = 0; m < MAXE; ++m)
+#pragma unroll
+    for (int q = 0; q < NW; ++q) acc[m][q] = 0;
+  auto consume = [&](const uint32_t (&v)[NW], uint32_t s, uint32_t kk) {
+    SelN<NW> sel;
+    sel_split(v, sel);
+#pragma unroll
+    for (int m = 0; m < MAXE; ++m) {
+      if (m0 + m < e) {
+        const Tab& t = tabs[(m0 + m) * kk + s];
+        if constexpr ((POL & kNoCoefBranch) != 0) {
+#pragma unroll
+          for (int q = 0; q < NW; ++q) acc[m][q] ^= gmul(sel.s0[q], sel.s1[q], sel.s2[q], t);
+        } else if (t.coef == 1u) {
+#pragma unroll
+          for (int q = 0; q < NW; ++q) acc[m][q] ^= v[q];
+        } else if (t.coef != 0u) {
+#pragma unroll
+          for (int q = 0; q < NW; ++q) acc[m][q] ^= gmul(sel.s0[q], sel.s1[q], sel.s2[q], t);
+        }
+      }
+    }
+  };
+  if constexpr (K > 0) {
+    uint32_t x[K][NW];
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      if constexpr (std::is_same_v<SRC, RecordBases>) {
+        const uint32_t sid = rec_byte(rw, s);
+        const uint8_t* sp = sid < K ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - K) * static_cast<uint64_t>(P);
+        ldw<NW, POL>(sp + off, x[s]);
+      } else {
+        ldw<NW, POL>(src(s) + off, x[s]);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < K; ++s) consume(x[s], s, K);
+  } else {
+    for (uint32_t s0 = 0; s0 < k; s0 += kBatch) {
+      uint32_t v[kBatch][NW];
+#pragma unroll
+      for (uint32_t b = 0; b < kBatch; ++b) ldw<NW, POL>(src_of(s0 + b < k ? s0 + b : 0) + off, v[b]);
+#pragma unroll
+      for (uint32_t b = 0; b < kBatch; ++b)
+        if (s0 + b < k) consume(v[b], s0 + b, k);
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < MAXE; ++m) {
+    if (m0 + m < e) {
+      // in place: at the erased shard; compact (kCompactOut): row m0 + m of the group's run
+      const uint32_t eid = (POL & kCompactOut) != 0 ? m0 + m : rec_byte(rw, 64 + m0 + m);
+      stw<NW, POL>(og + eid * static_cast<uint64_t>(P) + off, acc[m]);
+    }
+  }
+}
+
+// One wave's walk over a group's packets: whole 1 KiB passes of 16 B per lane, then the
+// remainder (< 1 KiB) in 256-B passes of 4 B per lane, tail pieces past the packet end shifted
+// back to [P - 4, P) (a neighbour's bytes, same values), so any P >= 4 works and no lane
+// branches on the packet end.
+template <int K, int MAXE, int POL, typename SRC = RecordBases>
+__device__ __forceinline__ void decode_walk(const uint32_t* rw, const Tab* tabs, const uint8_t* dg, const uint8_t* pg,
+                                            uint8_t* og, uint32_t k, uint32_t P, uint32_t lane, uint32_t e,
+                                            uint32_t m0, bool xor_only, SRC src = SRC{}) {
+  const uint32_t main_end = P & ~1023u;
+  for (uint32_t base = 0; base < main_end; base += 1024u)
+    decode_piece<K, MAXE, POL, 4>(rw, tabs, dg, pg, og, k, P, base + lane * 16u, e, m0, xor_only, src);
+  for (uint32_t base = main_end; base < P; base += 256u) {
+    const uint32_t off = base + lane * 4u;
+    decode_piece<K, MAXE, POL, 1>(rw, tabs, dg, pg, og, k, P, off + 4u <= P ? off : P - 4u, e, m0, xor_only, src);
   }
 }
 

@@ -4,14 +4,15 @@
 // and erasure masks.
 //
 //  * classify_gather: forms each group's erasure mask from its table entries (bit s set where
-//    entry s is 0) and from it the status byte and the codebook record, exactly as `classify`
-//    (fec_kernels.hip) does from a given mask.
+//    entry s is 0); the status byte and the codebook record come from classify_mask, the rule
+//    `classify` (fec_kernels.hip) applies to a given mask.
 //  * recover_gather<K, MAXE, POL>: one wave per group, record-addressed like decode_wave.  The
 //    base address of the record's survivor s is the group's table entry of that shard id, fetched
-//    once per group (compile-time k: scalar loads into SGPRs; runtime k: a per-wave LDS slice);
-//    the packet is then walked as decode_wave walks it -- whole 1 KiB passes of 16 B per lane,
-//    the remainder in 256-B passes of 4 B per lane, tail pieces shifted back to end at P -- and the
-//    rebuilt rows go to the compact slot layout, out + (g * r + m) * P.
+//    once per group (compile-time k: scalar loads into SGPRs; runtime k: a per-wave LDS slice)
+//    and handed to decode_walk as its survivor functor; the rebuilt rows go to the compact slot
+//    layout, out + (g * r + m) * P (kCompactOut).
+// The rule, the record header, the piece rebuild and the walk are fec_device.hpp's; this file
+// holds only what the address table adds.
 //
 // Shards may have any byte alignment (unaligned 16-B / 4-B global access, as in fec_kernels.hip)
 // and P >= 16.  A lost shard's entry and a parity row the decode rule does not use are never
@@ -30,7 +31,7 @@ namespace {
 
 // Workgroup of 256 lanes = 256 consecutive groups.  The groups' table entries are one
 // contiguous run, read by consecutive lanes; a zero entry sets its bit in the group's mask in
-// LDS.  Lane t then classifies group t like `classify`.
+// LDS.  Lane t then classifies group t (classify_mask).
 __global__ __launch_bounds__(256) void classify_gather(const uint64_t* __restrict__ addrs, uint64_t groups,
                                                        uint32_t k, uint32_t r,
                                                        const uint64_t* __restrict__ binom, LevelMeta meta,
@@ -52,38 +53,9 @@ __global__ __launch_bounds__(256) void classify_gather(const uint64_t* __restric
   if (threadIdx.x >= gn) return;
   const uint64_t g = g0 + threadIdx.x;
   const uint64_t m = lost[threadIdx.x];
-  const uint64_t kmask = (1ull << k) - 1;  // k + r <= 64 and r >= 1: k < 64
-  const uint64_t rmask = (1ull << r) - 1;
-  uint64_t dm = m & kmask;
-  const uint64_t pm = (m >> k) & rmask;
-  const uint32_t e = __popcll(dm);
-  uint32_t rec = kRecNone;
-  uint8_t st = 0;
-  if (e > 0) {
-    const uint32_t alive = r - __popcll(pm);
-    if (e > alive) {
-      rec = kRecBad;
-      st = 1;
-    } else {
-      // colex ranks of the erased data set and of the e lowest surviving parity rows
-      uint64_t rank_e = 0, rank_r = 0;
-      for (uint32_t t = 0; dm; ++t) {
-        const uint32_t j = __ffsll(static_cast<unsigned long long>(dm)) - 1;
-        rank_e += binom[j * 65 + t + 1];
-        dm &= dm - 1;
-      }
-      uint64_t sp = ~pm & rmask;
-      for (uint32_t t = 0; t < e; ++t) {
-        const uint32_t i = __ffsll(static_cast<unsigned long long>(sp)) - 1;
-        rank_r += binom[i * 65 + t + 1];
-        sp &= sp - 1;
-      }
-      const uint64_t idx = rank_e * meta.count_r[e] + rank_r;
-      rec = static_cast<uint32_t>((meta.base[e] + idx * meta.stride[e]) >> 5);
-    }
-  }
-  rec_off[g] = rec;
-  if (status) status[g] = st;
+  const Classified c = classify_mask(m, k, r, binom, meta);
+  rec_off[g] = c.rec;
+  if (status) status[g] = c.status;
   if (masks_out) masks_out[g] = m;
 }
 
@@ -93,108 +65,6 @@ __global__ __launch_bounds__(256) void classify_gather(const uint64_t* __restric
 __device__ __forceinline__ const uint8_t* shard_ptr(uint64_t addr) {
   typedef const __attribute__((address_space(1))) uint8_t* global_u8p;
   return (const uint8_t*)reinterpret_cast<global_u8p>(addr);
-}
-
-// Rebuild rows [m0, m0 + MAXE) of one group at byte offset `off` of every shard, NW dwords per
-// lane (decode_piece of fec_kernels.hip with the survivors' bases from src(s)).  The tables
-// are wave-uniform: SGPRs.  Rows go to the compact layout: row m at og + m * P.
-template <int K, int MAXE, int POL, int NW, typename SRC>
-__device__ __forceinline__ void gather_piece(const Tab* __restrict__ tabs, const SRC& src, uint8_t* __restrict__ og,
-                                             uint32_t k, uint32_t P, uint32_t off, uint32_t e, uint32_t m0,
-                                             bool xor_only) {
-  // Runtime k: survivors in batches of kBatch loads in flight (slots past k re-load
-  // survivor 0, a valid address, and are not used).
-  constexpr uint32_t kBatch = 8;
-  if (xor_only) {  // single data loss rebuilt from parity row 0: the reference XOR
-    uint32_t acc[NW] = {};
-    if constexpr (K > 0) {
-      uint32_t x[K][NW];
-#pragma unroll
-      for (int s = 0; s < K; ++s) ldw<NW, POL>(src(s) + off, x[s]);
-#pragma unroll
-      for (int s = 0; s < K; ++s)
-#pragma unroll
-        for (int q = 0; q < NW; ++q) acc[q] ^= x[s][q];
-    } else {
-      for (uint32_t s0 = 0; s0 < k; s0 += kBatch) {
-        uint32_t v[kBatch][NW];
-#pragma unroll
-        for (uint32_t b = 0; b < kBatch; ++b) ldw<NW, POL>(src(s0 + b < k ? s0 + b : 0) + off, v[b]);
-#pragma unroll
-        for (uint32_t b = 0; b < kBatch; ++b)
-          if (s0 + b < k)
-#pragma unroll
-            for (int q = 0; q < NW; ++q) acc[q] ^= v[b][q];
-      }
-    }
-    stw<NW, POL>(og + off, acc);
-    return;
-  }
-  uint32_t acc[MAXE][NW];
-#pragma unroll
-  for (int m = 0; m < MAXE; ++m)
-#pragma unroll
-    for (int q = 0; q < NW; ++q) acc[m][q] = 0;
-  auto consume = [&](const uint32_t (&v)[NW], uint32_t s, uint32_t kk) {
-    uint32_t s0[NW], s1[NW], s2[NW];
-#pragma unroll
-    for (int q = 0; q < NW; ++q) {
-      s0[q] = v[q] & 0x07070707u;
-      s1[q] = (v[q] >> 3) & 0x07070707u;
-      s2[q] = (v[q] >> 6) & 0x03030303u;
-    }
-#pragma unroll
-    for (int m = 0; m < MAXE; ++m) {
-      if (m0 + m < e) {
-        const Tab& t = tabs[(m0 + m) * kk + s];
-        if constexpr ((POL & kNoCoefBranch) != 0) {
-          // coefficient 0 / 1 tables are the zero / identity maps: no branch on the value
-#pragma unroll
-          for (int q = 0; q < NW; ++q) acc[m][q] ^= gmul(s0[q], s1[q], s2[q], t);
-        } else if (t.coef == 1u) {
-#pragma unroll
-          for (int q = 0; q < NW; ++q) acc[m][q] ^= v[q];
-        } else if (t.coef != 0u) {
-#pragma unroll
-          for (int q = 0; q < NW; ++q) acc[m][q] ^= gmul(s0[q], s1[q], s2[q], t);
-        }
-      }
-    }
-  };
-  if constexpr (K > 0) {
-    uint32_t x[K][NW];
-#pragma unroll
-    for (int s = 0; s < K; ++s) ldw<NW, POL>(src(s) + off, x[s]);
-#pragma unroll
-    for (int s = 0; s < K; ++s) consume(x[s], s, K);
-  } else {
-    for (uint32_t s0 = 0; s0 < k; s0 += kBatch) {
-      uint32_t v[kBatch][NW];
-#pragma unroll
-      for (uint32_t b = 0; b < kBatch; ++b) ldw<NW, POL>(src(s0 + b < k ? s0 + b : 0) + off, v[b]);
-#pragma unroll
-      for (uint32_t b = 0; b < kBatch; ++b)
-        if (s0 + b < k) consume(v[b], s0 + b, k);
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < MAXE; ++m) {
-    if (m0 + m < e) stw<NW, POL>(og + (m0 + m) * static_cast<uint64_t>(P) + off, acc[m]);
-  }
-}
-
-// The piece walk of decode_wave over one group.
-template <int K, int MAXE, int POL, typename SRC>
-__device__ __forceinline__ void gather_walk(const Tab* __restrict__ tabs, const SRC& src, uint8_t* __restrict__ og,
-                                            uint32_t k, uint32_t P, uint32_t lane, uint32_t e, uint32_t m0,
-                                            bool xor_only) {
-  const uint32_t main_end = P & ~1023u;
-  for (uint32_t base = 0; base < main_end; base += 1024u)
-    gather_piece<K, MAXE, POL, 4>(tabs, src, og, k, P, base + lane * 16u, e, m0, xor_only);
-  for (uint32_t base = main_end; base < P; base += 256u) {
-    const uint32_t off = base + lane * 4u;
-    gather_piece<K, MAXE, POL, 1>(tabs, src, og, k, P, off + 4u <= P ? off : P - 4u, e, m0, xor_only);
-  }
 }
 
 // One wave per group (4 per workgroup).  K > 0: compile-time k, one pass of MAXE = r rows, the k
@@ -213,28 +83,29 @@ __global__ __launch_bounds__(256) void recover_gather(const uint64_t* __restrict
   const uint32_t rec = __builtin_amdgcn_readfirstlane(rec_off[gw]);
   if (rec >= kRecBad) return;
   const uint32_t k = K > 0 ? static_cast<uint32_t>(K) : k_rt;
-  const uint8_t* recp = codebook + static_cast<uint64_t>(rec) * 32u;
-  const uint32_t* rw = reinterpret_cast<const uint32_t*>(recp);
-  const uint32_t e = rw[24] & 0xFFu;
-  const bool xor_only = ((rw[24] >> 8) & 0xFFu) != 0;
+  const RecHead h = rec_head(codebook, rec);
+  const uint32_t e = h.e();
+  const bool xor_only = h.xor_only();
   if (m0 >= e) return;
-  const Tab* tabs = reinterpret_cast<const Tab*>(recp + 128);
+  const Tab* tabs = h.tabs();
   const uint64_t* __restrict__ ga = addrs + gw * (k + r);
   uint8_t* og = out + gw * r * static_cast<uint64_t>(P);
+  // decode_walk with the survivors' bases from the table; rows to the compact layout
+  static_assert((POL & kCompactOut) != 0, "recover_gather writes compact rows");
   if constexpr (K > 0) {
     const uint8_t* base[K];
 #pragma unroll
-    for (int s = 0; s < K; ++s) base[s] = shard_ptr(ga[rec_byte(rw, s)]);
+    for (int s = 0; s < K; ++s) base[s] = shard_ptr(ga[rec_byte(h.rw, s)]);
     const auto src = [&base](int s) { return base[s]; };
-    gather_walk<K, MAXE, POL>(tabs, src, og, k, P, lane, e, m0, xor_only);
+    decode_walk<K, MAXE, POL>(h.rw, tabs, nullptr, nullptr, og, k, P, lane, e, m0, xor_only, src);
   } else {
     __shared__ uint64_t slices[4 * 64];
     uint64_t* slice = slices + wave * 64u;
-    if (lane < k) slice[lane] = ga[recp[lane]];  // survivor `lane` of the record
+    if (lane < k) slice[lane] = ga[reinterpret_cast<const uint8_t*>(h.rw)[lane]];  // survivor `lane` of the record
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const auto src = [slice](uint32_t s) { return shard_ptr(slice[s]); };
-    gather_walk<K, MAXE, POL>(tabs, src, og, k, P, lane, e, m0, xor_only);
+    decode_walk<K, MAXE, POL>(h.rw, tabs, nullptr, nullptr, og, k, P, lane, e, m0, xor_only, src);
   }
 }
 

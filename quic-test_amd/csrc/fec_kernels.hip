@@ -9,8 +9,11 @@
 //    into parity row 0 (the reference XOR, fec_xor_simd.cpp:411-427) and multiplies them
 //    into rows 1..R-1 with v_perm_b32 table lookups (3 per dword per coefficient, tables
 //    in SGPRs via scalar loads), then stores R dwordx4.
-//  * classify: one lane per group, erasure mask -> codebook record (rank of the erased
-//    data set and of the parity rows used), status byte.
+//  * classify: one lane per group, erasure mask -> codebook record and status byte
+//    (classify_mask, fec_device.hpp).
+//  * decode_wave<K,MAXE>: one wave per group, record-addressed; the piece rebuild
+//    (decode_piece) and the record header (RecHead) are fec_device.hpp's, shared with the
+//    address-table recover of fec_gather.hip.
 //  * decode_v16<K,MAXE>: one wave per group, so the record (survivor list + tables) is
 //    wave-uniform and lives in SGPRs; lanes walk the group's 16-byte columns.
 //  * *_bytes: packets shorter than 16 B (one lane per byte), same tables.
@@ -29,7 +32,7 @@
 
 #include "bitslice.hpp"
 #include "coef_tables.hpp"
-#include "fec_device.hpp"  // Tab, ld16 / st16, gmul, ldw / stw, decode_block
+#include "fec_device.hpp"  // Tab, ld16 / st16, gmul, ldw / stw, decode_block; classify_mask, RecHead, decode_piece
 #include "fec_kernels.hpp"
 #include "fec_knobs.hpp"
 #include "fec_launch.hpp"  // launch limits, for_chunks, launch_record
@@ -37,19 +40,12 @@
 namespace qfec {
 namespace {
 
-// Selector bytes for the three pieces of every byte of a dword.
-struct Sel {
-  uint32_t s0[4], s1[4], s2[4];
-};
+// Selector bytes of a 16-byte column (SelN / sel_split: fec_device.hpp).
+using Sel = SelN<4>;
 
 __device__ __forceinline__ void prep(const u32x4& x, Sel& s) {
   const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    s.s0[q] = w[q] & 0x07070707u;
-    s.s1[q] = (w[q] >> 3) & 0x07070707u;
-    s.s2[q] = (w[q] >> 6) & 0x03030303u;
-  }
+  sel_split(w, s);
 }
 
 __device__ __forceinline__ void mac(u32x4& acc, const Sel& s, const Tab& t) {
@@ -357,38 +353,9 @@ __global__ __launch_bounds__(256) void classify(const uint64_t* __restrict__ mas
                                                 uint8_t* __restrict__ status) {
   const uint64_t g = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
   if (g >= groups) return;
-  const uint64_t m = masks[g];
-  const uint64_t kmask = k >= 64 ? ~0ull : ((1ull << k) - 1);
-  const uint64_t rmask = r >= 64 ? ~0ull : ((1ull << r) - 1);
-  uint64_t dm = m & kmask;
-  const uint64_t pm = (k >= 64) ? 0 : ((m >> k) & rmask);
-  const uint32_t e = __popcll(dm);
-  uint32_t rec = kRecNone;
-  uint8_t st = 0;
-  if (e > 0) {
-    const uint32_t alive = r - __popcll(pm);
-    if (e > alive) {
-      rec = kRecBad;
-      st = 1;
-    } else {
-      uint64_t rank_e = 0, rank_r = 0;
-      for (uint32_t t = 0; dm; ++t) {
-        const uint32_t j = __ffsll(static_cast<unsigned long long>(dm)) - 1;
-        rank_e += binom[j * 65 + t + 1];
-        dm &= dm - 1;
-      }
-      uint64_t sp = ~pm & rmask;
-      for (uint32_t t = 0; t < e; ++t) {
-        const uint32_t i = __ffsll(static_cast<unsigned long long>(sp)) - 1;
-        rank_r += binom[i * 65 + t + 1];
-        sp &= sp - 1;
-      }
-      const uint64_t idx = rank_e * meta.count_r[e] + rank_r;
-      rec = static_cast<uint32_t>((meta.base[e] + idx * meta.stride[e]) >> 5);
-    }
-  }
-  rec_off[g] = rec;
-  if (status) status[g] = st;
+  const Classified c = classify_mask(masks[g], k, r, binom, meta);
+  rec_off[g] = c.rec;
+  if (status) status[g] = c.status;
 }
 
 // C(n, t) for t = 1..3 without the table (the mask-addressed decode ranks inline; its
@@ -423,96 +390,6 @@ __device__ __forceinline__ void for_row_count(uint32_t n, F& f) {
 struct RankMeta {
   uint64_t base[4], stride[4], count_r[4];
 };
-
-// Rebuild rows [m0, m0 + MAXE) of one group's record at byte offset `off` of every
-// packet, NW dwords per lane.  The record (survivors, tables) is wave-uniform: SGPRs.
-template <int K, int MAXE, int POL, int NW>
-__device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, const Tab* __restrict__ tabs,
-                                             const uint8_t* __restrict__ dg, const uint8_t* __restrict__ pg,
-                                             uint8_t* __restrict__ og, uint32_t k, uint32_t P, uint32_t off,
-                                             uint32_t e, uint32_t m0, bool xor_only) {
-  auto src_of = [&](uint32_t s) {
-    const uint32_t sid = rec_byte(rw, s);
-    return sid < k ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - k) * static_cast<uint64_t>(P);
-  };
-  // Runtime k: survivors in batches of kBatch loads in flight (slots past k re-load
-  // survivor 0, a valid address, and are not used).
-  constexpr uint32_t kBatch = 8;
-  if (xor_only) {  // single data loss rebuilt from parity row 0: the reference XOR
-    uint32_t acc[NW] = {};
-    for (uint32_t s0 = 0; s0 < k; s0 += kBatch) {
-      uint32_t v[kBatch][NW];
-#pragma unroll
-      for (uint32_t b = 0; b < kBatch; ++b) ldw<NW, POL>(src_of(s0 + b < k ? s0 + b : 0) + off, v[b]);
-#pragma unroll
-      for (uint32_t b = 0; b < kBatch; ++b)
-        if (s0 + b < k)
-#pragma unroll
-          for (int q = 0; q < NW; ++q) acc[q] ^= v[b][q];
-    }
-    stw<NW, POL>(og + ((POL & kCompactOut) != 0 ? 0u : rec_byte(rw, 64)) * static_cast<uint64_t>(P) + off, acc);
-    return;
-  }
-  uint32_t acc[MAXE][NW];
-#pragma unroll
-  for (int m = 0; m < MAXE; ++m)
-#pragma unroll
-    for (int q = 0; q < NW; ++q) acc[m][q] = 0;
-  auto consume = [&](const uint32_t (&v)[NW], uint32_t s, uint32_t kk) {
-    uint32_t s0[NW], s1[NW], s2[NW];
-#pragma unroll
-    for (int q = 0; q < NW; ++q) {
-      s0[q] = v[q] & 0x07070707u;
-      s1[q] = (v[q] >> 3) & 0x07070707u;
-      s2[q] = (v[q] >> 6) & 0x03030303u;
-    }
-#pragma unroll
-    for (int m = 0; m < MAXE; ++m) {
-      if (m0 + m < e) {
-        const Tab& t = tabs[(m0 + m) * kk + s];
-        if constexpr ((POL & kNoCoefBranch) != 0) {
-          // coefficient 0 / 1 tables are the zero / identity maps: no branch on the value
-#pragma unroll
-          for (int q = 0; q < NW; ++q) acc[m][q] ^= gmul(s0[q], s1[q], s2[q], t);
-        } else if (t.coef == 1u) {
-#pragma unroll
-          for (int q = 0; q < NW; ++q) acc[m][q] ^= v[q];
-        } else if (t.coef != 0u) {
-#pragma unroll
-          for (int q = 0; q < NW; ++q) acc[m][q] ^= gmul(s0[q], s1[q], s2[q], t);
-        }
-      }
-    }
-  };
-  if constexpr (K > 0) {
-    uint32_t x[K][NW];
-#pragma unroll
-    for (int s = 0; s < K; ++s) {
-      const uint32_t sid = rec_byte(rw, s);
-      const uint8_t* src = sid < K ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - K) * static_cast<uint64_t>(P);
-      ldw<NW, POL>(src + off, x[s]);
-    }
-#pragma unroll
-    for (int s = 0; s < K; ++s) consume(x[s], s, K);
-  } else {
-    for (uint32_t s0 = 0; s0 < k; s0 += kBatch) {
-      uint32_t v[kBatch][NW];
-#pragma unroll
-      for (uint32_t b = 0; b < kBatch; ++b) ldw<NW, POL>(src_of(s0 + b < k ? s0 + b : 0) + off, v[b]);
-#pragma unroll
-      for (uint32_t b = 0; b < kBatch; ++b)
-        if (s0 + b < k) consume(v[b], s0 + b, k);
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < MAXE; ++m) {
-    if (m0 + m < e) {
-      // in place: at the erased shard; compact (kCompactOut): row m0 + m of the group's run
-      const uint32_t eid = (POL & kCompactOut) != 0 ? m0 + m : rec_byte(rw, 64 + m0 + m);
-      stw<NW, POL>(og + eid * static_cast<uint64_t>(P) + off, acc[m]);
-    }
-  }
-}
 
 // decode_wave with the main (16 B/lane) and tail (4 B/lane) passes fused: each lane holds
 // NM 16-byte pieces and NT 4-byte pieces of every survivor, so every coefficient table is
@@ -574,7 +451,8 @@ __device__ __forceinline__ void fused_group(uint64_t gw, uint64_t m, uint32_t la
     rec_byte_off = static_cast<uint64_t>(rec) * 32u;
   }
   const uint8_t* recp = codebook + rec_byte_off;
-  const uint32_t* rw = reinterpret_cast<const uint32_t*>(recp);
+  const RecHead h = rec_head(recp);
+  const uint32_t* rw = h.rw;
   uint32_t e;
   bool xor_only;
   // DIRECT: survivor ids (ascending bits of `surv`) and erased ids (bits of `lost`).
@@ -591,11 +469,11 @@ __device__ __forceinline__ void fused_group(uint64_t gw, uint64_t m, uint32_t la
     }
     surv = (~lost & kmask) | (rsel << K);
   } else {
-    e = rw[24] & 0xFFu;
-    xor_only = ((rw[24] >> 8) & 0xFFu) != 0;
+    e = h.e();
+    xor_only = h.xor_only();
   }
   if (m0 >= e) return;
-  const Tab* tabs = reinterpret_cast<const Tab*>(recp + 128);
+  const Tab* tabs = h.tabs();
   const uint8_t* dg = data + gw * K * static_cast<uint64_t>(P);
   const uint8_t* pg = parity + gw * r * static_cast<uint64_t>(P);
   uint8_t* og = out + gw * K * static_cast<uint64_t>(P);
@@ -766,19 +644,14 @@ __device__ __forceinline__ void fused_group(uint64_t gw, uint64_t m, uint32_t la
         for (int q = 0; q < NW; ++q) __asm__ volatile("" : "+v"(x[s][q]));
         __builtin_amdgcn_sched_barrier(0);
         if (s + kWin < K) load(shard(sid[s + kWin]), x[s + kWin]);  // folded when unrolled
-        uint32_t s0[NW], s1[NW], s2[NW];
-#pragma unroll
-        for (int q = 0; q < NW; ++q) {
-          s0[q] = x[s][q] & 0x07070707u;
-          s1[q] = (x[s][q] >> 3) & 0x07070707u;
-          s2[q] = (x[s][q] >> 6) & 0x03030303u;
-        }
+        SelN<NW> sel;
+        sel_split(x[s], sel);
 #pragma unroll
         for (int m = 0; m < NR; ++m) {
           const Tab t = lt[m * K + s];
 #pragma unroll
           for (int q = 0; q < NW; ++q) {
-            acc[m][q] ^= gmul(s0[q], s1[q], s2[q], t);
+            acc[m][q] ^= gmul(sel.s0[q], sel.s1[q], sel.s2[q], t);
             // pin the accumulation order: reassociating the K-term XOR chains into trees
             // keeps every survivor's products live at once (spills)
             __asm__ volatile("" : "+v"(acc[m][q]));
@@ -801,6 +674,7 @@ __device__ __forceinline__ void fused_group(uint64_t gw, uint64_t m, uint32_t la
     for (int q = 0; q < NW; ++q) acc[m][q] = 0;
 #pragma unroll
   for (int s = 0; s < K; ++s) {
+    // (sel_split here moves ten decode_fused instantiations: spelled out)
     uint32_t s0[NW], s1[NW], s2[NW];
 #pragma unroll
     for (int q = 0; q < NW; ++q) {
@@ -1047,13 +921,8 @@ __device__ __forceinline__ void runs_compute(const RunMeta& mt, uint32_t (&x)[K]
     // selectors ahead of the arithmetic: 160 VGPRs, 3 waves per SIMD; see decode_fused kLdsTabs)
 #pragma unroll
     for (int q = 0; q < NW; ++q) __asm__ volatile("" : "+v"(x[s][q]));
-    uint32_t s0[NW], s1[NW], s2[NW];
-#pragma unroll
-    for (int q = 0; q < NW; ++q) {
-      s0[q] = x[s][q] & 0x07070707u;
-      s1[q] = (x[s][q] >> 3) & 0x07070707u;
-      s2[q] = (x[s][q] >> 6) & 0x03030303u;
-    }
+    SelN<NW> sel;
+    sel_split(x[s], sel);
 #pragma unroll
     for (int mm = 0; mm < R; ++mm) {
       if (static_cast<uint32_t>(mm) < mt.e) {
@@ -1063,7 +932,7 @@ __device__ __forceinline__ void runs_compute(const RunMeta& mt, uint32_t (&x)[K]
           for (int q = 0; q < NW; ++q) acc[mm][q] ^= x[s][q];
         } else if (t.coef != 0u) {
 #pragma unroll
-          for (int q = 0; q < NW; ++q) acc[mm][q] ^= gmul(s0[q], s1[q], s2[q], t);
+          for (int q = 0; q < NW; ++q) acc[mm][q] ^= gmul(sel.s0[q], sel.s1[q], sel.s2[q], t);
         }
       }
     }
@@ -1445,12 +1314,12 @@ __global__ __launch_bounds__(256) void decode_wave(uint8_t* __restrict__ data,
   const uint32_t rec = __builtin_amdgcn_readfirstlane(rec_off[gw]);
   if (rec >= kRecBad) return;
   const uint32_t k = K > 0 ? static_cast<uint32_t>(K) : k_rt;
-  const uint8_t* recp = codebook + static_cast<uint64_t>(rec) * 32u;
-  const uint32_t* rw = reinterpret_cast<const uint32_t*>(recp);
-  const uint32_t e = rw[24] & 0xFFu;
-  const bool xor_only = ((rw[24] >> 8) & 0xFFu) != 0;
+  const RecHead h = rec_head(codebook, rec);
+  const uint32_t* rw = h.rw;
+  const uint32_t e = h.e();
+  const bool xor_only = h.xor_only();
   if (m0 >= e) return;
-  const Tab* tabs = reinterpret_cast<const Tab*>(recp + 128);
+  const Tab* tabs = h.tabs();
   if constexpr ((POL & kLdsTabs) != 0) {
     if (!xor_only) {
       // rows [m0, m0 + min(e - m0, MAXE)) of the record into this wave's slice, by
@@ -1468,13 +1337,15 @@ __global__ __launch_bounds__(256) void decode_wave(uint8_t* __restrict__ data,
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      // decode_piece indexes rows from m0
+      // decode_piece (fec_device.hpp) indexes rows from m0
       tabs = reinterpret_cast<const Tab*>(slice) - static_cast<ptrdiff_t>(m0) * k;
     }
   }
   const uint8_t* dg = data + gw * k * static_cast<uint64_t>(P);
   const uint8_t* pg = parity + gw * r * static_cast<uint64_t>(P);
   uint8_t* og = out + gw * ((POL & kCompactOut) != 0 ? r : k) * static_cast<uint64_t>(P);
+  // decode_walk's two loops, spelled out: routed through the helper, the compile-time-k
+  // instantiations come out with another instruction order (same instructions)
   const uint32_t main_end = P & ~1023u;
   for (uint32_t base = 0; base < main_end; base += 1024u)
     decode_piece<K, MAXE, POL, 4>(rw, tabs, dg, pg, og, k, P, base + lane * 16u, e, m0, xor_only);
@@ -1500,12 +1371,12 @@ __global__ __launch_bounds__(256) void decode_v16(uint8_t* __restrict__ data,
   const uint32_t rec = __builtin_amdgcn_readfirstlane(rec_off[gw]);
   if (rec >= kRecBad) return;
   const uint32_t k = K > 0 ? static_cast<uint32_t>(K) : k_rt;
-  const uint8_t* recp = codebook + static_cast<uint64_t>(rec) * 32u;
-  const uint32_t* rw = reinterpret_cast<const uint32_t*>(recp);
-  const uint32_t e = rw[24] & 0xFFu;
-  const bool xor_only = ((rw[24] >> 8) & 0xFFu) != 0;
+  const RecHead h = rec_head(codebook, rec);
+  const uint32_t* rw = h.rw;
+  const uint32_t e = h.e();
+  const bool xor_only = h.xor_only();
   if (m0 >= e) return;
-  const Tab* tabs = reinterpret_cast<const Tab*>(recp + 128);
+  const Tab* tabs = h.tabs();
   uint8_t* dg = data + gw * k * static_cast<uint64_t>(P);
   const uint8_t* pg = parity + gw * r * static_cast<uint64_t>(P);
 
@@ -1597,10 +1468,10 @@ __global__ __launch_bounds__(512) void decode_tiled(const uint8_t* __restrict__ 
   const uint64_t g = gl;
   const uint32_t rec = rec_off[g];
   if (rec >= kRecBad) return;
-  const uint8_t* recp = codebook + static_cast<uint64_t>(rec) * 32u;
-  const uint32_t* rw = reinterpret_cast<const uint32_t*>(recp);
-  const uint32_t e = rw[24] & 0xFFu;
-  const Tab* tabs = reinterpret_cast<const Tab*>(recp + 128);
+  const RecHead h = rec_head(codebook, rec);  // per lane: a wave may hold two groups
+  const uint32_t* rw = h.rw;
+  const uint32_t e = h.e();
+  const Tab* tabs = h.tabs();
   const uint8_t* dg = data + g * K * static_cast<uint64_t>(P);
   const uint8_t* pg = parity + g * r * static_cast<uint64_t>(P);
   // in place: the erased shard's slot; kCompactOut: row m of the group's run (g*r + m)*P

@@ -614,6 +614,17 @@ hipError_t find_stream_ws(FECEncoderCtx* ctx, hipStream_t s, StreamWorkspace** o
   return hipSuccess;
 }
 
+// The codebook's levels e = 1..32 as the classify rule reads them (fec_device.hpp classify_mask).
+qfec::LevelMeta level_meta(const qfec::CodebookLayout& layout, uint32_t r) {
+  qfec::LevelMeta m{};
+  for (uint32_t e = 1; e <= 32; ++e) {
+    m.base[e] = layout.level_base[e];
+    m.stride[e] = layout.level_stride[e];
+    m.count_r[e] = qfec::binom().c[r][e];
+  }
+  return m;
+}
+
 int decode_dev_locked(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
                       const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
                       uint8_t* d_status, hipStream_t s, DevBuf* rec = nullptr,
@@ -632,12 +643,7 @@ int decode_dev_locked(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_pari
   a.status = d_status;
   a.codebook = plan->codebook.as<uint8_t>();
   a.binom = ctx->d_binom.as<uint64_t>();
-  std::memset(&a.meta, 0, sizeof(a.meta));
-  for (uint32_t e = 1; e <= 32; ++e) {
-    a.meta.base[e] = plan->layout.level_base[e];
-    a.meta.stride[e] = plan->layout.level_stride[e];
-    a.meta.count_r[e] = qfec::binom().c[r][e];
-  }
+  a.meta = level_meta(plan->layout, r);
   a.groups = G;
   a.k = k;
   a.r = r;
@@ -666,10 +672,7 @@ int decode_dev_locked(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_pari
     }
     a.compact_tables = true;
     a.codebook = plan->cbook.as<uint8_t>();
-    for (uint32_t e = 1; e <= 32; ++e) {
-      a.meta.base[e] = plan->clayout.level_base[e];
-      a.meta.stride[e] = plan->clayout.level_stride[e];
-    }
+    a.meta = level_meta(plan->clayout, r);
   }
   if (row_start != nullptr) {
     // refused, one recover_runs launch, or the row prefix + the mask-addressed decode_fused
@@ -1717,11 +1720,7 @@ static int fec_recover_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_
   a.masks_out = d_masks_out;
   a.codebook = plan->codebook.as<uint8_t>();
   a.binom = ctx->d_binom.as<uint64_t>();
-  for (uint32_t e = 1; e <= 32; ++e) {
-    a.meta.base[e] = plan->layout.level_base[e];
-    a.meta.stride[e] = plan->layout.level_stride[e];
-    a.meta.count_r[e] = qfec::binom().c[r][e];
-  }
+  a.meta = level_meta(plan->layout, r);
   // record offsets: the caller stream's workspace, shared in stream order with the other decodes
   void* ws = nullptr;
   QFEC_HIP(stream_workspace(ctx, s, G * sizeof(uint32_t), &ws));

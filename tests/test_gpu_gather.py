@@ -44,8 +44,11 @@ def _no_switches(monkeypatch):
 # Cases: one batch and what the oracle says about it, computed once and never modified
 # ------------------------------------------------------------------------------------------
 def _planted(k, r):
-    """Untouched, parity lost only, unrecoverable (a data shard and every parity row lost)."""
-    return [0, 1 << k, 1 | (((1 << r) - 1) << k)]
+    """Untouched, parity lost only, unrecoverable (a data shard and every parity row lost); then the
+    two single-loss rebuilds: one data shard lost with parity row 0 alive (the XOR path), and one
+    data shard lost with parity row 0 lost too (the GF path with e = 1; r = 1 has no such group
+    and gets a second XOR group)."""
+    return [0, 1 << k, 1 | (((1 << r) - 1) << k), 1 << 1, (1 << 2) | (1 << k) if r >= 2 else 1 << (k - 1)]
 
 
 def perm_masks(k, r, G, seed):
@@ -54,8 +57,19 @@ def perm_masks(k, r, G, seed):
     for g in range(G):
         for s in rng.permutation(k + r)[: rng.integers(0, r + 2)]:
             masks[g] |= np.uint64(1) << np.uint64(int(s))
-    masks[:3] = _planted(k, r)
+    planted = _planted(k, r)[:G]
+    masks[:len(planted)] = planted
     return masks
+
+
+def rebuild_kinds(masks, k, r):
+    """Per group: the number of data shards it rebuilds (0 when none lost or unrecoverable), and
+    whether parity row 0 is lost."""
+    masks = np.asarray(masks, dtype=np.uint64)
+    bits = ((masks[:, None] >> np.arange(k + r, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+    e = bits[:, :k].sum(axis=1)
+    e[e + bits[:, k:].sum(axis=1) > r] = 0
+    return e, bits[:, k]
 
 
 def iid_masks(k, r, G, loss, rng):
@@ -90,7 +104,7 @@ def make_case(oracle, k, r, P, masks, seed):
 
 @lru_cache(maxsize=None)
 def main_case(oracle, k, r, P):
-    """The G = 67 case of a shape and size: permutation masks with the three planted groups, and the
+    """The G = 67 case of a shape and size: permutation masks with the five planted groups, and the
     mix checked on the CPU before anything runs."""
     salt = k * 100000 + r * 10000 + P
     c = make_case(oracle, k, r, P, perm_masks(k, r, G_MAIN, salt), SEED + salt)
@@ -98,6 +112,12 @@ def main_case(oracle, k, r, P):
     assert (c.masks == 0).any() and (c.status != 0).any() and c.rows > 0
     assert ((c.masks != 0) & ((c.masks & kmask) == 0)).any()
     assert c.masks[0] == 0 and c.status[2] == 1 and c.status[1] == 0
+    # the single-loss XOR path, the GF path with e = 1, and more than one row (r >= 2)
+    e, row0_lost = rebuild_kinds(c.masks, k, r)
+    assert ((e == 1) & ~row0_lost).any()
+    if r >= 2:
+        assert ((e == 1) & row0_lost).any() and (e >= 2).any()
+    assert np.array_equal(e > 0, (c.status == 0) & ((c.masks & kmask) != 0))
     return c
 
 
@@ -260,7 +280,7 @@ def test_identity_table_equals_contiguous_recover(quicfec_mod, oracle_mod, torch
 def test_edge_masks(quicfec_mod, oracle_mod, torch_cuda, k, r, P, kind):
     unrec = 1 | (((1 << r) - 1) << k)
     masks = {"all_survive": [0] * G_MAIN, "all_unrecoverable": [unrec] * G_MAIN,
-             "one_group": [0b110 | (1 << k)], "three_groups": _planted(k, r)}[kind]
+             "one_group": [0b110 | (1 << k)], "three_groups": _planted(k, r)[:3]}[kind]
     c = make_case(oracle_mod, k, r, P, masks, SEED + len(masks) + k)
     if kind == "all_survive":
         assert (c.status == 0).all() and c.rows == 0
