@@ -168,6 +168,39 @@ int fec_recover_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
 int fec_encode_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs, uint64_t num_groups,
                              uint32_t k, uint32_t r, uint32_t packet_size, uint8_t* d_parity, void* stream);
 
+/* ---- address tables with a length per entry: variable-length packets, partial groups ----
+ * The two calls above with a second table, u32 in device memory and indexed exactly like the
+ * address table: entry (g, s) is the number of readable bytes at that shard's address.
+ *   - packet_size (P) is the symbol size and the row pitch of the output.  A length above P is
+ *     clamped to P.  Shard (g, s) is the bytes [0, min(len, P)) at its address followed by zeros
+ *     up to P, as the reference's decoder pads a symbol and its encoder XORs only the bytes a
+ *     packet has.
+ *   - No byte at or past address + len is ever read: a packet may be the last thing in its
+ *     allocation.  A present shard of length 0 is all zero and its address is never dereferenced.
+ *   - Recover: address 0 is still the only loss marker; the length of a lost entry is ignored.
+ *     The table carries the parity shards with their lengths too, because a repair packet on the
+ *     wire holds only its group's symbol length.
+ *   - Encode: address 0 means the packet is absent (a flush of a partial group) and counts as all
+ *     zero; a group with every packet absent gets all-zero rows.  The parity rows are written as
+ *     full P-byte rows.
+ *   - Output layout as in the fixed-length calls (rebuilt rows at (g*r + m)*P, slots m >= e and
+ *     every slot of an unrecoverable group unwritten; parity at (g*r + i)*P).  Every written row
+ *     is a full P bytes, with zeros where every contributing shard had ended.
+ *   - d_symbol_len_out (nullable, u32 per group): written for every group when given; the largest
+ *     min(len, P) over the group's present entries, 0 when none is present -- the decoder's symbol
+ *     length, and on the encode side the length of the repair payload.
+ * Refused like the fixed-length calls, with nothing launched or written; a NULL length table is
+ * FEC_ERR_NULL and the message names it.  Asynchronous on `stream`, drained by fec_encoder_free;
+ * the recover's record offsets live in the caller stream's workspace, no new per-context state. */
+int fec_recover_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
+                                  const uint32_t* d_shard_lens, uint64_t num_groups, uint32_t k, uint32_t r,
+                                  uint32_t packet_size, uint8_t* d_rebuilt, uint8_t* d_status,
+                                  uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream);
+
+int fec_encode_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
+                                 const uint32_t* d_packet_lens, uint64_t num_groups, uint32_t k, uint32_t r,
+                                 uint32_t packet_size, uint8_t* d_parity, uint32_t* d_symbol_len_out, void* stream);
+
 /* Expected share (0..1) of groups that lost data shards in this context's device-resident
  * decode calls, e.g. 1 - (1 - p)^k for iid loss p (the receiver knows its network profile;
  * satellite p = 0.01, k = 10: ~0.10).  Below 0.25 the decode checks several groups per

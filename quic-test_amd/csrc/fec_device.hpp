@@ -1,8 +1,8 @@
 // fec_device.hpp — the device code shared by the kernel translation units (fec_kernels.hip,
-// fec_gather.hip).  First the small pieces: the coefficient table entry, byte-aligned packet loads
-// and stores under a memory policy, the GF(2^8) product of a dword, the selector split of a
-// dword (SelN / sel_split), record bytes and the workgroup order.  Then the record-addressed
-// decode, stated once:
+// fec_gather.hip, fec_gather_var.hip).  First the small pieces: the coefficient table entry,
+// byte-aligned packet loads and stores under a memory policy, the GF(2^8) product of a dword, the
+// selector split of a dword (SelN / sel_split), record bytes and the workgroup order.  Then the
+// record-addressed decode, stated once:
 //  * classify_mask: erasure mask -> codebook record and status (the classify rule);
 //  * RecHead / rec_head: a record's header (row count, XOR flag, coefficient tables);
 //  * decode_piece: the rebuild of one lane's piece of every lost row.  The survivors' bases come
@@ -185,6 +185,15 @@ __device__ __forceinline__ RecHead rec_head(const uint8_t* codebook, uint32_t re
 // contiguous data (dg) or parity (pg).  Any other SRC is a functor s -> base of survivor s.
 struct RecordBases {};
 
+// A functor SRC with a member type `loads_piece` loads a lane's piece itself,
+// src.load<NW, POL>(s, off, v), instead of decode_piece loading NW dwords at src(s) + off (the
+// variable-length address-table recover, fec_gather_var.hip: the load is masked by the shard's
+// length).
+template <typename SRC, typename = void>
+struct loads_piece : std::false_type {};
+template <typename SRC>
+struct loads_piece<SRC, std::void_t<typename SRC::loads_piece>> : std::true_type {};
+
 // Rebuild rows [m0, m0 + MAXE) of one group's record at byte offset `off` of every
 // packet, NW dwords per lane.  The record (survivors, tables) is wave-uniform: SGPRs.
 template <int K, int MAXE, int POL, int NW, typename SRC = RecordBases>
@@ -196,6 +205,8 @@ __device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, co
     if constexpr (std::is_same_v<SRC, RecordBases>) {
       const uint32_t sid = rec_byte(rw, s);
       return sid < k ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - k) * static_cast<uint64_t>(P);
+    } else if constexpr (loads_piece<SRC>::value) {
+      return nullptr;  // not used: src loads the piece itself
     } else {
       return src(s);
     }
@@ -209,7 +220,10 @@ __device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, co
       // functor bases, compile-time k: exactly K loads, all in flight
       uint32_t x[K][NW];
 #pragma unroll
-      for (int s = 0; s < K; ++s) ldw<NW, POL>(src(s) + off, x[s]);
+      for (int s = 0; s < K; ++s) {
+        if constexpr (loads_piece<SRC>::value) src.template load<NW, POL>(s, off, x[s]);
+        else ldw<NW, POL>(src(s) + off, x[s]);
+      }
 #pragma unroll
       for (int s = 0; s < K; ++s)
 #pragma unroll
@@ -218,7 +232,10 @@ __device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, co
       for (uint32_t s0 = 0; s0 < k; s0 += kBatch) {
         uint32_t v[kBatch][NW];
 #pragma unroll
-        for (uint32_t b = 0; b < kBatch; ++b) ldw<NW, POL>(src_of(s0 + b < k ? s0 + b : 0) + off, v[b]);
+        for (uint32_t b = 0; b < kBatch; ++b) {
+          if constexpr (loads_piece<SRC>::value) src.template load<NW, POL>(s0 + b < k ? s0 + b : 0, off, v[b]);
+          else ldw<NW, POL>(src_of(s0 + b < k ? s0 + b : 0) + off, v[b]);
+        }
 #pragma unroll
         for (uint32_t b = 0; b < kBatch; ++b)
           if (s0 + b < k)
@@ -262,6 +279,8 @@ __device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, co
         const uint32_t sid = rec_byte(rw, s);
         const uint8_t* sp = sid < K ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - K) * static_cast<uint64_t>(P);
         ldw<NW, POL>(sp + off, x[s]);
+      } else if constexpr (loads_piece<SRC>::value) {
+        src.template load<NW, POL>(s, off, x[s]);
       } else {
         ldw<NW, POL>(src(s) + off, x[s]);
       }
@@ -272,7 +291,10 @@ __device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, co
     for (uint32_t s0 = 0; s0 < k; s0 += kBatch) {
       uint32_t v[kBatch][NW];
 #pragma unroll
-      for (uint32_t b = 0; b < kBatch; ++b) ldw<NW, POL>(src_of(s0 + b < k ? s0 + b : 0) + off, v[b]);
+      for (uint32_t b = 0; b < kBatch; ++b) {
+        if constexpr (loads_piece<SRC>::value) src.template load<NW, POL>(s0 + b < k ? s0 + b : 0, off, v[b]);
+        else ldw<NW, POL>(src_of(s0 + b < k ? s0 + b : 0) + off, v[b]);
+      }
 #pragma unroll
       for (uint32_t b = 0; b < kBatch; ++b)
         if (s0 + b < k) consume(v[b], s0 + b, k);

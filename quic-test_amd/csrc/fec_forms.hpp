@@ -451,6 +451,55 @@ inline GatherForm gather_form(uint32_t k, uint32_t r, uint32_t P) {
   return f;
 }
 
+// ---- variable-length address tables (fec_recover_gather_var_rs_dev, fec_encode_gather_var_rs_dev;
+// fec_gather_var.hip) ----
+// The address table with a u32 length per entry, indexed alike: shard (g, s) is the bytes
+// [0, min(len, P)) at its address, zeros up to P (fec_varlen.hpp).
+struct GatherVarLaunch {
+  GatherLaunch g;            // as the fixed-length recover
+  const uint32_t* lens;      // groups * (k + r) readable bytes per entry; a lost entry's is ignored
+  uint32_t* symlen_out;      // nullable: per group the largest min(len, P) of its present entries
+};
+
+struct GatherVarEncodeLaunch {
+  const uint64_t* addrs;     // groups * k absolute device addresses, 0 = absent (counts as zeros)
+  const uint32_t* lens;      // groups * k
+  uint64_t groups;
+  uint32_t k, r, P;
+  uint8_t* parity;           // parity row (g, i) at (g * r + i) * P, full P-byte rows
+  uint32_t* symlen_out;      // nullable
+  const void* tables;        // (r-1) x k CoefEntry (rows 1..r-1), device
+};
+
+// The instantiations of recover_gather_var, X(K, MAXE, POL): the shapes and policies of
+// recover_gather, in a list of their own (QFEC_GATHER_FORMS stays the fixed-length kernel's).
+#define QFEC_GATHER_VAR_FORMS(X) QFEC_GATHER_SHAPES(QFEC_GATHER_FIXED, X) X(0, 8, kGatherPol | kNoCoefBranch)
+
+// The form fec_recover_gather_var_rs_dev runs for (k, r, P): a classify_gather_var launch, then
+// recover_gather_var<K, MAXE, POL> in ceil(r / MAXE) passes -- the fixed-length call's choice.
+inline GatherForm gather_var_form(uint32_t k, uint32_t r, uint32_t P) { return gather_form(k, r, P); }
+
+// fec_encode_gather_var_rs_dev: encode_gather_var<0, R, FIRST> at runtime k for every shape, in
+// passes of up to kGatherVarEncodeRows parity rows (the route the fixed-length gather encode takes
+// for every shape but k=10 r=1); the first pass owns the XOR row and writes the symbol lengths.
+constexpr uint32_t kGatherVarEncodeRows = 8;
+constexpr int kGatherVarEncodePol = kNtStore;
+struct GatherVarEncodeForm {
+  bool supported = false;  // false: P < 16, the call is refused
+  uint32_t passes = 0;     // pass p: rows [p * 8, min(r, p * 8 + 8)), FIRST = (p == 0)
+};
+inline GatherVarEncodeForm gather_var_encode_form(uint32_t k, uint32_t r, uint32_t P) {
+  GatherVarEncodeForm f;
+  if (P < kVecMinP) return f;
+  f.supported = true;
+  f.passes = (r + kGatherVarEncodeRows - 1) / kGatherVarEncodeRows;
+  return f;
+}
+inline uint32_t gather_var_encode_rows(uint32_t r, uint32_t pass) {
+  const uint32_t row0 = pass * kGatherVarEncodeRows;
+  return r - row0 < kGatherVarEncodeRows ? r - row0 : kGatherVarEncodeRows;
+}
+
 // ---- encode ----
 enum class EncodeKernel : int { kBytes, kV16, kBits };
 

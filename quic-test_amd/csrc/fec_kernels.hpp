@@ -39,6 +39,10 @@ hipError_t launch_encode(const EncodeLaunch& a, hipStream_t s);
 hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s);
 // Recover from an address table (fec_gather.hip): classify_gather, then gather_form's recover_gather.
 hipError_t launch_recover_gather(const GatherLaunch& a, hipStream_t s);
+// The same with a length per table entry (fec_gather_var.hip): classify_gather_var, then
+// gather_var_form's recover_gather_var; and the encode from addresses and lengths, 0 = absent.
+hipError_t launch_recover_gather_var(const GatherVarLaunch& a, hipStream_t s);
+hipError_t launch_encode_gather_var(const GatherVarEncodeLaunch& a, hipStream_t s);
 // Packed recover rows: row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.

@@ -82,6 +82,13 @@ enum class GatherLaunchForm : int64_t {
   kClassifyGather = 18,
   kRecoverGather = 19,
 };
+// The variable-length address-table kernels (fec_gather_var.hip), numbered on in a list of their
+// own again (fec_forms.hpp QFEC_GATHER_VAR_FORMS); named by quicfec.GATHER_VAR_LAUNCH_FORMS.
+enum class GatherVarLaunchForm : int64_t {
+  kClassifyGatherVar = 20,
+  kRecoverGatherVar = 21,
+  kEncodeGatherVar = 22,
+};
 
 // One launch: 16 words, -1 where a field does not apply to the form.
 struct LaunchRecord {
@@ -100,7 +107,7 @@ struct LaunchRecord {
   int64_t block = 0;     // work items per workgroup
   int64_t first_item = 0;  // first group (fill / copy: first 16-B word or byte) of this launch
   int64_t items = 0;     // groups (fill / copy: words or bytes) of this launch
-  int64_t aux = -1;      // encode_v16: first parity row; decodes, recover_gather: first rebuilt row of the pass;
+  int64_t aux = -1;      // encode_v16, encode_gather_var: first parity row; decodes, recover_gather(_var): first rebuilt row of the pass;
                          // encode_bits: W; recover_runs: run-image bytes; fill / copy: bytes per
                          // work item
 };

@@ -1758,6 +1758,104 @@ QFEC_EXPORT int fec_encode_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_p
   return record_ctx_error(ctx, fec_encode_gather_rs_dev_impl(ctx, d_packet_addrs, G, k, r, P, d_parity, stream));
 }
 
+// ---- the same with a length per table entry (fec_gather_var.hip) ----
+static int fec_recover_gather_var_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
+                                              const uint32_t* d_shard_lens, uint64_t G, uint32_t k, uint32_t r,
+                                              uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
+                                              uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream) {
+  if (!ctx || !d_shard_addrs || !d_shard_lens || !d_rebuilt) {
+    set_error("variable-length gather recover: %s is NULL", !ctx             ? "the context"
+                                                            : !d_shard_addrs ? "d_shard_addrs"
+                                                            : !d_shard_lens  ? "d_shard_lens (the length table)"
+                                                                             : "d_rebuilt");
+    return FEC_ERR_NULL;
+  }
+  int rc = check_gather_shape("variable-length gather recover", G, k, r, P);
+  if (rc != FEC_OK) return rc;
+  qfec::CodebookLayout layout;
+  if (!qfec::codebook_layout(k, r, kCodebookCap, layout)) {
+    set_error("variable-length gather recover: the codebook of k=%u r=%u exceeds the %llu-byte cap (sparse-plan "
+              "shape: use fec_recover_batch_rs_dev)", k, r, static_cast<unsigned long long>(kCodebookCap));
+    return FEC_ERR_RANGE;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard dg(ctx->device);
+  if (!dg.ok) return FEC_ERR_NODEV;
+  DecodePlan* plan = nullptr;
+  rc = get_decode_plan(ctx, k, r, &plan);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = pick_stream(ctx, stream);
+  qfec::GatherVarLaunch a{};
+  a.g.addrs = d_shard_addrs;
+  a.g.groups = G;
+  a.g.k = k;
+  a.g.r = r;
+  a.g.P = P;
+  a.g.out = d_rebuilt;
+  a.g.status = d_status;
+  a.g.masks_out = d_masks_out;
+  a.g.codebook = plan->codebook.as<uint8_t>();
+  a.g.binom = ctx->d_binom.as<uint64_t>();
+  a.g.meta = level_meta(plan->layout, r);
+  a.lens = d_shard_lens;
+  a.symlen_out = d_symbol_len_out;
+  // record offsets: the caller stream's workspace, as the fixed-length call's
+  void* ws = nullptr;
+  QFEC_HIP(stream_workspace(ctx, s, G * sizeof(uint32_t), &ws));
+  a.g.rec_off = static_cast<uint32_t*>(ws);
+  QFEC_HIP(qfec::launch_recover_gather_var(a, s));
+  return FEC_OK;
+}
+
+QFEC_EXPORT int fec_recover_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
+                                              const uint32_t* d_shard_lens, uint64_t G, uint32_t k, uint32_t r,
+                                              uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
+                                              uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream) {
+  g_last_error.clear();
+  return record_ctx_error(ctx, fec_recover_gather_var_rs_dev_impl(ctx, d_shard_addrs, d_shard_lens, G, k, r, P, d_rebuilt,
+                                                                  d_status, d_masks_out, d_symbol_len_out, stream));
+}
+
+static int fec_encode_gather_var_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
+                                             const uint32_t* d_packet_lens, uint64_t G, uint32_t k, uint32_t r,
+                                             uint32_t P, uint8_t* d_parity, uint32_t* d_symbol_len_out, void* stream) {
+  if (!ctx || !d_packet_addrs || !d_packet_lens || !d_parity) {
+    set_error("variable-length gather encode: %s is NULL", !ctx              ? "the context"
+                                                           : !d_packet_addrs ? "d_packet_addrs"
+                                                           : !d_packet_lens  ? "d_packet_lens (the length table)"
+                                                                             : "d_parity");
+    return FEC_ERR_NULL;
+  }
+  int rc = check_gather_shape("variable-length gather encode", G, k, r, P);
+  if (rc != FEC_OK) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard dg(ctx->device);
+  if (!dg.ok) return FEC_ERR_NODEV;
+  const void* tables = nullptr;
+  rc = get_encode_plan(ctx, k, r, &tables);
+  if (rc != FEC_OK) return rc;
+  qfec::GatherVarEncodeLaunch a{};
+  a.addrs = d_packet_addrs;
+  a.lens = d_packet_lens;
+  a.groups = G;
+  a.k = k;
+  a.r = r;
+  a.P = P;
+  a.parity = d_parity;
+  a.symlen_out = d_symbol_len_out;
+  a.tables = tables;
+  QFEC_HIP(qfec::launch_encode_gather_var(a, pick_stream(ctx, stream)));
+  return FEC_OK;
+}
+
+QFEC_EXPORT int fec_encode_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
+                                             const uint32_t* d_packet_lens, uint64_t G, uint32_t k, uint32_t r,
+                                             uint32_t P, uint8_t* d_parity, uint32_t* d_symbol_len_out, void* stream) {
+  g_last_error.clear();
+  return record_ctx_error(ctx, fec_encode_gather_var_rs_dev_impl(ctx, d_packet_addrs, d_packet_lens, G, k, r, P, d_parity,
+                                                                 d_symbol_len_out, stream));
+}
+
 static int fec_decode_prepare_impl(FECEncoderCtx* ctx, uint32_t k, uint32_t r, uint64_t* bytes_out) {
   if (!ctx) return FEC_ERR_NULL;
   int rc = check_shape(1, k, r, 1, true);

@@ -55,6 +55,7 @@ HIP_SYMBOLS = (
     "fec_batcher_new_multi", "fec_batcher_new_decoder_multi", "fec_batcher_devices",
     "fec_recover_batch_rs_dev_packed", "fec_coalesce_stats", "fec_coalesce_stats_sized",
     "fec_recover_gather_rs_dev", "fec_encode_gather_rs_dev",
+    "fec_recover_gather_var_rs_dev", "fec_encode_gather_var_rs_dev",
 )
 
 
@@ -149,6 +150,8 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
                                                    _vp, _vp, _vp]),
         "fec_recover_gather_rs_dev": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
         "fec_encode_gather_rs_dev": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
+        "fec_recover_gather_var_rs_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+        "fec_encode_gather_var_rs_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -324,6 +327,28 @@ class Context:
         rc = self.lib.fec_encode_gather_rs_dev(self.handle, _ptr(d_packet_addrs) if d_packet_addrs is not None else None,
                                                num_groups, k, r, packet_size, _ptr(d_parity), stream)
         _check(rc, "fec_encode_gather_rs_dev", self.lib)
+
+    def recover_gather_var_dev(self, d_shard_addrs, d_shard_lens, num_groups: int, k: int, r: int, packet_size: int,
+                               d_rebuilt, d_status=None, d_masks_out=None, d_symbol_len_out=None,
+                               stream: Optional[int] = None) -> None:
+        """recover_gather_dev with a u32 length per table entry (d_shard_lens, indexed like the
+        addresses): shard (g, s) is its first min(len, packet_size) bytes, zero-padded; nothing at or
+        past address + len is read.  d_symbol_len_out (nullable, u32 per group): the largest clamped
+        length among the group's present entries."""
+        opt = lambda t: _ptr(t) if t is not None else None   # noqa: E731
+        rc = self.lib.fec_recover_gather_var_rs_dev(self.handle, opt(d_shard_addrs), opt(d_shard_lens), num_groups, k, r,
+                                                    packet_size, opt(d_rebuilt), opt(d_status), opt(d_masks_out),
+                                                    opt(d_symbol_len_out), stream)
+        _check(rc, "fec_recover_gather_var_rs_dev", self.lib)
+
+    def encode_gather_var_dev(self, d_packet_addrs, d_packet_lens, num_groups: int, k: int, r: int, packet_size: int,
+                              d_parity, d_symbol_len_out=None, stream: Optional[int] = None) -> None:
+        """encode_gather_dev with a u32 length per packet; address 0 = absent (all zero).  Parity rows
+        are full packet_size-byte rows; d_symbol_len_out (nullable): each group's repair payload length."""
+        opt = lambda t: _ptr(t) if t is not None else None   # noqa: E731
+        rc = self.lib.fec_encode_gather_var_rs_dev(self.handle, opt(d_packet_addrs), opt(d_packet_lens), num_groups, k, r,
+                                                   packet_size, opt(d_parity), opt(d_symbol_len_out), stream)
+        _check(rc, "fec_encode_gather_var_rs_dev", self.lib)
 
     def decode_prepare(self, k: int, r: int) -> int:
         n = ctypes.c_uint64(0)
@@ -564,6 +589,8 @@ LAUNCH_FORMS = {1: "encode_v16", 2: "encode_bits", 3: "encode_bytes", 4: "classi
                 17: "runs_rezero"}     # no kernel: recover_runs' workspace re-zeroed at an epoch wrap (items = bytes)
 # the address-table kernels (csrc/fec_gather.hip; fec_knobs.hpp GatherLaunchForm), a list of their own
 GATHER_LAUNCH_FORMS = {18: "classify_gather", 19: "recover_gather"}
+# the variable-length address-table kernels (csrc/fec_gather_var.hip; GatherVarLaunchForm), again their own
+GATHER_VAR_LAUNCH_FORMS = {20: "classify_gather_var", 21: "recover_gather_var", 22: "encode_gather_var"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -590,6 +617,7 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
     out = []
     for row in buf[:seen]:
         rec = dict(zip(LAUNCH_FIELDS, (int(x) for x in row)))
-        rec["form"] = LAUNCH_FORMS.get(rec["form"], GATHER_LAUNCH_FORMS.get(rec["form"], rec["form"]))
+        form = rec["form"]
+        rec["form"] = LAUNCH_FORMS.get(form, GATHER_LAUNCH_FORMS.get(form, GATHER_VAR_LAUNCH_FORMS.get(form, form)))
         out.append(rec)
     return out
