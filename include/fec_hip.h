@@ -201,6 +201,43 @@ int fec_encode_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_ad
                                  const uint32_t* d_packet_lens, uint64_t num_groups, uint32_t k, uint32_t r,
                                  uint32_t packet_size, uint8_t* d_parity, uint32_t* d_symbol_len_out, void* stream);
 
+/* ---- scatter recover: rebuilt packets written to a table of destinations ----
+ * The gather recovers above write every rebuilt packet into a library-shaped buffer as a full
+ * P-byte row.  This call writes each rebuilt packet where the caller says, and only the bytes the
+ * packet has (the reference's decoder returns each recovered packet as a buffer of its symbol
+ * length).
+ *   - Inputs: d_shard_addrs and d_shard_lens exactly as fec_recover_gather_var_rs_dev (clamping
+ *     at P, zero padding, no byte at or past address + len read, a present shard of length 0 never
+ *     dereferenced).  d_shard_lens == NULL: every present shard has P bytes, the inputs of
+ *     fec_recover_gather_rs_dev.
+ *   - d_symbol_len_out (nullable, u32 per group), written for every group: L_g, the largest
+ *     min(len, P) over the group's present entries (P without a length table), 0 when none is
+ *     present.
+ *   - d_dest_addrs: num_groups*k absolute device addresses (u64), entry [g*k + j] for data shard j
+ *     of group g, any byte alignment.  If the call rebuilds that shard it writes exactly L_g bytes
+ *     there (the rebuilt bytes past L_g are zero by construction): no byte before the address or
+ *     at or past address + L_g is written, so a rebuilt packet may sit between two live ones.
+ *     L_g == 0 writes nothing and dereferences nothing.
+ *   - An entry is read only for a data shard that is lost in a recoverable group; the entries of
+ *     present shards, of groups with nothing lost and of unrecoverable groups are ignored.  An
+ *     entry of 0 for a shard the call would rebuild means "not wanted": that row is not stored,
+ *     the group's other rows are, and the status stays 0.
+ *   - Decode rule, d_status and d_masks_out as in the gather recovers; a lost shard's source entry
+ *     and a parity row the rule does not use are never read.
+ *   - A destination range must not overlap any shard the call reads, in any group, nor another
+ *     destination range.  Destinations that are the holes the receiver reserved for the lost
+ *     packets in its arena give in-place gathered decode; destinations back to back give packed
+ *     output; destinations at d_rebuilt + (g*r + m)*P give the slot layout of the gather recovers.
+ * Refused like the gather calls, with nothing launched or written; a NULL context, address table
+ * or destination table is FEC_ERR_NULL and the message names it.  Asynchronous on `stream`,
+ * drained by fec_encoder_free; record offsets (and L_g, when d_symbol_len_out is NULL) live in the
+ * caller stream's workspace, no new per-context state. */
+int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
+                               const uint32_t* d_shard_lens, const uint64_t* d_dest_addrs,
+                               uint64_t num_groups, uint32_t k, uint32_t r, uint32_t packet_size,
+                               uint8_t* d_status, uint64_t* d_masks_out, uint32_t* d_symbol_len_out,
+                               void* stream);
+
 /* Expected share (0..1) of groups that lost data shards in this context's device-resident
  * decode calls, e.g. 1 - (1 - p)^k for iid loss p (the receiver knows its network profile;
  * satellite p = 0.01, k = 10: ~0.10).  Below 0.25 the decode checks several groups per

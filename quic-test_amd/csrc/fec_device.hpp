@@ -1,5 +1,5 @@
 // fec_device.hpp — the device code shared by the kernel translation units (fec_kernels.hip,
-// fec_gather.hip, fec_gather_var.hip).  First the small pieces: the coefficient table entry,
+// fec_gather.hip, fec_gather_var.hip, fec_scatter.hip).  First the small pieces: the coefficient table entry,
 // byte-aligned packet loads and stores under a memory policy, the GF(2^8) product of a dword, the
 // selector split of a dword (SelN / sel_split), record bytes and the workgroup order.  Then the
 // record-addressed decode, stated once:
@@ -7,7 +7,9 @@
 //  * RecHead / rec_head: a record's header (row count, XOR flag, coefficient tables);
 //  * decode_piece: the rebuild of one lane's piece of every lost row.  The survivors' bases come
 //    from the record and the group's contiguous data / parity (RecordBases, the default), or
-//    from a caller's functor (the address-table recover);
+//    from a caller's functor (the address-table recovers); the rebuilt rows go to the record's
+//    places in the group's output (RecordRows, the default) or through a caller's functor (the
+//    scatter recover);
 //  * decode_walk: the walk of a wave over a packet, piece by piece.
 // Everything is internal to its translation unit (unnamed namespace).  The helpers keep the
 // statement order of the kernels they were taken from: the kernels' instruction order follows it.
@@ -194,13 +196,20 @@ struct loads_piece : std::false_type {};
 template <typename SRC>
 struct loads_piece<SRC, std::void_t<typename SRC::loads_piece>> : std::true_type {};
 
+// decode_piece's default destination: row m0 + m at the erased shard's place in `og` (in place)
+// or at row m0 + m of the group's compact run (kCompactOut).  Any other DST is a functor that
+// stores the lane's piece of row m0 + m itself, dst.store<NW, POL>(m, off, v) (the scatter
+// recover, fec_scatter.hip: the row goes to a destination of the caller's).
+struct RecordRows {};
+
 // Rebuild rows [m0, m0 + MAXE) of one group's record at byte offset `off` of every
 // packet, NW dwords per lane.  The record (survivors, tables) is wave-uniform: SGPRs.
-template <int K, int MAXE, int POL, int NW, typename SRC = RecordBases>
+template <int K, int MAXE, int POL, int NW, typename SRC = RecordBases, typename DST = RecordRows>
 __device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, const Tab* __restrict__ tabs,
                                              const uint8_t* __restrict__ dg, const uint8_t* __restrict__ pg,
                                              uint8_t* __restrict__ og, uint32_t k, uint32_t P, uint32_t off,
-                                             uint32_t e, uint32_t m0, bool xor_only, SRC src = SRC{}) {
+                                             uint32_t e, uint32_t m0, bool xor_only, SRC src = SRC{},
+                                             DST dst = DST{}) {
   auto src_of = [&](uint32_t s) -> const uint8_t* {
     if constexpr (std::is_same_v<SRC, RecordBases>) {
       const uint32_t sid = rec_byte(rw, s);
@@ -243,7 +252,9 @@ __device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, co
             for (int q = 0; q < NW; ++q) acc[q] ^= v[b][q];
       }
     }
-    stw<NW, POL>(og + ((POL & kCompactOut) != 0 ? 0u : rec_byte(rw, 64)) * static_cast<uint64_t>(P) + off, acc);
+    if constexpr (std::is_same_v<DST, RecordRows>)
+      stw<NW, POL>(og + ((POL & kCompactOut) != 0 ? 0u : rec_byte(rw, 64)) * static_cast<uint64_t>(P) + off, acc);
+    else dst.template store<NW, POL>(0u, off, acc);  // e = 1: row 0, m0 = 0
     return;
   }
   uint32_t acc[MAXE][NW];
@@ -304,8 +315,12 @@ __device__ __forceinline__ void decode_piece(const uint32_t* __restrict__ rw, co
   for (int m = 0; m < MAXE; ++m) {
     if (m0 + m < e) {
       // in place: at the erased shard; compact (kCompactOut): row m0 + m of the group's run
-      const uint32_t eid = (POL & kCompactOut) != 0 ? m0 + m : rec_byte(rw, 64 + m0 + m);
-      stw<NW, POL>(og + eid * static_cast<uint64_t>(P) + off, acc[m]);
+      if constexpr (std::is_same_v<DST, RecordRows>) {
+        const uint32_t eid = (POL & kCompactOut) != 0 ? m0 + m : rec_byte(rw, 64 + m0 + m);
+        stw<NW, POL>(og + eid * static_cast<uint64_t>(P) + off, acc[m]);
+      } else {
+        dst.template store<NW, POL>(static_cast<uint32_t>(m), off, acc[m]);
+      }
     }
   }
 }

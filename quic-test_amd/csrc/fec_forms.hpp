@@ -500,6 +500,45 @@ inline uint32_t gather_var_encode_rows(uint32_t r, uint32_t pass) {
   return r - row0 < kGatherVarEncodeRows ? r - row0 : kGatherVarEncodeRows;
 }
 
+// ---- scatter recover (fec_recover_scatter_rs_dev, fec_scatter.hip) ----
+// The address table (with or without the length table) in, and a table of destinations out:
+// data shard j of group g, if the call rebuilds it, goes to dests[g * k + j], exactly the group's
+// symbol length of it (fec_scatter_cut.hpp); 0 = not wanted.
+struct ScatterLaunch {
+  GatherLaunch g;            // as the fixed-length recover; g.out is not used
+  const uint32_t* lens;      // nullable: groups * (k + r) readable bytes per entry; NULL = every present shard has P
+  const uint64_t* dests;     // groups * k absolute device addresses
+  uint32_t* symlen;          // per group the largest min(len, P) of its present entries (P without
+                             // a length table), 0 when none is present: the caller's output or, when
+                             // that is NULL and there is a length table, workspace (the kernel reads it)
+};
+
+// The instantiations of recover_scatter, X(K, MAXE, POL, VAR): the shapes and policies of
+// recover_gather once without (VAR = false) and once with the length table, in a list of their own.
+// kCompactOut stays set in POL (the forms are the gather recover's); the rows go to the
+// destination table whatever it says.
+#define QFEC_SCATTER_FIXED(X, K, R) X(K, R, kGatherPol, false) X(K, R, kGatherPol, true)
+#define QFEC_SCATTER_FORMS(X)                  \
+  QFEC_GATHER_SHAPES(QFEC_SCATTER_FIXED, X)    \
+  X(0, 8, kGatherPol | kNoCoefBranch, false) X(0, 8, kGatherPol | kNoCoefBranch, true)
+
+struct ScatterForm {
+  bool supported = false;  // false: P < 16, the call is refused
+  int K = 0, MAXE = 0;     // template shape; runtime k as K = 0, MAXE = 8
+  int POL = 0;
+  bool VAR = false;        // loads masked by the length table, stores cut at the symbol length
+};
+
+// The form fec_recover_scatter_rs_dev runs for (k, r, P) with (var) or without a length table: a
+// classify_scatter launch, then recover_scatter<K, MAXE, POL, VAR> in ceil(r / MAXE) passes -- the
+// gather recover's choice of shape and policy.
+inline ScatterForm scatter_form(uint32_t k, uint32_t r, uint32_t P, bool var) {
+  const GatherForm g = gather_form(k, r, P);
+  ScatterForm f;
+  f.supported = g.supported, f.K = g.K, f.MAXE = g.MAXE, f.POL = g.POL, f.VAR = g.supported && var;
+  return f;
+}
+
 // ---- encode ----
 enum class EncodeKernel : int { kBytes, kV16, kBits };
 

@@ -43,6 +43,9 @@ hipError_t launch_recover_gather(const GatherLaunch& a, hipStream_t s);
 // gather_var_form's recover_gather_var; and the encode from addresses and lengths, 0 = absent.
 hipError_t launch_recover_gather_var(const GatherVarLaunch& a, hipStream_t s);
 hipError_t launch_encode_gather_var(const GatherVarEncodeLaunch& a, hipStream_t s);
+// Recover from an address table into a table of destinations (fec_scatter.hip): classify_scatter,
+// then scatter_form's recover_scatter.
+hipError_t launch_recover_scatter(const ScatterLaunch& a, hipStream_t s);
 // Packed recover rows: row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.

@@ -89,6 +89,12 @@ enum class GatherVarLaunchForm : int64_t {
   kRecoverGatherVar = 21,
   kEncodeGatherVar = 22,
 };
+// The scatter recover's kernels (fec_scatter.hip), numbered on in a list of their own
+// (fec_forms.hpp QFEC_SCATTER_FORMS); named by quicfec.SCATTER_LAUNCH_FORMS.
+enum class ScatterLaunchForm : int64_t {
+  kClassifyScatter = 23,
+  kRecoverScatter = 24,  // LaunchRecord::first: 1 with a length table (VAR), 0 without
+};
 
 // One launch: 16 words, -1 where a field does not apply to the form.
 struct LaunchRecord {
@@ -98,7 +104,7 @@ struct LaunchRecord {
   int64_t nm = -1;       // 16-B pieces per lane (decode_fused, recover_runs)
   int64_t nt = -1;       //  4-B pieces per lane
   int64_t off = -1;      // encode: OffsetKind of the instantiation
-  int64_t first = -1;    // encode_v16: this pass owns the XOR row
+  int64_t first = -1;    // encode_v16: this pass owns the XOR row; recover_scatter: the length-table form
   int64_t pol = -1;      // memory policy / form bits (fec_forms.hpp kNtLoad .. kStageRows)
   int64_t direct = -1;   // decode_fused: mask-addressed; rows_write: writes the total itself
   int64_t scan = -1;     // decode_fused: groups per wave of the scan form (0: one wave per group)
@@ -107,7 +113,7 @@ struct LaunchRecord {
   int64_t block = 0;     // work items per workgroup
   int64_t first_item = 0;  // first group (fill / copy: first 16-B word or byte) of this launch
   int64_t items = 0;     // groups (fill / copy: words or bytes) of this launch
-  int64_t aux = -1;      // encode_v16, encode_gather_var: first parity row; decodes, recover_gather(_var): first rebuilt row of the pass;
+  int64_t aux = -1;      // encode_v16, encode_gather_var: first parity row; decodes, recover_gather(_var), recover_scatter: first rebuilt row of the pass;
                          // encode_bits: W; recover_runs: run-image bytes; fill / copy: bytes per
                          // work item
 };

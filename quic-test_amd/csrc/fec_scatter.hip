@@ -1,0 +1,302 @@
+// fec_scatter.hip — gfx950 kernels of fec_recover_scatter_rs_dev: recover from an address table
+// (with or without a length per entry) and write every rebuilt packet where the caller's table of
+// destinations says, exactly the group's symbol length L of it.  Destinations that are the holes
+// of the caller's arena give in-place gathered decode, destinations back to back packed output.
+//
+//  * classify_scatter: classify_gather_var with a nullable length table (NULL: every present shard
+//    has P bytes) -- the mask, the status, the codebook record and the symbol length of each group.
+//  * recover_scatter<K, MAXE, POL, VAR>: one wave per group, record-addressed like recover_gather /
+//    recover_gather_var (VAR: with the length table).  The survivors' addresses (and lengths) are
+//    fetched once per group as there; so are the destinations of the rows of the pass, row m0 + m
+//    from the entry of shard id rec_byte(rw, 64 + m0 + m) (compile-time k: scalar loads into SGPRs;
+//    runtime k: a per-wave LDS slice).  The wave walks [0, L) instead of [0, P) (scatter_walk), so
+//    the rebuilt zeros past L are neither loaded for nor stored; VAR loads stay masked per shard
+//    (var_load).  Which bytes a lane stores is decided in fec_scatter_cut.hpp and nowhere else.
+// The rule, the record header, the piece rebuild and the GF(2^8) product are fec_device.hpp's.
+//
+// A lost shard's source entry, a parity row the rule does not use, and the destination entry of
+// any shard the call does not rebuild are never read.  A destination of 0 is not stored to.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <type_traits>
+
+#include "fec_device.hpp"
+#include "fec_kernels.hpp"
+#include "fec_knobs.hpp"
+#include "fec_launch.hpp"
+#include "fec_scatter_cut.hpp"
+#include "fec_varlen.hpp"
+
+namespace qfec {
+namespace {
+
+// A table entry as a packet pointer: cast to a global-memory pointer first, so the accesses
+// through it are global loads / stores (as fec_gather.hip's).
+__device__ __forceinline__ const uint8_t* shard_ptr(uint64_t addr) {
+  typedef const __attribute__((address_space(1))) uint8_t* global_u8p;
+  return (const uint8_t*)reinterpret_cast<global_u8p>(addr);
+}
+
+__device__ __forceinline__ uint8_t* dest_ptr(uint64_t addr) {
+  typedef __attribute__((address_space(1))) uint8_t* global_u8p;
+  return (uint8_t*)reinterpret_cast<global_u8p>(addr);
+}
+
+__device__ __forceinline__ uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+
+// The piece at `off` of the shard (p, len): var_load over the form's loads.
+template <int NW, int POL>
+__device__ __forceinline__ void load_masked(const uint8_t* p, uint32_t off, uint32_t len, uint32_t (&v)[NW]) {
+  var_load<NW>(
+      p, off, len, v, [](const uint8_t* q, uint32_t(&w)[NW]) { ldw<NW, POL>(q, w); },
+      [](const uint8_t* q) { return *q; });
+}
+
+// Workgroup of 256 lanes = 256 consecutive groups, as classify_gather_var; `lens` nullable.
+__global__ __launch_bounds__(256) void classify_scatter(const uint64_t* __restrict__ addrs,
+                                                        const uint32_t* __restrict__ lens, uint64_t groups,
+                                                        uint32_t k, uint32_t r, uint32_t P,
+                                                        const uint64_t* __restrict__ binom, LevelMeta meta,
+                                                        uint32_t* __restrict__ rec_off,
+                                                        uint8_t* __restrict__ status,
+                                                        uint64_t* __restrict__ masks_out,
+                                                        uint32_t* __restrict__ symlen_out) {
+  __shared__ unsigned long long lost[256];
+  __shared__ uint32_t symlen[256];
+  const uint64_t g0 = static_cast<uint64_t>(blockIdx.x) * 256u;
+  const uint32_t gn = groups - g0 < 256u ? static_cast<uint32_t>(groups - g0) : 256u;
+  const uint32_t n = k + r;
+  lost[threadIdx.x] = 0;
+  symlen[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t* __restrict__ tab = addrs + g0 * n;
+  const uint32_t* __restrict__ ltab = lens ? lens + g0 * n : nullptr;
+  const uint32_t entries = gn * n;  // at most 256 * 64
+  for (uint32_t i = threadIdx.x; i < entries; i += 256u) {
+    if (tab[i] == 0) {
+      atomicOr(&lost[i / n], 1ull << (i % n));  // a lost entry's length is ignored
+    } else {
+      atomicMax(&symlen[i / n], ltab ? min_u32(ltab[i], P) : P);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x >= gn) return;
+  const uint64_t g = g0 + threadIdx.x;
+  const uint64_t m = lost[threadIdx.x];
+  const Classified c = classify_mask(m, k, r, binom, meta);
+  rec_off[g] = c.rec;
+  if (status) status[g] = c.status;
+  if (masks_out) masks_out[g] = m;
+  if (symlen_out) symlen_out[g] = symlen[threadIdx.x];
+}
+
+// The survivors of a group as decode_piece's functor, loading through the mask (`loads_piece`):
+// fec_gather_var.hip's.  Compile-time k: bases and clamped lengths in SGPRs.
+template <int K>
+struct VarSurvivors {
+  using loads_piece = void;
+  const uint8_t* base[K];
+  uint32_t len[K];
+  template <int NW, int POL>
+  __device__ __forceinline__ void load(uint32_t s, uint32_t off, uint32_t (&v)[NW]) const {
+    load_masked<NW, POL>(base[s], off, len[s], v);
+  }
+};
+
+// Runtime k: addresses and clamped lengths in the wave's two LDS slices.
+struct VarSurvivorsLds {
+  using loads_piece = void;
+  const uint64_t* addr;
+  const uint32_t* len;
+  template <int NW, int POL>
+  __device__ __forceinline__ void load(uint32_t s, uint32_t off, uint32_t (&v)[NW]) const {
+    load_masked<NW, POL>(shard_ptr(addr[s]), off, len[s], v);
+  }
+};
+
+// decode_piece's destination functor: rows(m) is the destination of row m0 + m (nullptr: not
+// wanted).  BYTES: the byte-wise pass of L < 4.  The stores are fec_scatter_cut.hpp's.
+template <typename ROWS, bool BYTES>
+struct ScatterDst {
+  ROWS rows;
+  uint32_t lane, L;
+  template <int NW, int POL>
+  __device__ __forceinline__ void store(uint32_t m, uint32_t off, const uint32_t (&v)[NW]) const {
+    if constexpr (BYTES) {
+      static_assert(NW == 1, "the byte-wise pass rebuilds one dword");
+      scatter_store_byte(rows(m), lane, L, v[0], [](uint8_t* q, uint8_t b) { *q = b; });
+    } else {
+      scatter_store<NW>(rows(m), off, v, [](uint8_t* q, const uint32_t(&w)[NW]) { stw<NW, POL>(q, w); });
+    }
+  }
+};
+
+// The walk of a wave over [0, L) (scatter_walk) with the choice of loads per pass.  VAR: a pass
+// whose bytes lie below `minlen`, the shortest survivor (wave-uniform), takes `plain` (s -> base,
+// unmasked loads), any other pass `masked`, as fec_gather_var.hip's var_walk.  Without a length
+// table every pass takes `plain`.
+template <int K, int MAXE, int POL, bool VAR, typename PLAIN, typename MASKED, typename ROWS>
+__device__ __forceinline__ void scatter_decode(const uint32_t* rw, const Tab* tabs, uint32_t k, uint32_t P,
+                                               uint32_t lane, uint32_t e, uint32_t m0, bool xor_only, uint32_t L,
+                                               uint32_t minlen, PLAIN plain, MASKED masked, ROWS rows) {
+  const auto piece = [&](auto nw, auto bytes, uint32_t end, uint32_t off) {
+    constexpr int NW = decltype(nw)::value;
+    const ScatterDst<ROWS, decltype(bytes)::value> dst{rows, lane, L};
+    if constexpr (VAR) {
+      if (end <= minlen) decode_piece<K, MAXE, POL, NW>(rw, tabs, nullptr, nullptr, nullptr, k, P, off, e, m0, xor_only, plain, dst);
+      else decode_piece<K, MAXE, POL, NW>(rw, tabs, nullptr, nullptr, nullptr, k, P, off, e, m0, xor_only, masked, dst);
+    } else {
+      decode_piece<K, MAXE, POL, NW>(rw, tabs, nullptr, nullptr, nullptr, k, P, off, e, m0, xor_only, plain, dst);
+    }
+  };
+  using W4 = std::integral_constant<int, 4>;
+  using W1 = std::integral_constant<int, 1>;
+  scatter_walk(
+      L, lane, [&](uint32_t base, uint32_t off) { piece(W4{}, std::false_type{}, base + 1024u, off); },
+      [&](uint32_t base, uint32_t off) { piece(W1{}, std::false_type{}, min_u32(base + 256u, L), off); },
+      [&]() { piece(W1{}, std::true_type{}, 4u, 0u); });
+}
+
+// One wave per group (4 per workgroup), the shapes of recover_gather.  `lens` and `symlen` are
+// read only when VAR.
+template <int K, int MAXE, int POL, bool VAR>
+__global__ __launch_bounds__(256) void recover_scatter(const uint64_t* __restrict__ addrs,
+                                                       const uint32_t* __restrict__ lens,
+                                                       const uint64_t* __restrict__ dests,
+                                                       const uint32_t* __restrict__ rec_off,
+                                                       const uint32_t* __restrict__ symlen,
+                                                       const uint8_t* __restrict__ codebook, uint64_t groups,
+                                                       uint32_t P, uint32_t k_rt, uint32_t r, uint32_t m0,
+                                                       uint32_t swz) {
+  const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+  const uint64_t gw = static_cast<uint64_t>(decode_block(swz)) * 4u + wave;
+  if (gw >= groups) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t rec = __builtin_amdgcn_readfirstlane(rec_off[gw]);
+  if (rec >= kRecBad) return;
+  const uint32_t k = K > 0 ? static_cast<uint32_t>(K) : k_rt;
+  const RecHead h = rec_head(codebook, rec);
+  const uint32_t e = h.e();
+  const bool xor_only = h.xor_only();
+  if (m0 >= e) return;
+  uint32_t L = P;
+  if constexpr (VAR) L = min_u32(__builtin_amdgcn_readfirstlane(symlen[gw]), P);
+  if (L == 0) return;  // nothing to write, nothing dereferenced
+  const Tab* tabs = h.tabs();
+  const uint64_t* __restrict__ ga = addrs + gw * (k + r);
+  const uint64_t* __restrict__ gd = dests + gw * k;
+  if constexpr (K > 0) {
+    uint8_t* row[MAXE];
+#pragma unroll
+    for (int m = 0; m < MAXE; ++m) row[m] = m0 + m < e ? dest_ptr(gd[rec_byte(h.rw, 64 + m0 + m)]) : nullptr;
+    const auto rows = [&row](uint32_t m) { return row[m]; };
+    if constexpr (VAR) {
+      const uint32_t* __restrict__ gl = lens + gw * (k + r);
+      VarSurvivors<K> sv;
+      uint32_t minlen = P;
+#pragma unroll
+      for (int s = 0; s < K; ++s) {
+        const uint32_t sid = rec_byte(h.rw, s);
+        sv.base[s] = shard_ptr(ga[sid]);
+        sv.len[s] = min_u32(gl[sid], P);
+        minlen = min_u32(minlen, sv.len[s]);
+      }
+      const auto plain = [&sv](uint32_t s) { return sv.base[s]; };
+      scatter_decode<K, MAXE, POL, true>(h.rw, tabs, k, P, lane, e, m0, xor_only, L, minlen, plain, sv, rows);
+    } else {
+      const uint8_t* base[K];
+#pragma unroll
+      for (int s = 0; s < K; ++s) base[s] = shard_ptr(ga[rec_byte(h.rw, s)]);
+      const auto plain = [&base](uint32_t s) { return base[s]; };
+      scatter_decode<K, MAXE, POL, false>(h.rw, tabs, k, P, lane, e, m0, xor_only, L, P, plain, plain, rows);
+    }
+  } else {
+    __shared__ uint64_t slices[4 * 64];
+    __shared__ uint64_t dest_slices[4 * MAXE];
+    __shared__ uint32_t len_slices[VAR ? 4 * 64 : 4];
+    __shared__ uint32_t shortest[4];
+    uint64_t* slice = slices + wave * 64u;
+    uint64_t* dest_slice = dest_slices + wave * MAXE;
+    uint32_t* len_slice = len_slices + (VAR ? wave * 64u : 0u);
+    const uint8_t* ids = reinterpret_cast<const uint8_t*>(h.rw);
+    if (lane == 0) shortest[wave] = P;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lane < k) {  // survivor `lane` of the record
+      const uint32_t sid = ids[lane];
+      slice[lane] = ga[sid];
+      if constexpr (VAR) {
+        const uint32_t l = min_u32(lens[gw * (k + r) + sid], P);
+        len_slice[lane] = l;
+        atomicMin(&shortest[wave], l);
+      }
+    }
+    if (lane < MAXE) dest_slice[lane] = m0 + lane < e ? gd[ids[64 + m0 + lane]] : 0;  // row m0 + lane of the record
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t minlen = __builtin_amdgcn_readfirstlane(shortest[wave]);
+    const auto plain = [slice](uint32_t s) { return shard_ptr(slice[s]); };
+    const auto rows = [dest_slice](uint32_t m) { return dest_ptr(dest_slice[m]); };
+    if constexpr (VAR)
+      scatter_decode<K, MAXE, POL, true>(h.rw, tabs, k, P, lane, e, m0, xor_only, L, minlen, plain,
+                                         VarSurvivorsLds{slice, len_slice}, rows);
+    else
+      scatter_decode<K, MAXE, POL, false>(h.rw, tabs, k, P, lane, e, m0, xor_only, L, P, plain, plain, rows);
+  }
+}
+
+hipError_t run_classify_scatter(const ScatterLaunch& v, hipStream_t s) {
+  const GatherLaunch& a = v.g;
+  const uint64_t n = a.k + a.r;
+  return for_chunks(a.groups, max_launch_threads(), [&](uint64_t g0, uint64_t gn) {
+    trace_launch(launch_record(static_cast<int64_t>(ScatterLaunchForm::kClassifyScatter), blocks_for(gn), 256, g0, gn));
+    hipLaunchKernelGGL(classify_scatter, dim3(blocks_for(gn)), dim3(256), 0, s, a.addrs + g0 * n,
+                       v.lens ? v.lens + g0 * n : nullptr, gn, a.k, a.r, a.P, a.binom, a.meta, a.rec_off + g0,
+                       a.status ? a.status + g0 : nullptr, a.masks_out ? a.masks_out + g0 : nullptr,
+                       v.symlen ? v.symlen + g0 : nullptr);
+  });
+}
+
+// Wave-per-group launches chunk their groups by whole workgroups, like the decodes.
+template <int K, int MAXE, int POL, bool VAR>
+hipError_t run_recover_scatter(const ScatterLaunch& v, hipStream_t s) {
+  const GatherLaunch& a = v.g;
+  const uint32_t passes = (a.r + MAXE - 1) / MAXE;  // e <= r
+  const uint64_t n = a.k + a.r;
+  for (uint32_t p = 0; p < passes; ++p) {
+    const uint32_t m0 = p * MAXE;
+    const hipError_t e = for_chunks(a.groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
+      const uint64_t bn = (gn + 3) / 4;
+      LaunchRecord t = launch_record(static_cast<int64_t>(ScatterLaunchForm::kRecoverScatter), bn, 256, g0, gn);
+      t.k = K, t.r = MAXE, t.first = VAR, t.pol = POL, t.aux = m0;
+      trace_launch(t);
+      hipLaunchKernelGGL((recover_scatter<K, MAXE, POL, VAR>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
+                         a.addrs + g0 * n, VAR ? v.lens + g0 * n : nullptr, v.dests + g0 * a.k, a.rec_off + g0,
+                         VAR ? v.symlen + g0 : nullptr, a.codebook, gn, a.P, a.k, a.r, m0,
+                         static_cast<uint32_t>(kDecodeWaveXcdSwizzle));
+    });
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace
+
+// Which form runs is decided in fec_forms.hpp (scatter_form); this only launches it.
+hipError_t launch_recover_scatter(const ScatterLaunch& a, hipStream_t s) {
+  if (a.g.groups == 0) return hipSuccess;
+  const ScatterForm f = scatter_form(a.g.k, a.g.r, a.g.P, a.lens != nullptr);
+  if (!f.supported) return hipErrorInvalidValue;
+  if (f.VAR && a.symlen == nullptr) return hipErrorInvalidValue;  // the kernel reads the symbol lengths
+  hipError_t (*run)(const ScatterLaunch&, hipStream_t) = nullptr;
+#define QFEC_SCATTER(KK, MM, PP, VV) \
+  if (f.K == KK && f.MAXE == MM && f.POL == (PP) && f.VAR == VV) run = run_recover_scatter<KK, MM, PP, VV>;
+  QFEC_SCATTER_FORMS(QFEC_SCATTER)
+#undef QFEC_SCATTER
+  if (run == nullptr) return hipErrorNotSupported;
+  const hipError_t e = run_classify_scatter(a, s);
+  return e != hipSuccess ? e : run(a, s);
+}
+
+}  // namespace qfec

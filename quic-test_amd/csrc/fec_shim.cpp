@@ -1856,6 +1856,65 @@ QFEC_EXPORT int fec_encode_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t*
                                                                  d_symbol_len_out, stream));
 }
 
+// ---- the recover with a table of destinations (fec_scatter.hip) ----
+static int fec_recover_scatter_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
+                                           const uint32_t* d_shard_lens, const uint64_t* d_dest_addrs, uint64_t G,
+                                           uint32_t k, uint32_t r, uint32_t P, uint8_t* d_status,
+                                           uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream) {
+  if (!ctx || !d_shard_addrs || !d_dest_addrs) {
+    set_error("scatter recover: %s is NULL", !ctx             ? "the context"
+                                             : !d_shard_addrs ? "d_shard_addrs"
+                                                              : "d_dest_addrs (the destination table)");
+    return FEC_ERR_NULL;
+  }
+  int rc = check_gather_shape("scatter recover", G, k, r, P);
+  if (rc != FEC_OK) return rc;
+  qfec::CodebookLayout layout;
+  if (!qfec::codebook_layout(k, r, kCodebookCap, layout)) {
+    set_error("scatter recover: the codebook of k=%u r=%u exceeds the %llu-byte cap (sparse-plan shape: use "
+              "fec_recover_batch_rs_dev)", k, r, static_cast<unsigned long long>(kCodebookCap));
+    return FEC_ERR_RANGE;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard dg(ctx->device);
+  if (!dg.ok) return FEC_ERR_NODEV;
+  DecodePlan* plan = nullptr;
+  rc = get_decode_plan(ctx, k, r, &plan);
+  if (rc != FEC_OK) return rc;
+  hipStream_t s = pick_stream(ctx, stream);
+  qfec::ScatterLaunch a{};
+  a.g.addrs = d_shard_addrs;
+  a.g.groups = G;
+  a.g.k = k;
+  a.g.r = r;
+  a.g.P = P;
+  a.g.status = d_status;
+  a.g.masks_out = d_masks_out;
+  a.g.codebook = plan->codebook.as<uint8_t>();
+  a.g.binom = ctx->d_binom.as<uint64_t>();
+  a.g.meta = level_meta(plan->layout, r);
+  a.lens = d_shard_lens;
+  a.dests = d_dest_addrs;
+  // record offsets: the caller stream's workspace, as the gather calls'; behind them the symbol
+  // lengths the kernel cuts its stores at, when there is a length table and the caller asks for none
+  const bool own_symlen = d_shard_lens != nullptr && d_symbol_len_out == nullptr;
+  void* ws = nullptr;
+  QFEC_HIP(stream_workspace(ctx, s, (own_symlen ? 2 : 1) * G * sizeof(uint32_t), &ws));
+  a.g.rec_off = static_cast<uint32_t*>(ws);
+  a.symlen = own_symlen ? a.g.rec_off + G : d_symbol_len_out;
+  QFEC_HIP(qfec::launch_recover_scatter(a, s));
+  return FEC_OK;
+}
+
+QFEC_EXPORT int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
+                                           const uint32_t* d_shard_lens, const uint64_t* d_dest_addrs, uint64_t G,
+                                           uint32_t k, uint32_t r, uint32_t P, uint8_t* d_status,
+                                           uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream) {
+  g_last_error.clear();
+  return record_ctx_error(ctx, fec_recover_scatter_rs_dev_impl(ctx, d_shard_addrs, d_shard_lens, d_dest_addrs, G, k, r, P,
+                                                               d_status, d_masks_out, d_symbol_len_out, stream));
+}
+
 static int fec_decode_prepare_impl(FECEncoderCtx* ctx, uint32_t k, uint32_t r, uint64_t* bytes_out) {
   if (!ctx) return FEC_ERR_NULL;
   int rc = check_shape(1, k, r, 1, true);

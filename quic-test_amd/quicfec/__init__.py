@@ -56,6 +56,7 @@ HIP_SYMBOLS = (
     "fec_recover_batch_rs_dev_packed", "fec_coalesce_stats", "fec_coalesce_stats_sized",
     "fec_recover_gather_rs_dev", "fec_encode_gather_rs_dev",
     "fec_recover_gather_var_rs_dev", "fec_encode_gather_var_rs_dev",
+    "fec_recover_scatter_rs_dev",
 )
 
 
@@ -152,6 +153,7 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
         "fec_encode_gather_rs_dev": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
         "fec_recover_gather_var_rs_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
         "fec_encode_gather_var_rs_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
+        "fec_recover_scatter_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -349,6 +351,19 @@ class Context:
         rc = self.lib.fec_encode_gather_var_rs_dev(self.handle, opt(d_packet_addrs), opt(d_packet_lens), num_groups, k, r,
                                                    packet_size, opt(d_parity), opt(d_symbol_len_out), stream)
         _check(rc, "fec_encode_gather_var_rs_dev", self.lib)
+
+    def recover_scatter_dev(self, d_shard_addrs, d_shard_lens, d_dest_addrs, num_groups: int, k: int, r: int,
+                            packet_size: int, d_status=None, d_masks_out=None, d_symbol_len_out=None,
+                            stream: Optional[int] = None) -> None:
+        """recover_gather_var_dev (d_shard_lens None: recover_gather_dev) with a table of destinations
+        instead of an output buffer: d_dest_addrs holds num_groups*k absolute device addresses (u64), and
+        data shard j of group g, if the call rebuilds it, is written at entry [g*k + j], exactly the
+        group's symbol length of it; an entry of 0 = not wanted.  Every other entry is ignored."""
+        opt = lambda t: _ptr(t) if t is not None else None   # noqa: E731
+        rc = self.lib.fec_recover_scatter_rs_dev(self.handle, opt(d_shard_addrs), opt(d_shard_lens), opt(d_dest_addrs),
+                                                 num_groups, k, r, packet_size, opt(d_status), opt(d_masks_out),
+                                                 opt(d_symbol_len_out), stream)
+        _check(rc, "fec_recover_scatter_rs_dev", self.lib)
 
     def decode_prepare(self, k: int, r: int) -> int:
         n = ctypes.c_uint64(0)
@@ -591,6 +606,8 @@ LAUNCH_FORMS = {1: "encode_v16", 2: "encode_bits", 3: "encode_bytes", 4: "classi
 GATHER_LAUNCH_FORMS = {18: "classify_gather", 19: "recover_gather"}
 # the variable-length address-table kernels (csrc/fec_gather_var.hip; GatherVarLaunchForm), again their own
 GATHER_VAR_LAUNCH_FORMS = {20: "classify_gather_var", 21: "recover_gather_var", 22: "encode_gather_var"}
+# the scatter recover's kernels (csrc/fec_scatter.hip; ScatterLaunchForm), again their own
+SCATTER_LAUNCH_FORMS = {23: "classify_scatter", 24: "recover_scatter"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -618,6 +635,8 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
     for row in buf[:seen]:
         rec = dict(zip(LAUNCH_FIELDS, (int(x) for x in row)))
         form = rec["form"]
-        rec["form"] = LAUNCH_FORMS.get(form, GATHER_LAUNCH_FORMS.get(form, GATHER_VAR_LAUNCH_FORMS.get(form, form)))
+        for names in (LAUNCH_FORMS, GATHER_LAUNCH_FORMS, GATHER_VAR_LAUNCH_FORMS, SCATTER_LAUNCH_FORMS):
+            if form in names:
+                rec["form"] = names[form]
         out.append(rec)
     return out
