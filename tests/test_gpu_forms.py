@@ -720,7 +720,9 @@ NOT_LAUNCHED_HERE = {
     "decode_tiled k=20 r=5 (both layouts)": "auto leaves k=20 r=5 to the LDS-table fused form; only a probe's variant selects it",
     "encode_bits k=10 r=3 (both)": "only with QUICFEC_ENCODE_BITS=1 (tests/test_gpu_bits.py)",
     "encode_v16 runtime k, OFF=1 and OFF=3, and the row counts not used here": "u32 offsets reach the library only "
-        "through the legacy call (k=10 r=1, its own instantiation); OFF=3 is the coalescer's (tests/test_gpu_coalesce*.py)",
+        "through the legacy call (k=10 r=1, its own instantiation); OFF=3 is the coalescer's (tests/test_gpu_coalesce*.py) "
+        "and the address-table encode's (tests/test_gpu_gather.py; tests/test_gpu_address_limits.py runs its passes of 1, 7 "
+        "and 8 rows: k=63 r=1, k=1 r=63, k=32 r=32, k=48 r=16, k=12 r=9)",
     "encode_bytes OFF=1..3": "gathered packets shorter than 16 B (tests/test_gpu_parity.py offsets cases)",
     "rows_scan_blocks / rows_write<false>": "past 4096 prefix blocks or QUICFEC_ROWS_DIRECT_BLOCKS (tests/test_gpu_packed.py)",
     "fill, copy, legacy_server": "not dispatch forms; covered by their own tests",
