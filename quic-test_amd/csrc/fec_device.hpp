@@ -1,5 +1,6 @@
 // fec_device.hpp — the device code shared by the kernel translation units (fec_kernels.hip,
-// fec_gather.hip, fec_gather_var.hip, fec_scatter.hip).  First the small pieces: the coefficient table entry,
+// fec_gather.hip, fec_gather_var.hip, fec_scatter.hip; what only the three address-table units
+// share is fec_table.hpp's).  First the small pieces: the coefficient table entry,
 // byte-aligned packet loads and stores under a memory policy, the GF(2^8) product of a dword, the
 // selector split of a dword (SelN / sel_split), record bytes and the workgroup order.  Then the
 // record-addressed decode, stated once:

@@ -3,16 +3,18 @@
 // group (data shards, then parity rows; 0 = lost), instead of contiguous data / parity buffers
 // and erasure masks.
 //
-//  * classify_gather: forms each group's erasure mask from its table entries (bit s set where
-//    entry s is 0); the status byte and the codebook record come from classify_mask, the rule
-//    `classify` (fec_kernels.hip) applies to a given mask.
+//  * classify_table<Lens::kNone> (fec_table.hpp; the launch trace's classify_gather): forms each
+//    group's erasure mask from its table entries (bit s set where entry s is 0); the status byte
+//    and the codebook record come from classify_mask, the rule `classify` (fec_kernels.hip)
+//    applies to a given mask.
 //  * recover_gather<K, MAXE, POL>: one wave per group, record-addressed like decode_wave.  The
 //    base address of the record's survivor s is the group's table entry of that shard id, fetched
 //    once per group (compile-time k: scalar loads into SGPRs; runtime k: a per-wave LDS slice)
 //    and handed to decode_walk as its survivor functor; the rebuilt rows go to the compact slot
 //    layout, out + (g * r + m) * P (kCompactOut).
-// The rule, the record header, the piece rebuild and the walk are fec_device.hpp's; this file
-// holds only what the address table adds.
+// The rule, the record header, the piece rebuild and the walk are fec_device.hpp's, the classify
+// scan and the table-entry pointer fec_table.hpp's; this file holds only what the address table
+// adds to the recover.
 //
 // Shards may have any byte alignment (unaligned 16-B / 4-B global access, as in fec_kernels.hip)
 // and P >= 16.  A lost shard's entry and a parity row the decode rule does not use are never
@@ -25,47 +27,10 @@
 #include "fec_kernels.hpp"
 #include "fec_knobs.hpp"
 #include "fec_launch.hpp"
+#include "fec_table.hpp"
 
 namespace qfec {
 namespace {
-
-// Workgroup of 256 lanes = 256 consecutive groups.  The groups' table entries are one
-// contiguous run, read by consecutive lanes; a zero entry sets its bit in the group's mask in
-// LDS.  Lane t then classifies group t (classify_mask).
-__global__ __launch_bounds__(256) void classify_gather(const uint64_t* __restrict__ addrs, uint64_t groups,
-                                                       uint32_t k, uint32_t r,
-                                                       const uint64_t* __restrict__ binom, LevelMeta meta,
-                                                       uint32_t* __restrict__ rec_off,
-                                                       uint8_t* __restrict__ status,
-                                                       uint64_t* __restrict__ masks_out) {
-  __shared__ unsigned long long lost[256];
-  const uint64_t g0 = static_cast<uint64_t>(blockIdx.x) * 256u;
-  const uint32_t gn = groups - g0 < 256u ? static_cast<uint32_t>(groups - g0) : 256u;
-  const uint32_t n = k + r;
-  lost[threadIdx.x] = 0;
-  __syncthreads();
-  const uint64_t* __restrict__ tab = addrs + g0 * n;
-  const uint32_t entries = gn * n;  // at most 256 * 64
-  for (uint32_t i = threadIdx.x; i < entries; i += 256u) {
-    if (tab[i] == 0) atomicOr(&lost[i / n], 1ull << (i % n));
-  }
-  __syncthreads();
-  if (threadIdx.x >= gn) return;
-  const uint64_t g = g0 + threadIdx.x;
-  const uint64_t m = lost[threadIdx.x];
-  const Classified c = classify_mask(m, k, r, binom, meta);
-  rec_off[g] = c.rec;
-  if (status) status[g] = c.status;
-  if (masks_out) masks_out[g] = m;
-}
-
-// A table entry as a packet pointer.  The entry is cast to a global-memory pointer first, so the
-// loads through it are global loads; a pointer made straight from the integer would be generic
-// (flat loads, which also count against the LDS / scalar counter).
-__device__ __forceinline__ const uint8_t* shard_ptr(uint64_t addr) {
-  typedef const __attribute__((address_space(1))) uint8_t* global_u8p;
-  return (const uint8_t*)reinterpret_cast<global_u8p>(addr);
-}
 
 // One wave per group (4 per workgroup).  K > 0: compile-time k, one pass of MAXE = r rows, the k
 // survivor addresses in SGPRs.  K = 0: runtime k, rows [m0, m0 + MAXE) per launch, the addresses
@@ -109,35 +74,17 @@ __global__ __launch_bounds__(256) void recover_gather(const uint64_t* __restrict
   }
 }
 
-hipError_t run_classify_gather(const GatherLaunch& a, hipStream_t s) {
-  const uint64_t n = a.k + a.r;
-  return for_chunks(a.groups, max_launch_threads(), [&](uint64_t g0, uint64_t gn) {
-    trace_launch(launch_record(static_cast<int64_t>(GatherLaunchForm::kClassifyGather), blocks_for(gn), 256, g0, gn));
-    hipLaunchKernelGGL(classify_gather, dim3(blocks_for(gn)), dim3(256), 0, s, a.addrs + g0 * n, gn, a.k, a.r,
-                       a.binom, a.meta, a.rec_off + g0, a.status ? a.status + g0 : nullptr,
-                       a.masks_out ? a.masks_out + g0 : nullptr);
-  });
-}
-
-// Wave-per-group launches chunk their groups by whole workgroups, like the decodes.
 template <int K, int MAXE, int POL>
 hipError_t run_recover_gather(const GatherLaunch& a, hipStream_t s) {
-  const uint32_t passes = (a.r + MAXE - 1) / MAXE;  // e <= r
   const uint64_t n = a.k + a.r;
-  for (uint32_t p = 0; p < passes; ++p) {
-    const uint32_t m0 = p * MAXE;
-    const hipError_t e = for_chunks(a.groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
-      const uint64_t bn = (gn + 3) / 4;
-      LaunchRecord t = launch_record(static_cast<int64_t>(GatherLaunchForm::kRecoverGather), bn, 256, g0, gn);
-      t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
-      trace_launch(t);
-      hipLaunchKernelGGL((recover_gather<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
-                         a.addrs + g0 * n, a.rec_off + g0, a.codebook, gn, a.P, a.k, a.r, m0,
-                         a.out + g0 * a.r * static_cast<uint64_t>(a.P), static_cast<uint32_t>(kDecodeWaveXcdSwizzle));
-    });
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_wave_passes(a.groups, a.r, MAXE, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
+    LaunchRecord t = launch_record(static_cast<int64_t>(GatherLaunchForm::kRecoverGather), bn, 256, g0, gn);
+    t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
+    trace_launch(t);
+    hipLaunchKernelGGL((recover_gather<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
+                       a.addrs + g0 * n, a.rec_off + g0, a.codebook, gn, a.P, a.k, a.r, m0,
+                       a.out + g0 * a.r * static_cast<uint64_t>(a.P), static_cast<uint32_t>(kDecodeWaveXcdSwizzle));
+  });
 }
 
 }  // namespace
@@ -153,7 +100,8 @@ hipError_t launch_recover_gather(const GatherLaunch& a, hipStream_t s) {
   QFEC_GATHER_FORMS(QFEC_GATHER)
 #undef QFEC_GATHER
   if (run == nullptr) return hipErrorNotSupported;
-  const hipError_t e = run_classify_gather(a, s);
+  const hipError_t e =
+      run_classify_table<Lens::kNone>(a, nullptr, nullptr, static_cast<int64_t>(GatherLaunchForm::kClassifyGather), s);
   return e != hipSuccess ? e : run(a, s);
 }
 

@@ -3,9 +3,10 @@
 // (g, s) is the bytes [0, min(len, P)) at its address followed by zeros up to P; no byte at or
 // past addr + len is read, and an entry of length 0 is never dereferenced.
 //
-//  * classify_gather_var: classify_gather plus the symbol length -- the lanes that scan a
-//    workgroup's table entries read the lengths too and keep each group's largest min(len, P)
-//    over its present entries in LDS beside the mask.
+//  * classify_table<Lens::kGiven> (fec_table.hpp; the launch trace's classify_gather_var): the
+//    classify scan plus the symbol length -- the lanes that scan a workgroup's table entries read
+//    the lengths too and keep each group's largest min(len, P) over its present entries in LDS
+//    beside the mask.
 //  * recover_gather_var<K, MAXE, POL>: one wave per group, record-addressed like recover_gather.
 //    The survivors' lengths are fetched once per group beside their addresses (compile-time k:
 //    scalar loads into SGPRs; runtime k: a second per-wave LDS slice).  A pass of the walk that
@@ -15,7 +16,9 @@
 //  * encode_gather_var<0, R, FIRST>: one lane per 16-B column of a group, runtime k, rows
 //    [row0, row0 + R) per launch; every packet load is masked by its length, address 0 (absent)
 //    contributes zeros; the lane of column 0 of the first pass writes the group's symbol length.
-// The rule, the record header, the piece rebuild and the GF(2^8) product are fec_device.hpp's.
+// The rule, the record header, the piece rebuild and the GF(2^8) product are fec_device.hpp's;
+// the classify scan, the table-entry pointer, the masked piece load (load_masked) and the
+// survivor functors (VarSurvivors, VarSurvivorsLds) are fec_table.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -24,89 +27,11 @@
 #include "fec_kernels.hpp"
 #include "fec_knobs.hpp"
 #include "fec_launch.hpp"
+#include "fec_table.hpp"
 #include "fec_varlen.hpp"
 
 namespace qfec {
 namespace {
-
-// A table entry as a packet pointer: cast to a global-memory pointer first, so the loads through
-// it are global loads (as fec_gather.hip's).
-__device__ __forceinline__ const uint8_t* shard_ptr(uint64_t addr) {
-  typedef const __attribute__((address_space(1))) uint8_t* global_u8p;
-  return (const uint8_t*)reinterpret_cast<global_u8p>(addr);
-}
-
-__device__ __forceinline__ uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
-
-// The piece at `off` of the shard (p, len): var_load over the form's loads.
-template <int NW, int POL>
-__device__ __forceinline__ void load_masked(const uint8_t* p, uint32_t off, uint32_t len, uint32_t (&v)[NW]) {
-  var_load<NW>(
-      p, off, len, v, [](const uint8_t* q, uint32_t(&w)[NW]) { ldw<NW, POL>(q, w); },
-      [](const uint8_t* q) { return *q; });
-}
-
-// Workgroup of 256 lanes = 256 consecutive groups, as classify_gather; `symlen` beside `lost`.
-__global__ __launch_bounds__(256) void classify_gather_var(const uint64_t* __restrict__ addrs,
-                                                           const uint32_t* __restrict__ lens, uint64_t groups,
-                                                           uint32_t k, uint32_t r, uint32_t P,
-                                                           const uint64_t* __restrict__ binom, LevelMeta meta,
-                                                           uint32_t* __restrict__ rec_off,
-                                                           uint8_t* __restrict__ status,
-                                                           uint64_t* __restrict__ masks_out,
-                                                           uint32_t* __restrict__ symlen_out) {
-  __shared__ unsigned long long lost[256];
-  __shared__ uint32_t symlen[256];
-  const uint64_t g0 = static_cast<uint64_t>(blockIdx.x) * 256u;
-  const uint32_t gn = groups - g0 < 256u ? static_cast<uint32_t>(groups - g0) : 256u;
-  const uint32_t n = k + r;
-  lost[threadIdx.x] = 0;
-  symlen[threadIdx.x] = 0;
-  __syncthreads();
-  const uint64_t* __restrict__ tab = addrs + g0 * n;
-  const uint32_t* __restrict__ ltab = lens + g0 * n;
-  const uint32_t entries = gn * n;  // at most 256 * 64
-  for (uint32_t i = threadIdx.x; i < entries; i += 256u) {
-    if (tab[i] == 0) {
-      atomicOr(&lost[i / n], 1ull << (i % n));  // a lost entry's length is ignored
-    } else {
-      atomicMax(&symlen[i / n], min_u32(ltab[i], P));
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x >= gn) return;
-  const uint64_t g = g0 + threadIdx.x;
-  const uint64_t m = lost[threadIdx.x];
-  const Classified c = classify_mask(m, k, r, binom, meta);
-  rec_off[g] = c.rec;
-  if (status) status[g] = c.status;
-  if (masks_out) masks_out[g] = m;
-  if (symlen_out) symlen_out[g] = symlen[threadIdx.x];
-}
-
-// The survivors of a group as decode_piece's functor, loading through the mask (`loads_piece`).
-// Compile-time k: bases and clamped lengths in SGPRs.
-template <int K>
-struct VarSurvivors {
-  using loads_piece = void;
-  const uint8_t* base[K];
-  uint32_t len[K];
-  template <int NW, int POL>
-  __device__ __forceinline__ void load(uint32_t s, uint32_t off, uint32_t (&v)[NW]) const {
-    load_masked<NW, POL>(base[s], off, len[s], v);
-  }
-};
-
-// Runtime k: addresses and clamped lengths in the wave's two LDS slices.
-struct VarSurvivorsLds {
-  using loads_piece = void;
-  const uint64_t* addr;
-  const uint32_t* len;
-  template <int NW, int POL>
-  __device__ __forceinline__ void load(uint32_t s, uint32_t off, uint32_t (&v)[NW]) const {
-    load_masked<NW, POL>(shard_ptr(addr[s]), off, len[s], v);
-  }
-};
 
 // decode_walk's walk with the choice per pass: a pass whose bytes [base, end) lie below
 // `minlen`, the shortest survivor (wave-uniform), takes `plain` (s -> base, unmasked loads: every
@@ -241,36 +166,18 @@ __global__ __launch_bounds__(256) void encode_gather_var(const uint64_t* __restr
   if (FIRST && col == 0 && symlen_out) symlen_out[g] = symlen;
 }
 
-hipError_t run_classify_gather_var(const GatherVarLaunch& v, hipStream_t s) {
-  const GatherLaunch& a = v.g;
-  const uint64_t n = a.k + a.r;
-  return for_chunks(a.groups, max_launch_threads(), [&](uint64_t g0, uint64_t gn) {
-    trace_launch(launch_record(static_cast<int64_t>(GatherVarLaunchForm::kClassifyGatherVar), blocks_for(gn), 256, g0, gn));
-    hipLaunchKernelGGL(classify_gather_var, dim3(blocks_for(gn)), dim3(256), 0, s, a.addrs + g0 * n, v.lens + g0 * n, gn,
-                       a.k, a.r, a.P, a.binom, a.meta, a.rec_off + g0, a.status ? a.status + g0 : nullptr,
-                       a.masks_out ? a.masks_out + g0 : nullptr, v.symlen_out ? v.symlen_out + g0 : nullptr);
-  });
-}
-
 template <int K, int MAXE, int POL>
 hipError_t run_recover_gather_var(const GatherVarLaunch& v, hipStream_t s) {
   const GatherLaunch& a = v.g;
-  const uint32_t passes = (a.r + MAXE - 1) / MAXE;  // e <= r
   const uint64_t n = a.k + a.r;
-  for (uint32_t p = 0; p < passes; ++p) {
-    const uint32_t m0 = p * MAXE;
-    const hipError_t e = for_chunks(a.groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
-      const uint64_t bn = (gn + 3) / 4;
-      LaunchRecord t = launch_record(static_cast<int64_t>(GatherVarLaunchForm::kRecoverGatherVar), bn, 256, g0, gn);
-      t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
-      trace_launch(t);
-      hipLaunchKernelGGL((recover_gather_var<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
-                         a.addrs + g0 * n, v.lens + g0 * n, a.rec_off + g0, a.codebook, gn, a.P, a.k, a.r, m0,
-                         a.out + g0 * a.r * static_cast<uint64_t>(a.P), static_cast<uint32_t>(kDecodeWaveXcdSwizzle));
-    });
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_wave_passes(a.groups, a.r, MAXE, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
+    LaunchRecord t = launch_record(static_cast<int64_t>(GatherVarLaunchForm::kRecoverGatherVar), bn, 256, g0, gn);
+    t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
+    trace_launch(t);
+    hipLaunchKernelGGL((recover_gather_var<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
+                       a.addrs + g0 * n, v.lens + g0 * n, a.rec_off + g0, a.codebook, gn, a.P, a.k, a.r, m0,
+                       a.out + g0 * a.r * static_cast<uint64_t>(a.P), static_cast<uint32_t>(kDecodeWaveXcdSwizzle));
+  });
 }
 
 template <int R, bool FIRST>
@@ -301,7 +208,8 @@ hipError_t launch_recover_gather_var(const GatherVarLaunch& a, hipStream_t s) {
   QFEC_GATHER_VAR_FORMS(QFEC_GATHER_VAR)
 #undef QFEC_GATHER_VAR
   if (run == nullptr) return hipErrorNotSupported;
-  const hipError_t e = run_classify_gather_var(a, s);
+  const hipError_t e = run_classify_table<Lens::kGiven>(
+      a.g, a.lens, a.symlen_out, static_cast<int64_t>(GatherVarLaunchForm::kClassifyGatherVar), s);
   return e != hipSuccess ? e : run(a, s);
 }
 

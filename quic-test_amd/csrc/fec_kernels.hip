@@ -2168,53 +2168,41 @@ hipError_t run_decode_bytes(const DecodeLaunch& a, hipStream_t s) {
   });
 }
 
-// The wave-per-group decodes (4 groups per workgroup, decode_fused's scan form more) chunk
-// their groups by whole workgroups: at most max_wave_blocks() of them per launch.
+// The wave-per-group decodes chunk their groups by whole workgroups, at most max_wave_blocks() of
+// them per launch: decode_v16 and decode_wave (4 groups per workgroup) through for_wave_passes
+// (fec_launch.hpp); decode_fused, whose scan forms take more groups per workgroup, in a loop of
+// its own.
 template <int K, int MAXE>
 hipError_t run_decode_v16(const DecodeLaunch& a, hipStream_t s) {
   const uint32_t cpp = (a.P + 15u) / 16u;
-  const uint32_t passes = (a.r + MAXE - 1) / MAXE;  // e <= r
-  for (uint32_t p = 0; p < passes; ++p) {
-    const uint32_t m0 = p * MAXE;
-    const hipError_t e = for_chunks(a.groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
-      const uint64_t bn = (gn + 3) / 4;
-      LaunchRecord t = launch_record(LaunchForm::kDecodeV16, bn, 256, g0, gn);
-      t.k = K, t.r = MAXE, t.aux = m0;
-      trace_launch(t);
-      hipLaunchKernelGGL((decode_v16<K, MAXE>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
-                         a.data + g0 * a.k * static_cast<uint64_t>(a.P),
-                         a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook,
-                         gn, cpp, a.P, a.k, a.r, m0);
-    });
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_wave_passes(a.groups, a.r, MAXE, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
+    LaunchRecord t = launch_record(LaunchForm::kDecodeV16, bn, 256, g0, gn);
+    t.k = K, t.r = MAXE, t.aux = m0;
+    trace_launch(t);
+    hipLaunchKernelGGL((decode_v16<K, MAXE>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
+                       a.data + g0 * a.k * static_cast<uint64_t>(a.P),
+                       a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook,
+                       gn, cpp, a.P, a.k, a.r, m0);
+  });
 }
 
 template <int K, int MAXE, int POL>
 hipError_t run_decode_wave(const DecodeLaunch& a, hipStream_t s) {
-  const uint32_t passes = (a.r + MAXE - 1) / MAXE;  // e <= r
   const uint32_t cap = occupancy_cap_lds(a.waves_per_cu ? a.waves_per_cu : knob(TestKnob::kDecodeWaves, kDecodeWavesPerCU), 4);
-  for (uint32_t p = 0; p < passes; ++p) {
-    const uint32_t m0 = p * MAXE;
+  return for_wave_passes(a.groups, a.r, MAXE, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
     // kLdsTabs: per-wave slice of whole 1 KiB wave-loads covering this pass's rows
     const uint32_t rows = a.r - m0 < MAXE ? a.r - m0 : MAXE;
     const uint32_t slice = (POL & kLdsTabs) != 0 ? (rows * a.k * 2u + 63u) / 64u * 1024u : 0u;
     const uint32_t smem = cap > 4 * slice ? cap : 4 * slice;
-    const hipError_t e = for_chunks(a.groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
-      const uint64_t bn = (gn + 3) / 4;
-      LaunchRecord t = launch_record(LaunchForm::kDecodeWave, bn, 256, g0, gn);
-      t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
-      trace_launch(t);
-      hipLaunchKernelGGL((decode_wave<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), smem, s,
-                         a.data + g0 * a.k * static_cast<uint64_t>(a.P),
-                         a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook, gn, a.P,
-                         a.k, a.r, m0, (a.out ? a.out : a.data) + g0 * ((POL & kCompactOut) != 0 ? a.r : a.k) * static_cast<uint64_t>(a.P), 0u,
-                         decode_swizzle(a, kDecodeWaveXcdSwizzle), slice);
-    });
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    LaunchRecord t = launch_record(LaunchForm::kDecodeWave, bn, 256, g0, gn);
+    t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
+    trace_launch(t);
+    hipLaunchKernelGGL((decode_wave<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), smem, s,
+                       a.data + g0 * a.k * static_cast<uint64_t>(a.P),
+                       a.parity + g0 * a.r * static_cast<uint64_t>(a.P), a.rec_off ? a.rec_off + g0 : nullptr, a.codebook, gn, a.P,
+                       a.k, a.r, m0, (a.out ? a.out : a.data) + g0 * ((POL & kCompactOut) != 0 ? a.r : a.k) * static_cast<uint64_t>(a.P), 0u,
+                       decode_swizzle(a, kDecodeWaveXcdSwizzle), slice);
+  });
 }
 
 template <int K, int MAXE, int POL, int NM, int NT, bool DIRECT = false, bool INLINE = DIRECT, int SCAN = 0>

@@ -1,5 +1,6 @@
 // fec_kernels.hpp — launch interface between the C-ABI shim (fec_shim.cpp) and the
-// gfx950 kernels (fec_kernels.hip).  Internal to libfec_hip.so.
+// gfx950 kernels (fec_kernels.hip; the address-table units fec_gather.hip, fec_gather_var.hip,
+// fec_scatter.hip with their shared fec_table.hpp).  Internal to libfec_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,14 +38,16 @@ constexpr int kDecodeWaveXcdSwizzle = 1;
 
 hipError_t launch_encode(const EncodeLaunch& a, hipStream_t s);
 hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s);
-// Recover from an address table (fec_gather.hip): classify_gather, then gather_form's recover_gather.
+// Recover from an address table (fec_gather.hip): the classify scan (fec_table.hpp classify_table,
+// one kernel template for the three table recovers, traced under each call's own classify form),
+// then gather_form's recover_gather.
 hipError_t launch_recover_gather(const GatherLaunch& a, hipStream_t s);
-// The same with a length per table entry (fec_gather_var.hip): classify_gather_var, then
+// The same with a length per table entry (fec_gather_var.hip): classify_table with the lengths, then
 // gather_var_form's recover_gather_var; and the encode from addresses and lengths, 0 = absent.
 hipError_t launch_recover_gather_var(const GatherVarLaunch& a, hipStream_t s);
 hipError_t launch_encode_gather_var(const GatherVarEncodeLaunch& a, hipStream_t s);
-// Recover from an address table into a table of destinations (fec_scatter.hip): classify_scatter,
-// then scatter_form's recover_scatter.
+// Recover from an address table into a table of destinations (fec_scatter.hip): classify_table
+// with a nullable length table, then scatter_form's recover_scatter.
 hipError_t launch_recover_scatter(const ScatterLaunch& a, hipStream_t s);
 // Packed recover rows: row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:

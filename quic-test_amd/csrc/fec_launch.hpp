@@ -1,5 +1,6 @@
 // fec_launch.hpp — what the host launchers of the kernel translation units (fec_kernels.hip,
-// fec_gather.hip) share: the per-launch limits with their test switches, the chunk walk and the
+// fec_gather.hip, fec_gather_var.hip, fec_scatter.hip) share: the per-launch limits with their
+// test switches, the chunk walk, the pass-and-chunk walk of the wave-per-group kernels and the
 // launch trace's record.  Host code only.
 #pragma once
 
@@ -58,6 +59,21 @@ hipError_t for_chunks(uint64_t n, uint64_t per, F launch) {
   for (uint64_t i0 = 0; i0 < n; i0 += per) {
     launch(i0, n - i0 < per ? n - i0 : per);
     const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// The launches of a wave-per-group kernel (4 groups per 256-lane workgroup) that rebuilds `maxe`
+// rows per pass: for every pass of rows [m0, m0 + maxe) below r (e <= r), all groups in chunks of
+// whole workgroups, at most max_wave_blocks() per launch; every chunk of a pass before the next
+// pass.  launch(first group, groups, workgroups, m0) traces and launches one chunk.
+template <typename F>
+hipError_t for_wave_passes(uint64_t groups, uint32_t r, uint32_t maxe, F launch) {
+  for (uint32_t m0 = 0; m0 < r; m0 += maxe) {
+    const hipError_t e = for_chunks(groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
+      launch(g0, gn, (gn + 3) / 4, m0);
+    });
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

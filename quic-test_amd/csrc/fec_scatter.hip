@@ -3,8 +3,9 @@
 // destinations says, exactly the group's symbol length L of it.  Destinations that are the holes
 // of the caller's arena give in-place gathered decode, destinations back to back packed output.
 //
-//  * classify_scatter: classify_gather_var with a nullable length table (NULL: every present shard
-//    has P bytes) -- the mask, the status, the codebook record and the symbol length of each group.
+//  * classify_table<Lens::kNullable> (fec_table.hpp; the launch trace's classify_scatter): the
+//    classify scan with a nullable length table (NULL: every present shard has P bytes) -- the
+//    mask, the status, the codebook record and the symbol length of each group.
 //  * recover_scatter<K, MAXE, POL, VAR>: one wave per group, record-addressed like recover_gather /
 //    recover_gather_var (VAR: with the length table).  The survivors' addresses (and lengths) are
 //    fetched once per group as there; so are the destinations of the rows of the pass, row m0 + m
@@ -12,7 +13,9 @@
 //    runtime k: a per-wave LDS slice).  The wave walks [0, L) instead of [0, P) (scatter_walk), so
 //    the rebuilt zeros past L are neither loaded for nor stored; VAR loads stay masked per shard
 //    (var_load).  Which bytes a lane stores is decided in fec_scatter_cut.hpp and nowhere else.
-// The rule, the record header, the piece rebuild and the GF(2^8) product are fec_device.hpp's.
+// The rule, the record header, the piece rebuild and the GF(2^8) product are fec_device.hpp's;
+// the classify scan, the table-entry pointers (shard_ptr, dest_ptr), the masked piece load and
+// the survivor functors are fec_table.hpp's.
 //
 // A lost shard's source entry, a parity row the rule does not use, and the destination entry of
 // any shard the call does not rebuild are never read.  A destination of 0 is not stored to.
@@ -26,94 +29,11 @@
 #include "fec_knobs.hpp"
 #include "fec_launch.hpp"
 #include "fec_scatter_cut.hpp"
+#include "fec_table.hpp"
 #include "fec_varlen.hpp"
 
 namespace qfec {
 namespace {
-
-// A table entry as a packet pointer: cast to a global-memory pointer first, so the accesses
-// through it are global loads / stores (as fec_gather.hip's).
-__device__ __forceinline__ const uint8_t* shard_ptr(uint64_t addr) {
-  typedef const __attribute__((address_space(1))) uint8_t* global_u8p;
-  return (const uint8_t*)reinterpret_cast<global_u8p>(addr);
-}
-
-__device__ __forceinline__ uint8_t* dest_ptr(uint64_t addr) {
-  typedef __attribute__((address_space(1))) uint8_t* global_u8p;
-  return (uint8_t*)reinterpret_cast<global_u8p>(addr);
-}
-
-__device__ __forceinline__ uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
-
-// The piece at `off` of the shard (p, len): var_load over the form's loads.
-template <int NW, int POL>
-__device__ __forceinline__ void load_masked(const uint8_t* p, uint32_t off, uint32_t len, uint32_t (&v)[NW]) {
-  var_load<NW>(
-      p, off, len, v, [](const uint8_t* q, uint32_t(&w)[NW]) { ldw<NW, POL>(q, w); },
-      [](const uint8_t* q) { return *q; });
-}
-
-// Workgroup of 256 lanes = 256 consecutive groups, as classify_gather_var; `lens` nullable.
-__global__ __launch_bounds__(256) void classify_scatter(const uint64_t* __restrict__ addrs,
-                                                        const uint32_t* __restrict__ lens, uint64_t groups,
-                                                        uint32_t k, uint32_t r, uint32_t P,
-                                                        const uint64_t* __restrict__ binom, LevelMeta meta,
-                                                        uint32_t* __restrict__ rec_off,
-                                                        uint8_t* __restrict__ status,
-                                                        uint64_t* __restrict__ masks_out,
-                                                        uint32_t* __restrict__ symlen_out) {
-  __shared__ unsigned long long lost[256];
-  __shared__ uint32_t symlen[256];
-  const uint64_t g0 = static_cast<uint64_t>(blockIdx.x) * 256u;
-  const uint32_t gn = groups - g0 < 256u ? static_cast<uint32_t>(groups - g0) : 256u;
-  const uint32_t n = k + r;
-  lost[threadIdx.x] = 0;
-  symlen[threadIdx.x] = 0;
-  __syncthreads();
-  const uint64_t* __restrict__ tab = addrs + g0 * n;
-  const uint32_t* __restrict__ ltab = lens ? lens + g0 * n : nullptr;
-  const uint32_t entries = gn * n;  // at most 256 * 64
-  for (uint32_t i = threadIdx.x; i < entries; i += 256u) {
-    if (tab[i] == 0) {
-      atomicOr(&lost[i / n], 1ull << (i % n));  // a lost entry's length is ignored
-    } else {
-      atomicMax(&symlen[i / n], ltab ? min_u32(ltab[i], P) : P);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x >= gn) return;
-  const uint64_t g = g0 + threadIdx.x;
-  const uint64_t m = lost[threadIdx.x];
-  const Classified c = classify_mask(m, k, r, binom, meta);
-  rec_off[g] = c.rec;
-  if (status) status[g] = c.status;
-  if (masks_out) masks_out[g] = m;
-  if (symlen_out) symlen_out[g] = symlen[threadIdx.x];
-}
-
-// The survivors of a group as decode_piece's functor, loading through the mask (`loads_piece`):
-// fec_gather_var.hip's.  Compile-time k: bases and clamped lengths in SGPRs.
-template <int K>
-struct VarSurvivors {
-  using loads_piece = void;
-  const uint8_t* base[K];
-  uint32_t len[K];
-  template <int NW, int POL>
-  __device__ __forceinline__ void load(uint32_t s, uint32_t off, uint32_t (&v)[NW]) const {
-    load_masked<NW, POL>(base[s], off, len[s], v);
-  }
-};
-
-// Runtime k: addresses and clamped lengths in the wave's two LDS slices.
-struct VarSurvivorsLds {
-  using loads_piece = void;
-  const uint64_t* addr;
-  const uint32_t* len;
-  template <int NW, int POL>
-  __device__ __forceinline__ void load(uint32_t s, uint32_t off, uint32_t (&v)[NW]) const {
-    load_masked<NW, POL>(shard_ptr(addr[s]), off, len[s], v);
-  }
-};
 
 // decode_piece's destination functor: rows(m) is the destination of row m0 + m (nullptr: not
 // wanted).  BYTES: the byte-wise pass of L < 4.  The stores are fec_scatter_cut.hpp's.
@@ -246,39 +166,19 @@ __global__ __launch_bounds__(256) void recover_scatter(const uint64_t* __restric
   }
 }
 
-hipError_t run_classify_scatter(const ScatterLaunch& v, hipStream_t s) {
-  const GatherLaunch& a = v.g;
-  const uint64_t n = a.k + a.r;
-  return for_chunks(a.groups, max_launch_threads(), [&](uint64_t g0, uint64_t gn) {
-    trace_launch(launch_record(static_cast<int64_t>(ScatterLaunchForm::kClassifyScatter), blocks_for(gn), 256, g0, gn));
-    hipLaunchKernelGGL(classify_scatter, dim3(blocks_for(gn)), dim3(256), 0, s, a.addrs + g0 * n,
-                       v.lens ? v.lens + g0 * n : nullptr, gn, a.k, a.r, a.P, a.binom, a.meta, a.rec_off + g0,
-                       a.status ? a.status + g0 : nullptr, a.masks_out ? a.masks_out + g0 : nullptr,
-                       v.symlen ? v.symlen + g0 : nullptr);
-  });
-}
-
-// Wave-per-group launches chunk their groups by whole workgroups, like the decodes.
 template <int K, int MAXE, int POL, bool VAR>
 hipError_t run_recover_scatter(const ScatterLaunch& v, hipStream_t s) {
   const GatherLaunch& a = v.g;
-  const uint32_t passes = (a.r + MAXE - 1) / MAXE;  // e <= r
   const uint64_t n = a.k + a.r;
-  for (uint32_t p = 0; p < passes; ++p) {
-    const uint32_t m0 = p * MAXE;
-    const hipError_t e = for_chunks(a.groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
-      const uint64_t bn = (gn + 3) / 4;
-      LaunchRecord t = launch_record(static_cast<int64_t>(ScatterLaunchForm::kRecoverScatter), bn, 256, g0, gn);
-      t.k = K, t.r = MAXE, t.first = VAR, t.pol = POL, t.aux = m0;
-      trace_launch(t);
-      hipLaunchKernelGGL((recover_scatter<K, MAXE, POL, VAR>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
-                         a.addrs + g0 * n, VAR ? v.lens + g0 * n : nullptr, v.dests + g0 * a.k, a.rec_off + g0,
-                         VAR ? v.symlen + g0 : nullptr, a.codebook, gn, a.P, a.k, a.r, m0,
-                         static_cast<uint32_t>(kDecodeWaveXcdSwizzle));
-    });
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_wave_passes(a.groups, a.r, MAXE, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
+    LaunchRecord t = launch_record(static_cast<int64_t>(ScatterLaunchForm::kRecoverScatter), bn, 256, g0, gn);
+    t.k = K, t.r = MAXE, t.first = VAR, t.pol = POL, t.aux = m0;
+    trace_launch(t);
+    hipLaunchKernelGGL((recover_scatter<K, MAXE, POL, VAR>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
+                       a.addrs + g0 * n, VAR ? v.lens + g0 * n : nullptr, v.dests + g0 * a.k, a.rec_off + g0,
+                       VAR ? v.symlen + g0 : nullptr, a.codebook, gn, a.P, a.k, a.r, m0,
+                       static_cast<uint32_t>(kDecodeWaveXcdSwizzle));
+  });
 }
 
 }  // namespace
@@ -295,7 +195,8 @@ hipError_t launch_recover_scatter(const ScatterLaunch& a, hipStream_t s) {
   QFEC_SCATTER_FORMS(QFEC_SCATTER)
 #undef QFEC_SCATTER
   if (run == nullptr) return hipErrorNotSupported;
-  const hipError_t e = run_classify_scatter(a, s);
+  const hipError_t e = run_classify_table<Lens::kNullable>(
+      a.g, a.lens, a.symlen, static_cast<int64_t>(ScatterLaunchForm::kClassifyScatter), s);
   return e != hipSuccess ? e : run(a, s);
 }
 

@@ -1684,22 +1684,28 @@ int check_gather_shape(const char* what, uint64_t G, uint32_t k, uint32_t r, uin
   return FEC_OK;
 }
 
-}  // namespace
+// The record-offset workspace step of the gather recovers, as a failure of it is reported.
+constexpr const char* kRecOffWorkspaceCall = "stream_workspace(ctx, s, G * sizeof(uint32_t), &ws)";
 
-static int fec_recover_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
-                                          uint32_t r, uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
-                                          uint64_t* d_masks_out, void* stream) {
-  if (!ctx || !d_shard_addrs || !d_rebuilt) {
-    set_error("gather recover: %s is NULL", !ctx ? "the context" : !d_shard_addrs ? "d_shard_addrs" : "d_rebuilt");
-    return FEC_ERR_NULL;
-  }
-  int rc = check_gather_shape("gather recover", G, k, r, P);
+// What the three table recovers do between their own NULL checks and their launch.  Refused
+// before any lock or device call: the shape, then a codebook past the cap (the sparse plan reads
+// masks back on the host; judged before a plan and its codebook are built).  Then, under the
+// context's lock and on its device: the decode plan, the stream, the launch fields every table
+// recover sets, and `ws_words` uint32_t per group of the caller stream's workspace (shared in
+// stream order with the other decodes), the first G of them the record offsets; `ws_call` is
+// the text a failure of that step reports (each call's message as it was: QFEC_HIP reports the
+// failing expression, and the calls wrote this one differently).  launch(a, s) adds the call's
+// own fields and launches, the lock still held.
+template <typename F>
+int table_recover_locked(const char* what, FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
+                         uint32_t r, uint32_t P, uint8_t* d_status, uint64_t* d_masks_out, void* stream,
+                         uint32_t ws_words, const char* ws_call, F launch) {
+  int rc = check_gather_shape(what, G, k, r, P);
   if (rc != FEC_OK) return rc;
-  // the sparse plan reads masks back on the host; judged before a plan (and its codebook) is built
   qfec::CodebookLayout layout;
   if (!qfec::codebook_layout(k, r, kCodebookCap, layout)) {
-    set_error("gather recover: the codebook of k=%u r=%u exceeds the %llu-byte cap (sparse-plan shape: use "
-              "fec_recover_batch_rs_dev)", k, r, static_cast<unsigned long long>(kCodebookCap));
+    set_error("%s: the codebook of k=%u r=%u exceeds the %llu-byte cap (sparse-plan shape: use "
+              "fec_recover_batch_rs_dev)", what, k, r, static_cast<unsigned long long>(kCodebookCap));
     return FEC_ERR_RANGE;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -1715,18 +1721,33 @@ static int fec_recover_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_
   a.k = k;
   a.r = r;
   a.P = P;
-  a.out = d_rebuilt;
   a.status = d_status;
   a.masks_out = d_masks_out;
   a.codebook = plan->codebook.as<uint8_t>();
   a.binom = ctx->d_binom.as<uint64_t>();
   a.meta = level_meta(plan->layout, r);
-  // record offsets: the caller stream's workspace, shared in stream order with the other decodes
   void* ws = nullptr;
-  QFEC_HIP(stream_workspace(ctx, s, G * sizeof(uint32_t), &ws));
+  const hipError_t we = stream_workspace(ctx, s, ws_words * G * sizeof(uint32_t), &ws);
+  if (we != hipSuccess) return hip_fail(we, ws_call);
   a.rec_off = static_cast<uint32_t*>(ws);
-  QFEC_HIP(qfec::launch_recover_gather(a, s));
-  return FEC_OK;
+  return launch(a, s);
+}
+
+}  // namespace
+
+static int fec_recover_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
+                                          uint32_t r, uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
+                                          uint64_t* d_masks_out, void* stream) {
+  if (!ctx || !d_shard_addrs || !d_rebuilt) {
+    set_error("gather recover: %s is NULL", !ctx ? "the context" : !d_shard_addrs ? "d_shard_addrs" : "d_rebuilt");
+    return FEC_ERR_NULL;
+  }
+  return table_recover_locked("gather recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out, stream, 1,
+                              kRecOffWorkspaceCall, [&](qfec::GatherLaunch& a, hipStream_t s) {
+                                a.out = d_rebuilt;
+                                QFEC_HIP(qfec::launch_recover_gather(a, s));
+                                return FEC_OK;
+                              });
 }
 
 QFEC_EXPORT int fec_recover_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
@@ -1770,41 +1791,16 @@ static int fec_recover_gather_var_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t
                                                                              : "d_rebuilt");
     return FEC_ERR_NULL;
   }
-  int rc = check_gather_shape("variable-length gather recover", G, k, r, P);
-  if (rc != FEC_OK) return rc;
-  qfec::CodebookLayout layout;
-  if (!qfec::codebook_layout(k, r, kCodebookCap, layout)) {
-    set_error("variable-length gather recover: the codebook of k=%u r=%u exceeds the %llu-byte cap (sparse-plan "
-              "shape: use fec_recover_batch_rs_dev)", k, r, static_cast<unsigned long long>(kCodebookCap));
-    return FEC_ERR_RANGE;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  DecodePlan* plan = nullptr;
-  rc = get_decode_plan(ctx, k, r, &plan);
-  if (rc != FEC_OK) return rc;
-  hipStream_t s = pick_stream(ctx, stream);
-  qfec::GatherVarLaunch a{};
-  a.g.addrs = d_shard_addrs;
-  a.g.groups = G;
-  a.g.k = k;
-  a.g.r = r;
-  a.g.P = P;
-  a.g.out = d_rebuilt;
-  a.g.status = d_status;
-  a.g.masks_out = d_masks_out;
-  a.g.codebook = plan->codebook.as<uint8_t>();
-  a.g.binom = ctx->d_binom.as<uint64_t>();
-  a.g.meta = level_meta(plan->layout, r);
-  a.lens = d_shard_lens;
-  a.symlen_out = d_symbol_len_out;
-  // record offsets: the caller stream's workspace, as the fixed-length call's
-  void* ws = nullptr;
-  QFEC_HIP(stream_workspace(ctx, s, G * sizeof(uint32_t), &ws));
-  a.g.rec_off = static_cast<uint32_t*>(ws);
-  QFEC_HIP(qfec::launch_recover_gather_var(a, s));
-  return FEC_OK;
+  return table_recover_locked("variable-length gather recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out,
+                              stream, 1, kRecOffWorkspaceCall, [&](qfec::GatherLaunch& g, hipStream_t s) {
+                                g.out = d_rebuilt;
+                                qfec::GatherVarLaunch a{};
+                                a.g = g;
+                                a.lens = d_shard_lens;
+                                a.symlen_out = d_symbol_len_out;
+                                QFEC_HIP(qfec::launch_recover_gather_var(a, s));
+                                return FEC_OK;
+                              });
 }
 
 QFEC_EXPORT int fec_recover_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
@@ -1867,43 +1863,21 @@ static int fec_recover_scatter_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d
                                                               : "d_dest_addrs (the destination table)");
     return FEC_ERR_NULL;
   }
-  int rc = check_gather_shape("scatter recover", G, k, r, P);
-  if (rc != FEC_OK) return rc;
-  qfec::CodebookLayout layout;
-  if (!qfec::codebook_layout(k, r, kCodebookCap, layout)) {
-    set_error("scatter recover: the codebook of k=%u r=%u exceeds the %llu-byte cap (sparse-plan shape: use "
-              "fec_recover_batch_rs_dev)", k, r, static_cast<unsigned long long>(kCodebookCap));
-    return FEC_ERR_RANGE;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  DecodePlan* plan = nullptr;
-  rc = get_decode_plan(ctx, k, r, &plan);
-  if (rc != FEC_OK) return rc;
-  hipStream_t s = pick_stream(ctx, stream);
-  qfec::ScatterLaunch a{};
-  a.g.addrs = d_shard_addrs;
-  a.g.groups = G;
-  a.g.k = k;
-  a.g.r = r;
-  a.g.P = P;
-  a.g.status = d_status;
-  a.g.masks_out = d_masks_out;
-  a.g.codebook = plan->codebook.as<uint8_t>();
-  a.g.binom = ctx->d_binom.as<uint64_t>();
-  a.g.meta = level_meta(plan->layout, r);
-  a.lens = d_shard_lens;
-  a.dests = d_dest_addrs;
-  // record offsets: the caller stream's workspace, as the gather calls'; behind them the symbol
-  // lengths the kernel cuts its stores at, when there is a length table and the caller asks for none
+  // behind the record offsets the symbol lengths the kernel cuts its stores at, when there is a
+  // length table and the caller asks for none
   const bool own_symlen = d_shard_lens != nullptr && d_symbol_len_out == nullptr;
-  void* ws = nullptr;
-  QFEC_HIP(stream_workspace(ctx, s, (own_symlen ? 2 : 1) * G * sizeof(uint32_t), &ws));
-  a.g.rec_off = static_cast<uint32_t*>(ws);
-  a.symlen = own_symlen ? a.g.rec_off + G : d_symbol_len_out;
-  QFEC_HIP(qfec::launch_recover_scatter(a, s));
-  return FEC_OK;
+  return table_recover_locked("scatter recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out, stream,
+                              own_symlen ? 2 : 1,
+                              "stream_workspace(ctx, s, (own_symlen ? 2 : 1) * G * sizeof(uint32_t), &ws)",
+                              [&](qfec::GatherLaunch& g, hipStream_t s) {
+                                qfec::ScatterLaunch a{};
+                                a.g = g;
+                                a.lens = d_shard_lens;
+                                a.dests = d_dest_addrs;
+                                a.symlen = own_symlen ? g.rec_off + G : d_symbol_len_out;
+                                QFEC_HIP(qfec::launch_recover_scatter(a, s));
+                                return FEC_OK;
+                              });
 }
 
 QFEC_EXPORT int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
