@@ -238,6 +238,43 @@ int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs
                                uint8_t* d_status, uint64_t* d_masks_out, uint32_t* d_symbol_len_out,
                                void* stream);
 
+/* ---- scatter encode: parity rows written to a table of destinations ----
+ * The gather encodes above write every parity row into a library-shaped buffer as a full P-byte
+ * row at (g*r + i)*P.  This call writes each parity row where the caller says, and only the bytes
+ * the repair payload has (the reference's repair packet carries the group's symbol length of
+ * it), so a sender that keeps its packets in a device arena needs no second pass to move the
+ * payloads behind their wire headers.
+ *   - Inputs: d_packet_addrs (num_groups*k u64 addresses) and d_packet_lens (u32, indexed alike)
+ *     exactly as fec_encode_gather_var_rs_dev: a length above P is clamped to P; a packet is its
+ *     bytes [0, min(len, P)) followed by zeros; no byte at or past address + len is read; a
+ *     present packet of length 0 is never dereferenced; address 0 means absent (the flush of a
+ *     partial group) and counts as all zero.  d_packet_lens == NULL: every present packet has P
+ *     bytes, the inputs of fec_encode_gather_rs_dev; address 0 is still "absent".
+ *   - d_symbol_len_out (nullable, u32 per group), written for every group: L_g, the largest
+ *     min(len, P) over the group's present packets (P without a length table when any packet is
+ *     present), 0 when none is present -- the length of the group's repair payloads.
+ *   - d_dest_addrs: num_groups*r absolute device addresses (u64), entry [g*r + i] for parity row i
+ *     of group g, any byte alignment.  The call writes exactly L_g bytes of the row there (the
+ *     row's bytes past L_g are zero by construction): no byte before the address or at or past
+ *     address + L_g is written, so a repair payload may sit between a header and the next live
+ *     packet.  An entry of 0 means "not wanted": that row is not stored, the group's other rows
+ *     are (a sender whose plan is r rows may send fewer for some groups).
+ *   - L_g == 0 writes nothing and dereferences nothing.  This differs from the gather encodes,
+ *     which write all-zero rows for a group with no packet present.
+ *   - Destinations at d_parity + (g*r + i)*P with every length P give the gather encode's output;
+ *     destinations back to back give packed repair payloads.
+ *   - A destination range must not overlap any packet the call reads, in any group, nor another
+ *     destination range.
+ * Refused like the gather calls, with nothing launched or written: FEC_ERR_NULL for a NULL
+ * context, address table or destination table (the message names it); FEC_ERR_RANGE for
+ * k + r > 64, packet_size < 16, num_groups == 0 or >= 2^32.  There is no codebook cap (encode has
+ * none).  Asynchronous on `stream`, drained by fec_encoder_free; no new per-context state and no
+ * workspace: every lane derives L_g from the k lengths of its own group. */
+int fec_encode_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
+                              const uint32_t* d_packet_lens, const uint64_t* d_dest_addrs,
+                              uint64_t num_groups, uint32_t k, uint32_t r, uint32_t packet_size,
+                              uint32_t* d_symbol_len_out, void* stream);
+
 /* Expected share (0..1) of groups that lost data shards in this context's device-resident
  * decode calls, e.g. 1 - (1 - p)^k for iid loss p (the receiver knows its network profile;
  * satellite p = 0.01, k = 10: ~0.10).  Below 0.25 the decode checks several groups per

@@ -539,6 +539,49 @@ inline ScatterForm scatter_form(uint32_t k, uint32_t r, uint32_t P, bool var) {
   return f;
 }
 
+// ---- scatter encode (fec_encode_scatter_rs_dev, fec_scatter_encode.hip) ----
+// The packets' address table (with or without the length table) in, and a table of destinations
+// out: parity row i of group g goes to dests[g * r + i], exactly the group's symbol length of it
+// (fec_scatter_encode_cut.hpp); 0 = not wanted.
+struct ScatterEncodeLaunch {
+  const uint64_t* addrs;     // groups * k absolute device addresses, 0 = absent (counts as zeros)
+  const uint32_t* lens;      // nullable: groups * k readable bytes per packet; NULL = every present packet has P
+  const uint64_t* dests;     // groups * r absolute device addresses
+  uint64_t groups;
+  uint32_t k, r, P;
+  uint32_t* symlen_out;      // nullable
+  const void* tables;        // (r-1) x k CoefEntry (rows 1..r-1), device
+};
+
+// fec_encode_scatter_rs_dev: encode_scatter<0, R, FIRST, VAR> at runtime k for every shape, in
+// passes of up to kScatterEncodeRows parity rows (the variable-length gather encode's passes); the
+// first pass owns the XOR row and writes the symbol lengths.  VAR: with the length table.
+constexpr uint32_t kScatterEncodeRows = 8;
+constexpr int kScatterEncodePol = kNtStore;
+struct ScatterEncodeForm {
+  bool supported = false;  // false: P < 16, the call is refused
+  uint32_t passes = 0;     // pass p: rows [p * 8, min(r, p * 8 + 8)), FIRST = (p == 0)
+  bool VAR = false;        // loads masked by the length table
+};
+inline ScatterEncodeForm scatter_encode_form(uint32_t k, uint32_t r, uint32_t P, bool var) {
+  ScatterEncodeForm f;
+  if (P < kVecMinP) return f;
+  f.supported = true;
+  f.passes = (r + kScatterEncodeRows - 1) / kScatterEncodeRows;
+  f.VAR = var;
+  return f;
+}
+inline uint32_t scatter_encode_rows(uint32_t r, uint32_t pass) {
+  const uint32_t row0 = pass * kScatterEncodeRows;
+  return r - row0 < kScatterEncodeRows ? r - row0 : kScatterEncodeRows;
+}
+// The instantiations of encode_scatter, X(R, FIRST, VAR): every row count of a pass, as the first
+// pass and as a later one (r = 8 + R), without and with the length table.
+#define QFEC_SCATTER_ENCODE_ROWS(X, F, V) X(1, F, V) X(2, F, V) X(3, F, V) X(4, F, V) X(5, F, V) X(6, F, V) X(7, F, V) X(8, F, V)
+#define QFEC_SCATTER_ENCODE_FORMS(X)                                                           \
+  QFEC_SCATTER_ENCODE_ROWS(X, true, false) QFEC_SCATTER_ENCODE_ROWS(X, false, false)           \
+  QFEC_SCATTER_ENCODE_ROWS(X, true, true) QFEC_SCATTER_ENCODE_ROWS(X, false, true)
+
 // ---- encode ----
 enum class EncodeKernel : int { kBytes, kV16, kBits };
 

@@ -1,6 +1,6 @@
 // fec_kernels.hpp — launch interface between the C-ABI shim (fec_shim.cpp) and the
 // gfx950 kernels (fec_kernels.hip; the address-table units fec_gather.hip, fec_gather_var.hip,
-// fec_scatter.hip with their shared fec_table.hpp).  Internal to libfec_hip.so.
+// fec_scatter.hip, fec_scatter_encode.hip with their shared fec_table.hpp).  Internal to libfec_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,6 +49,9 @@ hipError_t launch_encode_gather_var(const GatherVarEncodeLaunch& a, hipStream_t 
 // Recover from an address table into a table of destinations (fec_scatter.hip): classify_table
 // with a nullable length table, then scatter_form's recover_scatter.
 hipError_t launch_recover_scatter(const ScatterLaunch& a, hipStream_t s);
+// Encode from an address table (with a nullable length table) into a table of destinations
+// (fec_scatter_encode.hip): scatter_encode_form's passes of encode_scatter.
+hipError_t launch_encode_scatter(const ScatterEncodeLaunch& a, hipStream_t s);
 // Packed recover rows: row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.

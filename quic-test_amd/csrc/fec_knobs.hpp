@@ -95,6 +95,12 @@ enum class ScatterLaunchForm : int64_t {
   kClassifyScatter = 23,
   kRecoverScatter = 24,  // LaunchRecord::first: 1 with a length table (VAR), 0 without
 };
+// The scatter encode's kernel (fec_scatter_encode.hip), numbered on in a list of its own
+// (fec_forms.hpp QFEC_SCATTER_ENCODE_FORMS); named by quicfec.SCATTER_ENCODE_LAUNCH_FORMS.
+enum class ScatterEncodeLaunchForm : int64_t {
+  kEncodeScatter = 25,  // LaunchRecord::first: this pass owns the XOR row; LaunchRecord::direct: 1
+                        // with a length table (VAR), 0 without
+};
 
 // One launch: 16 words, -1 where a field does not apply to the form.
 struct LaunchRecord {
@@ -106,14 +112,15 @@ struct LaunchRecord {
   int64_t off = -1;      // encode: OffsetKind of the instantiation
   int64_t first = -1;    // encode_v16: this pass owns the XOR row; recover_scatter: the length-table form
   int64_t pol = -1;      // memory policy / form bits (fec_forms.hpp kNtLoad .. kStageRows)
-  int64_t direct = -1;   // decode_fused: mask-addressed; rows_write: writes the total itself
+  int64_t direct = -1;   // decode_fused: mask-addressed; rows_write: writes the total itself;
+                         // encode_scatter: the length-table form
   int64_t scan = -1;     // decode_fused: groups per wave of the scan form (0: one wave per group)
   int64_t tile = -1;     // groups per workgroup of the tiled mappings, 0 = flat mapping
   int64_t grid = 0;      // workgroups
   int64_t block = 0;     // work items per workgroup
   int64_t first_item = 0;  // first group (fill / copy: first 16-B word or byte) of this launch
   int64_t items = 0;     // groups (fill / copy: words or bytes) of this launch
-  int64_t aux = -1;      // encode_v16, encode_gather_var: first parity row; decodes, recover_gather(_var), recover_scatter: first rebuilt row of the pass;
+  int64_t aux = -1;      // encode_v16, encode_gather_var, encode_scatter: first parity row; decodes, recover_gather(_var), recover_scatter: first rebuilt row of the pass;
                          // encode_bits: W; recover_runs: run-image bytes; fill / copy: bytes per
                          // work item
 };

@@ -1,5 +1,5 @@
 // fec_launch.hpp — what the host launchers of the kernel translation units (fec_kernels.hip,
-// fec_gather.hip, fec_gather_var.hip, fec_scatter.hip) share: the per-launch limits with their
+// fec_gather.hip, fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip) share: the per-launch limits with their
 // test switches, the chunk walk, the pass-and-chunk walk of the wave-per-group kernels and the
 // launch trace's record.  Host code only.
 #pragma once

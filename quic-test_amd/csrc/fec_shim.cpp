@@ -1889,6 +1889,48 @@ QFEC_EXPORT int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d
                                                                d_status, d_masks_out, d_symbol_len_out, stream));
 }
 
+// ---- the encode with a table of destinations (fec_scatter_encode.hip) ----
+static int fec_encode_scatter_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
+                                          const uint32_t* d_packet_lens, const uint64_t* d_dest_addrs, uint64_t G,
+                                          uint32_t k, uint32_t r, uint32_t P, uint32_t* d_symbol_len_out,
+                                          void* stream) {
+  if (!ctx || !d_packet_addrs || !d_dest_addrs) {
+    set_error("scatter encode: %s is NULL", !ctx              ? "the context"
+                                            : !d_packet_addrs ? "d_packet_addrs"
+                                                              : "d_dest_addrs (the destination table)");
+    return FEC_ERR_NULL;
+  }
+  int rc = check_gather_shape("scatter encode", G, k, r, P);
+  if (rc != FEC_OK) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard dg(ctx->device);
+  if (!dg.ok) return FEC_ERR_NODEV;
+  const void* tables = nullptr;
+  rc = get_encode_plan(ctx, k, r, &tables);
+  if (rc != FEC_OK) return rc;
+  qfec::ScatterEncodeLaunch a{};
+  a.addrs = d_packet_addrs;
+  a.lens = d_packet_lens;
+  a.dests = d_dest_addrs;
+  a.groups = G;
+  a.k = k;
+  a.r = r;
+  a.P = P;
+  a.symlen_out = d_symbol_len_out;
+  a.tables = tables;
+  QFEC_HIP(qfec::launch_encode_scatter(a, pick_stream(ctx, stream)));
+  return FEC_OK;
+}
+
+QFEC_EXPORT int fec_encode_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
+                                          const uint32_t* d_packet_lens, const uint64_t* d_dest_addrs, uint64_t G,
+                                          uint32_t k, uint32_t r, uint32_t P, uint32_t* d_symbol_len_out,
+                                          void* stream) {
+  g_last_error.clear();
+  return record_ctx_error(ctx, fec_encode_scatter_rs_dev_impl(ctx, d_packet_addrs, d_packet_lens, d_dest_addrs, G, k, r, P,
+                                                              d_symbol_len_out, stream));
+}
+
 static int fec_decode_prepare_impl(FECEncoderCtx* ctx, uint32_t k, uint32_t r, uint64_t* bytes_out) {
   if (!ctx) return FEC_ERR_NULL;
   int rc = check_shape(1, k, r, 1, true);

@@ -56,7 +56,7 @@ HIP_SYMBOLS = (
     "fec_recover_batch_rs_dev_packed", "fec_coalesce_stats", "fec_coalesce_stats_sized",
     "fec_recover_gather_rs_dev", "fec_encode_gather_rs_dev",
     "fec_recover_gather_var_rs_dev", "fec_encode_gather_var_rs_dev",
-    "fec_recover_scatter_rs_dev",
+    "fec_recover_scatter_rs_dev", "fec_encode_scatter_rs_dev",
 )
 
 
@@ -154,6 +154,7 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
         "fec_recover_gather_var_rs_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
         "fec_encode_gather_var_rs_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
         "fec_recover_scatter_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+        "fec_encode_scatter_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -364,6 +365,17 @@ class Context:
                                                  num_groups, k, r, packet_size, opt(d_status), opt(d_masks_out),
                                                  opt(d_symbol_len_out), stream)
         _check(rc, "fec_recover_scatter_rs_dev", self.lib)
+
+    def encode_scatter_dev(self, d_packet_addrs, d_packet_lens, d_dest_addrs, num_groups: int, k: int, r: int,
+                           packet_size: int, d_symbol_len_out=None, stream: Optional[int] = None) -> None:
+        """encode_gather_var_dev (d_packet_lens None: encode_gather_dev, address 0 still absent) with a
+        table of destinations instead of a parity buffer: d_dest_addrs holds num_groups*r absolute device
+        addresses (u64), and parity row i of group g is written at entry [g*r + i], exactly the group's
+        symbol length of it; an entry of 0 = not wanted.  A group with no packet present writes nothing."""
+        opt = lambda t: _ptr(t) if t is not None else None   # noqa: E731
+        rc = self.lib.fec_encode_scatter_rs_dev(self.handle, opt(d_packet_addrs), opt(d_packet_lens), opt(d_dest_addrs),
+                                                num_groups, k, r, packet_size, opt(d_symbol_len_out), stream)
+        _check(rc, "fec_encode_scatter_rs_dev", self.lib)
 
     def decode_prepare(self, k: int, r: int) -> int:
         n = ctypes.c_uint64(0)
@@ -608,6 +620,9 @@ GATHER_LAUNCH_FORMS = {18: "classify_gather", 19: "recover_gather"}
 GATHER_VAR_LAUNCH_FORMS = {20: "classify_gather_var", 21: "recover_gather_var", 22: "encode_gather_var"}
 # the scatter recover's kernels (csrc/fec_scatter.hip; ScatterLaunchForm), again their own
 SCATTER_LAUNCH_FORMS = {23: "classify_scatter", 24: "recover_scatter"}
+# the scatter encode's kernel (csrc/fec_scatter_encode.hip; ScatterEncodeLaunchForm), again its own;
+# `first` = the pass owns the XOR row, `direct` = the length-table form
+SCATTER_ENCODE_LAUNCH_FORMS = {25: "encode_scatter"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -635,7 +650,8 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
     for row in buf[:seen]:
         rec = dict(zip(LAUNCH_FIELDS, (int(x) for x in row)))
         form = rec["form"]
-        for names in (LAUNCH_FORMS, GATHER_LAUNCH_FORMS, GATHER_VAR_LAUNCH_FORMS, SCATTER_LAUNCH_FORMS):
+        for names in (LAUNCH_FORMS, GATHER_LAUNCH_FORMS, GATHER_VAR_LAUNCH_FORMS, SCATTER_LAUNCH_FORMS,
+                      SCATTER_ENCODE_LAUNCH_FORMS):
             if form in names:
                 rec["form"] = names[form]
         out.append(rec)
