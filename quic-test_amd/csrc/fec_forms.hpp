@@ -1,7 +1,8 @@
 // fec_forms.hpp — which kernel form a call runs: the launch descriptions, the lists of compiled
 // shapes and the rules that choose among them.  Host-only (no HIP include, no device code), so a
-// plain C++ program can ask for every packet size (tests/csrc/forms_dump.cpp).  The launchers of
-// fec_kernels.hip dispatch on what is decided here and expand the same lists.
+// plain C++ program can ask for every packet size (tests/csrc/forms_dump.cpp; for the address-table
+// calls tests/csrc/table_forms_dump.cpp).  The launchers of fec_kernels.hip and of the
+// address-table units dispatch on what is decided here and expand the same lists.
 #pragma once
 
 #include <cstdint>
@@ -402,47 +403,84 @@ inline PackedForm packed_form(const DecodeLaunch& a, const DecodeForm& f, long r
   return PackedForm::kPrefixFused;
 }
 
-// ---- recover from an address table (fec_recover_gather_rs_dev, fec_gather.hip) ----
-struct GatherLaunch {
+// ---- the address-table calls (fec_gather.hip, fec_gather_var.hip, fec_scatter.hip,
+// fec_scatter_encode.hip) ----
+// Shards wherever they are in device memory: a table of absolute addresses per group (0 = lost /
+// absent), optionally a u32 length per entry, indexed alike -- shard (g, s) is then the bytes
+// [0, min(len, P)) at its address, zeros up to P (fec_varlen.hpp) -- and optionally a table of
+// destinations instead of an output buffer, each written exactly the group's symbol length (the
+// largest min(len, P) of its present entries; fec_scatter_cut.hpp, fec_scatter_encode_cut.hpp).
+//
+// A recover (fec_recover_gather_rs_dev, fec_recover_gather_var_rs_dev, fec_recover_scatter_rs_dev).
+struct TableRecoverLaunch {
   const uint64_t* addrs;     // groups * (k + r) absolute device addresses, 0 = lost
+  const uint32_t* lens;      // groups * (k + r) readable bytes per entry, a lost entry's ignored: the
+                             // variable-length gather's; the scatter's, nullable (NULL = every present
+                             // shard has P); not read by the fixed-length gather
+  const uint64_t* dests;     // the scatter's: groups * k absolute device addresses, 0 = not wanted
   uint64_t groups;
   uint32_t k, r, P;
-  uint8_t* out;              // rebuilt row (g, m) at (g * r + m) * P
+  uint8_t* out;              // the gathers': rebuilt row (g, m) at (g * r + m) * P; not used by the scatter
   uint8_t* status;           // nullable
   uint64_t* masks_out;       // nullable: the erasure mask derived for each group
+  uint32_t* symlen;          // per group its symbol length, 0 when no entry is present.  The
+                             // variable-length gather's nullable output; the scatter's output or, when
+                             // the caller gives none and there is a length table, workspace (its kernel
+                             // reads it); not used by the fixed-length gather
   uint32_t* rec_off;         // workspace, one u32 per group
   const uint8_t* codebook;   // dense CoefEntry codebook (the one `classify` addresses), device
   const uint64_t* binom;     // device, 65 x 65
   LevelMeta meta;
 };
 
-// The compiled shapes of recover_gather, M(k, r), and its instantiations, X(K, MAXE, POL): a list
-// of their own, apart from the decode lists above.  Every form loads and stores non-temporally and
-// writes the compact slot layout, like the slot recover's mask-addressed form; runtime k takes
-// passes of 8 rows and multiplies by every coefficient (as the runtime-k decode_wave does).
+// An encode (fec_encode_gather_var_rs_dev, fec_encode_scatter_rs_dev).  Exactly one of `parity`
+// (the gather's) and `dests` (the scatter's) is set.
+struct TableEncodeLaunch {
+  const uint64_t* addrs;     // groups * k absolute device addresses, 0 = absent (counts as zeros)
+  const uint32_t* lens;      // groups * k readable bytes per packet: the gather's; the scatter's,
+                             // nullable (NULL = every present packet has P)
+  uint64_t groups;
+  uint32_t k, r, P;
+  uint8_t* parity;           // parity row (g, i) at (g * r + i) * P, full P-byte rows
+  const uint64_t* dests;     // groups * r absolute device addresses, 0 = not wanted
+  uint32_t* symlen_out;      // nullable
+  const void* tables;        // (r-1) x k CoefEntry (rows 1..r-1), device
+};
+
+// The compiled shapes of the table recovers, M(extra, k, r), and the instantiations of each of
+// their kernels (recover_gather, recover_gather_var, recover_scatter), X(extra, K, MAXE, POL) with
+// one extra argument (`~` for none): a list of their own, apart from the decode lists above.  Every
+// form loads and stores non-temporally and has the compact slot layout in POL, like the slot
+// recover's mask-addressed form (the scatter's rows go to the destination table whatever it says);
+// runtime k takes passes of 8 rows and multiplies by every coefficient (as the runtime-k
+// decode_wave does).
 #define QFEC_GATHER_SHAPES(M, ...) \
   M(__VA_ARGS__, 10, 3) M(__VA_ARGS__, 10, 2) M(__VA_ARGS__, 10, 1) M(__VA_ARGS__, 4, 2) M(__VA_ARGS__, 20, 5)
 constexpr int kGatherPol = kNtStore | kNtLoad | kCompactOut;
-#define QFEC_GATHER_FIXED(X, K, R) X(K, R, kGatherPol)
-#define QFEC_GATHER_FORMS(X) QFEC_GATHER_SHAPES(QFEC_GATHER_FIXED, X) X(0, 8, kGatherPol | kNoCoefBranch)
+#define QFEC_TABLE_RECOVER_FIXED(X, A, K, R) X(A, K, R, kGatherPol)
+#define QFEC_TABLE_RECOVER_FORMS(X, ...) \
+  QFEC_GATHER_SHAPES(QFEC_TABLE_RECOVER_FIXED, X, __VA_ARGS__) X(__VA_ARGS__, 0, 8, kGatherPol | kNoCoefBranch)
 #define QFEC_IS_PAIR(_, A, B) || (a == A && b == B)
 constexpr bool is_gather_shape(uint32_t a, uint32_t b) { return false QFEC_GATHER_SHAPES(QFEC_IS_PAIR, ~); }
 #undef QFEC_IS_PAIR
 
-struct GatherForm {
+struct TableRecoverForm {
   bool supported = false;  // false: P < 16, the call is refused
   int K = 0, MAXE = 0;     // template shape; runtime k as K = 0, MAXE = 8
   int POL = 0;
+  bool VAR = false;        // with a length table: loads masked by it (the scatter: stores cut at the symbol length)
 };
 
-// The form fec_recover_gather_rs_dev runs for (k, r, P): a classify_gather launch, then
-// recover_gather<K, MAXE, POL> in ceil(r / MAXE) passes.  The kernel walks the pieces of any
-// P >= 16 itself, so the size only decides whether the call is served.  Every form takes its
-// records from the dense CoefEntry codebook; k=20 r=5 too (no compact-codebook / LDS-table form).
-inline GatherForm gather_form(uint32_t k, uint32_t r, uint32_t P) {
-  GatherForm f;
+// The form a table recover runs for (k, r, P) with (var) or without a length table: a classify
+// launch, then the call's kernel <K, MAXE, POL> (the scatter's: <K, MAXE, POL, VAR>) in
+// ceil(r / MAXE) passes.  The kernels walk the pieces of any P >= 16 themselves, so the size only
+// decides whether the call is served, and the length table never chooses a shape.  Every form
+// takes its records from the dense CoefEntry codebook; k=20 r=5 too (no compact-codebook /
+// LDS-table form).
+inline TableRecoverForm table_recover_form(uint32_t k, uint32_t r, uint32_t P, bool var) {
+  TableRecoverForm f;
   if (P < kVecMinP) return f;
-  f.supported = true;
+  f.supported = true, f.VAR = var;
   if (is_gather_shape(k, r)) {
     f.K = static_cast<int>(k), f.MAXE = static_cast<int>(r), f.POL = kGatherPol;
   } else {
@@ -451,136 +489,40 @@ inline GatherForm gather_form(uint32_t k, uint32_t r, uint32_t P) {
   return f;
 }
 
-// ---- variable-length address tables (fec_recover_gather_var_rs_dev, fec_encode_gather_var_rs_dev;
-// fec_gather_var.hip) ----
-// The address table with a u32 length per entry, indexed alike: shard (g, s) is the bytes
-// [0, min(len, P)) at its address, zeros up to P (fec_varlen.hpp).
-struct GatherVarLaunch {
-  GatherLaunch g;            // as the fixed-length recover
-  const uint32_t* lens;      // groups * (k + r) readable bytes per entry; a lost entry's is ignored
-  uint32_t* symlen_out;      // nullable: per group the largest min(len, P) of its present entries
-};
-
-struct GatherVarEncodeLaunch {
-  const uint64_t* addrs;     // groups * k absolute device addresses, 0 = absent (counts as zeros)
-  const uint32_t* lens;      // groups * k
-  uint64_t groups;
-  uint32_t k, r, P;
-  uint8_t* parity;           // parity row (g, i) at (g * r + i) * P, full P-byte rows
-  uint32_t* symlen_out;      // nullable
-  const void* tables;        // (r-1) x k CoefEntry (rows 1..r-1), device
-};
-
-// The instantiations of recover_gather_var, X(K, MAXE, POL): the shapes and policies of
-// recover_gather, in a list of their own (QFEC_GATHER_FORMS stays the fixed-length kernel's).
-#define QFEC_GATHER_VAR_FORMS(X) QFEC_GATHER_SHAPES(QFEC_GATHER_FIXED, X) X(0, 8, kGatherPol | kNoCoefBranch)
-
-// The form fec_recover_gather_var_rs_dev runs for (k, r, P): a classify_gather_var launch, then
-// recover_gather_var<K, MAXE, POL> in ceil(r / MAXE) passes -- the fixed-length call's choice.
-inline GatherForm gather_var_form(uint32_t k, uint32_t r, uint32_t P) { return gather_form(k, r, P); }
-
-// fec_encode_gather_var_rs_dev: encode_gather_var<0, R, FIRST> at runtime k for every shape, in
-// passes of up to kGatherVarEncodeRows parity rows (the route the fixed-length gather encode takes
-// for every shape but k=10 r=1); the first pass owns the XOR row and writes the symbol lengths.
-constexpr uint32_t kGatherVarEncodeRows = 8;
-constexpr int kGatherVarEncodePol = kNtStore;
-struct GatherVarEncodeForm {
-  bool supported = false;  // false: P < 16, the call is refused
-  uint32_t passes = 0;     // pass p: rows [p * 8, min(r, p * 8 + 8)), FIRST = (p == 0)
-};
-inline GatherVarEncodeForm gather_var_encode_form(uint32_t k, uint32_t r, uint32_t P) {
-  GatherVarEncodeForm f;
-  if (P < kVecMinP) return f;
-  f.supported = true;
-  f.passes = (r + kGatherVarEncodeRows - 1) / kGatherVarEncodeRows;
-  return f;
+// The passes of a runtime-k encode: at most kEncodePassRows parity rows per launch, pass p the rows
+// [p * 8, min(r, p * 8 + 8)), the first pass owning the XOR row.  The rule of encode_v16<0, R> (the
+// route the fixed-length gather encode takes for every shape but k=10 r=1) and of the table
+// encodes.  QFEC_ENCODE_PASS_ROWS: the row counts a pass can have, X(extra..., R).
+constexpr uint32_t kEncodePassRows = 8;
+constexpr uint32_t encode_pass_rows(uint32_t r, uint32_t pass) {
+  return r - pass * kEncodePassRows < kEncodePassRows ? r - pass * kEncodePassRows : kEncodePassRows;
 }
-inline uint32_t gather_var_encode_rows(uint32_t r, uint32_t pass) {
-  const uint32_t row0 = pass * kGatherVarEncodeRows;
-  return r - row0 < kGatherVarEncodeRows ? r - row0 : kGatherVarEncodeRows;
-}
+#define QFEC_ENCODE_PASS_ROWS(X, ...)                                                               \
+  X(__VA_ARGS__, 1) X(__VA_ARGS__, 2) X(__VA_ARGS__, 3) X(__VA_ARGS__, 4) X(__VA_ARGS__, 5) X(__VA_ARGS__, 6) \
+  X(__VA_ARGS__, 7) X(__VA_ARGS__, 8)
 
-// ---- scatter recover (fec_recover_scatter_rs_dev, fec_scatter.hip) ----
-// The address table (with or without the length table) in, and a table of destinations out:
-// data shard j of group g, if the call rebuilds it, goes to dests[g * k + j], exactly the group's
-// symbol length of it (fec_scatter_cut.hpp); 0 = not wanted.
-struct ScatterLaunch {
-  GatherLaunch g;            // as the fixed-length recover; g.out is not used
-  const uint32_t* lens;      // nullable: groups * (k + r) readable bytes per entry; NULL = every present shard has P
-  const uint64_t* dests;     // groups * k absolute device addresses
-  uint32_t* symlen;          // per group the largest min(len, P) of its present entries (P without
-                             // a length table), 0 when none is present: the caller's output or, when
-                             // that is NULL and there is a length table, workspace (the kernel reads it)
-};
-
-// The instantiations of recover_scatter, X(K, MAXE, POL, VAR): the shapes and policies of
-// recover_gather once without (VAR = false) and once with the length table, in a list of their own.
-// kCompactOut stays set in POL (the forms are the gather recover's); the rows go to the
-// destination table whatever it says.
-#define QFEC_SCATTER_FIXED(X, K, R) X(K, R, kGatherPol, false) X(K, R, kGatherPol, true)
-#define QFEC_SCATTER_FORMS(X)                  \
-  QFEC_GATHER_SHAPES(QFEC_SCATTER_FIXED, X)    \
-  X(0, 8, kGatherPol | kNoCoefBranch, false) X(0, 8, kGatherPol | kNoCoefBranch, true)
-
-struct ScatterForm {
+// The table encodes, encode_gather_var<0, R, FIRST> and encode_scatter<0, R, FIRST, VAR>: every
+// shape at runtime k in those passes, NT stores; the first pass also writes the symbol lengths.
+constexpr int kTableEncodePol = kNtStore;
+struct TableEncodeForm {
   bool supported = false;  // false: P < 16, the call is refused
-  int K = 0, MAXE = 0;     // template shape; runtime k as K = 0, MAXE = 8
-  int POL = 0;
-  bool VAR = false;        // loads masked by the length table, stores cut at the symbol length
-};
-
-// The form fec_recover_scatter_rs_dev runs for (k, r, P) with (var) or without a length table: a
-// classify_scatter launch, then recover_scatter<K, MAXE, POL, VAR> in ceil(r / MAXE) passes -- the
-// gather recover's choice of shape and policy.
-inline ScatterForm scatter_form(uint32_t k, uint32_t r, uint32_t P, bool var) {
-  const GatherForm g = gather_form(k, r, P);
-  ScatterForm f;
-  f.supported = g.supported, f.K = g.K, f.MAXE = g.MAXE, f.POL = g.POL, f.VAR = g.supported && var;
-  return f;
-}
-
-// ---- scatter encode (fec_encode_scatter_rs_dev, fec_scatter_encode.hip) ----
-// The packets' address table (with or without the length table) in, and a table of destinations
-// out: parity row i of group g goes to dests[g * r + i], exactly the group's symbol length of it
-// (fec_scatter_encode_cut.hpp); 0 = not wanted.
-struct ScatterEncodeLaunch {
-  const uint64_t* addrs;     // groups * k absolute device addresses, 0 = absent (counts as zeros)
-  const uint32_t* lens;      // nullable: groups * k readable bytes per packet; NULL = every present packet has P
-  const uint64_t* dests;     // groups * r absolute device addresses
-  uint64_t groups;
-  uint32_t k, r, P;
-  uint32_t* symlen_out;      // nullable
-  const void* tables;        // (r-1) x k CoefEntry (rows 1..r-1), device
-};
-
-// fec_encode_scatter_rs_dev: encode_scatter<0, R, FIRST, VAR> at runtime k for every shape, in
-// passes of up to kScatterEncodeRows parity rows (the variable-length gather encode's passes); the
-// first pass owns the XOR row and writes the symbol lengths.  VAR: with the length table.
-constexpr uint32_t kScatterEncodeRows = 8;
-constexpr int kScatterEncodePol = kNtStore;
-struct ScatterEncodeForm {
-  bool supported = false;  // false: P < 16, the call is refused
-  uint32_t passes = 0;     // pass p: rows [p * 8, min(r, p * 8 + 8)), FIRST = (p == 0)
+  uint32_t passes = 0;     // pass p: encode_pass_rows(r, p) rows from row p * 8, FIRST = (p == 0)
   bool VAR = false;        // loads masked by the length table
 };
-inline ScatterEncodeForm scatter_encode_form(uint32_t k, uint32_t r, uint32_t P, bool var) {
-  ScatterEncodeForm f;
+// The form a table encode runs for (k, r, P) with (var) or without a length table.
+inline TableEncodeForm table_encode_form(uint32_t /*k: every shape at runtime k*/, uint32_t r, uint32_t P, bool var) {
+  TableEncodeForm f;
   if (P < kVecMinP) return f;
   f.supported = true;
-  f.passes = (r + kScatterEncodeRows - 1) / kScatterEncodeRows;
+  f.passes = (r + kEncodePassRows - 1) / kEncodePassRows;
   f.VAR = var;
   return f;
 }
-inline uint32_t scatter_encode_rows(uint32_t r, uint32_t pass) {
-  const uint32_t row0 = pass * kScatterEncodeRows;
-  return r - row0 < kScatterEncodeRows ? r - row0 : kScatterEncodeRows;
-}
-// The instantiations of encode_scatter, X(R, FIRST, VAR): every row count of a pass, as the first
+// The instantiations of encode_scatter, X(FIRST, VAR, R): every row count of a pass, as the first
 // pass and as a later one (r = 8 + R), without and with the length table.
-#define QFEC_SCATTER_ENCODE_ROWS(X, F, V) X(1, F, V) X(2, F, V) X(3, F, V) X(4, F, V) X(5, F, V) X(6, F, V) X(7, F, V) X(8, F, V)
-#define QFEC_SCATTER_ENCODE_FORMS(X)                                                           \
-  QFEC_SCATTER_ENCODE_ROWS(X, true, false) QFEC_SCATTER_ENCODE_ROWS(X, false, false)           \
-  QFEC_SCATTER_ENCODE_ROWS(X, true, true) QFEC_SCATTER_ENCODE_ROWS(X, false, true)
+#define QFEC_SCATTER_ENCODE_FORMS(X)                                                  \
+  QFEC_ENCODE_PASS_ROWS(X, true, false) QFEC_ENCODE_PASS_ROWS(X, false, false)       \
+  QFEC_ENCODE_PASS_ROWS(X, true, true) QFEC_ENCODE_PASS_ROWS(X, false, true)
 
 // ---- encode ----
 enum class EncodeKernel : int { kBytes, kV16, kBits };

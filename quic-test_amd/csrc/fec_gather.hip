@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void recover_gather(const uint64_t* __restrict
 }
 
 template <int K, int MAXE, int POL>
-hipError_t run_recover_gather(const GatherLaunch& a, hipStream_t s) {
+hipError_t run_recover_gather(const TableRecoverLaunch& a, hipStream_t s) {
   const uint64_t n = a.k + a.r;
   return for_wave_passes(a.groups, a.r, MAXE, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
     LaunchRecord t = launch_record(static_cast<int64_t>(GatherLaunchForm::kRecoverGather), bn, 256, g0, gn);
@@ -89,19 +89,18 @@ hipError_t run_recover_gather(const GatherLaunch& a, hipStream_t s) {
 
 }  // namespace
 
-// Which form runs is decided in fec_forms.hpp (gather_form); this only launches it.
-hipError_t launch_recover_gather(const GatherLaunch& a, hipStream_t s) {
+// Which form runs is decided in fec_forms.hpp (table_recover_form); this only launches it.
+hipError_t launch_recover_gather(const TableRecoverLaunch& a, hipStream_t s) {
   if (a.groups == 0) return hipSuccess;
-  const GatherForm f = gather_form(a.k, a.r, a.P);
+  const TableRecoverForm f = table_recover_form(a.k, a.r, a.P, false);
   if (!f.supported) return hipErrorInvalidValue;
-  hipError_t (*run)(const GatherLaunch&, hipStream_t) = nullptr;
-#define QFEC_GATHER(KK, MM, PP) \
+  hipError_t (*run)(const TableRecoverLaunch&, hipStream_t) = nullptr;
+#define QFEC_GATHER(_, KK, MM, PP) \
   if (f.K == KK && f.MAXE == MM && f.POL == (PP)) run = run_recover_gather<KK, MM, PP>;
-  QFEC_GATHER_FORMS(QFEC_GATHER)
+  QFEC_TABLE_RECOVER_FORMS(QFEC_GATHER, ~)
 #undef QFEC_GATHER
   if (run == nullptr) return hipErrorNotSupported;
-  const hipError_t e =
-      run_classify_table<Lens::kNone>(a, nullptr, nullptr, static_cast<int64_t>(GatherLaunchForm::kClassifyGather), s);
+  const hipError_t e = run_classify_table<Lens::kNone>(a, static_cast<int64_t>(GatherLaunchForm::kClassifyGather), s);
   return e != hipSuccess ? e : run(a, s);
 }
 

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void encode_gather_var(const uint64_t* __restr
     const uint32_t len = a != 0 ? min_u32(gl[j], P) : 0u;  // absent: all zero, never dereferenced
     symlen = symlen > len ? symlen : len;
     uint32_t x[4];
-    load_masked<4, kGatherVarEncodePol>(shard_ptr(a), coff, len, x);
+    load_masked<4, kTableEncodePol>(shard_ptr(a), coff, len, x);
     SelN<4> sel;
     sel_split(x, sel);
 #pragma unroll
@@ -162,31 +162,30 @@ __global__ __launch_bounds__(256) void encode_gather_var(const uint64_t* __restr
   }
 #pragma unroll
   for (int i = 0; i < R; ++i)
-    stw<4, kGatherVarEncodePol>(parity + (static_cast<uint64_t>(g) * r_total + row0 + static_cast<uint32_t>(i)) * P + coff, acc[i]);
+    stw<4, kTableEncodePol>(parity + (static_cast<uint64_t>(g) * r_total + row0 + static_cast<uint32_t>(i)) * P + coff, acc[i]);
   if (FIRST && col == 0 && symlen_out) symlen_out[g] = symlen;
 }
 
 template <int K, int MAXE, int POL>
-hipError_t run_recover_gather_var(const GatherVarLaunch& v, hipStream_t s) {
-  const GatherLaunch& a = v.g;
+hipError_t run_recover_gather_var(const TableRecoverLaunch& a, hipStream_t s) {
   const uint64_t n = a.k + a.r;
   return for_wave_passes(a.groups, a.r, MAXE, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
     LaunchRecord t = launch_record(static_cast<int64_t>(GatherVarLaunchForm::kRecoverGatherVar), bn, 256, g0, gn);
     t.k = K, t.r = MAXE, t.pol = POL, t.aux = m0;
     trace_launch(t);
     hipLaunchKernelGGL((recover_gather_var<K, MAXE, POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
-                       a.addrs + g0 * n, v.lens + g0 * n, a.rec_off + g0, a.codebook, gn, a.P, a.k, a.r, m0,
+                       a.addrs + g0 * n, a.lens + g0 * n, a.rec_off + g0, a.codebook, gn, a.P, a.k, a.r, m0,
                        a.out + g0 * a.r * static_cast<uint64_t>(a.P), static_cast<uint32_t>(kDecodeWaveXcdSwizzle));
   });
 }
 
 template <int R, bool FIRST>
-hipError_t run_encode_gather_var(const GatherVarEncodeLaunch& a, uint32_t row0, hipStream_t s) {
+hipError_t run_encode_gather_var(const TableEncodeLaunch& a, uint32_t row0, hipStream_t s) {
   const uint32_t cpp = (a.P + 15u) / 16u;
   return for_chunks(a.groups, groups_per_launch(cpp), [&](uint64_t g0, uint64_t gn) {
     const uint32_t n = static_cast<uint32_t>(gn * cpp);
     LaunchRecord t = launch_record(static_cast<int64_t>(GatherVarLaunchForm::kEncodeGatherVar), blocks_for(n), 256, g0, gn);
-    t.k = 0, t.r = R, t.first = FIRST, t.pol = kGatherVarEncodePol, t.tile = 0, t.aux = row0;
+    t.k = 0, t.r = R, t.first = FIRST, t.pol = kTableEncodePol, t.tile = 0, t.aux = row0;
     trace_launch(t);
     hipLaunchKernelGGL((encode_gather_var<0, R, FIRST>), dim3(blocks_for(n)), dim3(256), 0, s, a.addrs + g0 * a.k,
                        a.lens + g0 * a.k, a.parity + g0 * a.r * static_cast<uint64_t>(a.P),
@@ -197,50 +196,33 @@ hipError_t run_encode_gather_var(const GatherVarEncodeLaunch& a, uint32_t row0, 
 
 }  // namespace
 
-// Which form runs is decided in fec_forms.hpp (gather_var_form); this only launches it.
-hipError_t launch_recover_gather_var(const GatherVarLaunch& a, hipStream_t s) {
-  if (a.g.groups == 0) return hipSuccess;
-  const GatherForm f = gather_var_form(a.g.k, a.g.r, a.g.P);
+// Which form runs is decided in fec_forms.hpp (table_recover_form); this only launches it.
+hipError_t launch_recover_gather_var(const TableRecoverLaunch& a, hipStream_t s) {
+  if (a.groups == 0) return hipSuccess;
+  const TableRecoverForm f = table_recover_form(a.k, a.r, a.P, true);
   if (!f.supported) return hipErrorInvalidValue;
-  hipError_t (*run)(const GatherVarLaunch&, hipStream_t) = nullptr;
-#define QFEC_GATHER_VAR(KK, MM, PP) \
+  hipError_t (*run)(const TableRecoverLaunch&, hipStream_t) = nullptr;
+#define QFEC_GATHER_VAR(_, KK, MM, PP) \
   if (f.K == KK && f.MAXE == MM && f.POL == (PP)) run = run_recover_gather_var<KK, MM, PP>;
-  QFEC_GATHER_VAR_FORMS(QFEC_GATHER_VAR)
+  QFEC_TABLE_RECOVER_FORMS(QFEC_GATHER_VAR, ~)
 #undef QFEC_GATHER_VAR
   if (run == nullptr) return hipErrorNotSupported;
-  const hipError_t e = run_classify_table<Lens::kGiven>(
-      a.g, a.lens, a.symlen_out, static_cast<int64_t>(GatherVarLaunchForm::kClassifyGatherVar), s);
+  const hipError_t e =
+      run_classify_table<Lens::kGiven>(a, static_cast<int64_t>(GatherVarLaunchForm::kClassifyGatherVar), s);
   return e != hipSuccess ? e : run(a, s);
 }
 
-// The passes of gather_var_encode_form; the first owns the XOR row.
-hipError_t launch_encode_gather_var(const GatherVarEncodeLaunch& a, hipStream_t s) {
+// The passes of table_encode_form (fec_forms.hpp); the first owns the XOR row.
+hipError_t launch_encode_gather_var(const TableEncodeLaunch& a, hipStream_t s) {
   if (a.groups == 0) return hipSuccess;
-  const GatherVarEncodeForm f = gather_var_encode_form(a.k, a.r, a.P);
-  if (!f.supported) return hipErrorInvalidValue;
-  for (uint32_t p = 0; p < f.passes; ++p) {
-    const uint32_t row0 = p * kGatherVarEncodeRows;
-    hipError_t e = hipSuccess;
-#define QFEC_PASS(RR)                                                                                   \
-  case RR:                                                                                              \
-    e = p == 0 ? run_encode_gather_var<RR, true>(a, row0, s) : run_encode_gather_var<RR, false>(a, row0, s); \
-    break;
-    switch (gather_var_encode_rows(a.r, p)) {
-      QFEC_PASS(1)
-      QFEC_PASS(2)
-      QFEC_PASS(3)
-      QFEC_PASS(4)
-      QFEC_PASS(5)
-      QFEC_PASS(6)
-      QFEC_PASS(7)
-      QFEC_PASS(8)
-      default:
-        return hipErrorInvalidValue;
-    }
+  if (!table_encode_form(a.k, a.r, a.P, true).supported) return hipErrorInvalidValue;
+  return for_row_passes(a.r, [&](uint32_t row0, uint32_t rows, bool first) {
+#define QFEC_PASS(_, RR) \
+  if (rows == RR) return first ? run_encode_gather_var<RR, true>(a, row0, s) : run_encode_gather_var<RR, false>(a, row0, s);
+    QFEC_ENCODE_PASS_ROWS(QFEC_PASS, ~)
 #undef QFEC_PASS
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return hipErrorInvalidValue;
+  });
 }
 
 }  // namespace qfec

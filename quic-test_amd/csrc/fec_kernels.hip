@@ -2091,31 +2091,14 @@ hipError_t run_encode_generic(const EncodeLaunch& a, hipStream_t s) {
                          a.parity, g0, n, a.P, a.k, a.r, static_cast<const Tab*>(a.tables));
     });
   }
-  // Runtime k: passes of up to 8 parity rows; the first pass owns the XOR row.
-  for (uint32_t row0 = 0; row0 < a.r; row0 += 8) {
-    const uint32_t rows = (a.r - row0 < 8) ? a.r - row0 : 8;
-    hipError_t e = hipSuccess;
-#define QFEC_PASS(RR)                                                            \
-  case RR:                                                                       \
-    e = row0 == 0 ? run_encode_v16<0, RR, OFF, true>(a, row0, s)                 \
-                  : run_encode_v16<0, RR, OFF, false>(a, row0, s);               \
-    break;
-    switch (rows) {
-      QFEC_PASS(1)
-      QFEC_PASS(2)
-      QFEC_PASS(3)
-      QFEC_PASS(4)
-      QFEC_PASS(5)
-      QFEC_PASS(6)
-      QFEC_PASS(7)
-      QFEC_PASS(8)
-      default:
-        return hipErrorInvalidValue;
-    }
+  // Runtime k: passes of up to 8 parity rows (for_row_passes); the first pass owns the XOR row.
+  return for_row_passes(a.r, [&](uint32_t row0, uint32_t rows, bool first) {
+#define QFEC_PASS(_, RR) \
+  if (rows == RR) return first ? run_encode_v16<0, RR, OFF, true>(a, row0, s) : run_encode_v16<0, RR, OFF, false>(a, row0, s);
+    QFEC_ENCODE_PASS_ROWS(QFEC_PASS, ~)
 #undef QFEC_PASS
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return hipErrorInvalidValue;
+  });
 }
 
 }  // namespace

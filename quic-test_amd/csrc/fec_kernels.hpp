@@ -40,18 +40,19 @@ hipError_t launch_encode(const EncodeLaunch& a, hipStream_t s);
 hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s);
 // Recover from an address table (fec_gather.hip): the classify scan (fec_table.hpp classify_table,
 // one kernel template for the three table recovers, traced under each call's own classify form),
-// then gather_form's recover_gather.
-hipError_t launch_recover_gather(const GatherLaunch& a, hipStream_t s);
+// then table_recover_form's recover_gather.
+hipError_t launch_recover_gather(const TableRecoverLaunch& a, hipStream_t s);
 // The same with a length per table entry (fec_gather_var.hip): classify_table with the lengths, then
-// gather_var_form's recover_gather_var; and the encode from addresses and lengths, 0 = absent.
-hipError_t launch_recover_gather_var(const GatherVarLaunch& a, hipStream_t s);
-hipError_t launch_encode_gather_var(const GatherVarEncodeLaunch& a, hipStream_t s);
+// table_recover_form's recover_gather_var; and the encode from addresses and lengths, 0 = absent:
+// table_encode_form's passes of encode_gather_var.
+hipError_t launch_recover_gather_var(const TableRecoverLaunch& a, hipStream_t s);
+hipError_t launch_encode_gather_var(const TableEncodeLaunch& a, hipStream_t s);
 // Recover from an address table into a table of destinations (fec_scatter.hip): classify_table
-// with a nullable length table, then scatter_form's recover_scatter.
-hipError_t launch_recover_scatter(const ScatterLaunch& a, hipStream_t s);
+// with a nullable length table, then table_recover_form's recover_scatter.
+hipError_t launch_recover_scatter(const TableRecoverLaunch& a, hipStream_t s);
 // Encode from an address table (with a nullable length table) into a table of destinations
-// (fec_scatter_encode.hip): scatter_encode_form's passes of encode_scatter.
-hipError_t launch_encode_scatter(const ScatterEncodeLaunch& a, hipStream_t s);
+// (fec_scatter_encode.hip): table_encode_form's passes of encode_scatter.
+hipError_t launch_encode_scatter(const TableEncodeLaunch& a, hipStream_t s);
 // Packed recover rows: row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.

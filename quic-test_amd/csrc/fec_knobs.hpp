@@ -77,20 +77,20 @@ enum class LaunchForm : int64_t {
   kRunsRezero = 17,  // no kernel: recover_runs' workspace zeroed again because its epochs wrapped
 };
 // The address-table kernels (fec_gather.hip), numbered on from LaunchForm in a list of their own,
-// as their forms are (fec_forms.hpp QFEC_GATHER_FORMS); named by quicfec.GATHER_LAUNCH_FORMS.
+// as their forms are (fec_forms.hpp QFEC_TABLE_RECOVER_FORMS); named by quicfec.GATHER_LAUNCH_FORMS.
 enum class GatherLaunchForm : int64_t {
   kClassifyGather = 18,
   kRecoverGather = 19,
 };
 // The variable-length address-table kernels (fec_gather_var.hip), numbered on in a list of their
-// own again (fec_forms.hpp QFEC_GATHER_VAR_FORMS); named by quicfec.GATHER_VAR_LAUNCH_FORMS.
+// own again (fec_forms.hpp QFEC_TABLE_RECOVER_FORMS); named by quicfec.GATHER_VAR_LAUNCH_FORMS.
 enum class GatherVarLaunchForm : int64_t {
   kClassifyGatherVar = 20,
   kRecoverGatherVar = 21,
   kEncodeGatherVar = 22,
 };
 // The scatter recover's kernels (fec_scatter.hip), numbered on in a list of their own
-// (fec_forms.hpp QFEC_SCATTER_FORMS); named by quicfec.SCATTER_LAUNCH_FORMS.
+// (fec_forms.hpp QFEC_TABLE_RECOVER_FORMS); named by quicfec.SCATTER_LAUNCH_FORMS.
 enum class ScatterLaunchForm : int64_t {
   kClassifyScatter = 23,
   kRecoverScatter = 24,  // LaunchRecord::first: 1 with a length table (VAR), 0 without

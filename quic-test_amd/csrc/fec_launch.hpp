@@ -1,13 +1,14 @@
 // fec_launch.hpp — what the host launchers of the kernel translation units (fec_kernels.hip,
 // fec_gather.hip, fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip) share: the per-launch limits with their
-// test switches, the chunk walk, the pass-and-chunk walk of the wave-per-group kernels and the
-// launch trace's record.  Host code only.
+// test switches, the chunk walk, the pass-and-chunk walk of the wave-per-group kernels, the row
+// passes of the runtime-k encodes and the launch trace's record.  Host code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "fec_forms.hpp"
 #include "fec_knobs.hpp"
 
 namespace qfec {
@@ -74,6 +75,18 @@ hipError_t for_wave_passes(uint64_t groups, uint32_t r, uint32_t maxe, F launch)
     const hipError_t e = for_chunks(groups, max_wave_blocks() * 4, [&](uint64_t g0, uint64_t gn) {
       launch(g0, gn, (gn + 3) / 4, m0);
     });
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// The passes of a runtime-k encode over its r parity rows (fec_forms.hpp encode_pass_rows), in row
+// order: launch(row0, rows, first) launches pass [row0, row0 + rows), every chunk of it, and
+// returns its error; `first`: the pass that owns the XOR row.  Stops at the first error.
+template <typename F>
+hipError_t for_row_passes(uint32_t r, F launch) {
+  for (uint32_t row0 = 0; row0 < r; row0 += kEncodePassRows) {
+    const hipError_t e = launch(row0, encode_pass_rows(r, row0 / kEncodePassRows), row0 == 0);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

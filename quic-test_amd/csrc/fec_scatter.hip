@@ -167,36 +167,37 @@ __global__ __launch_bounds__(256) void recover_scatter(const uint64_t* __restric
 }
 
 template <int K, int MAXE, int POL, bool VAR>
-hipError_t run_recover_scatter(const ScatterLaunch& v, hipStream_t s) {
-  const GatherLaunch& a = v.g;
+hipError_t run_recover_scatter(const TableRecoverLaunch& a, hipStream_t s) {
   const uint64_t n = a.k + a.r;
   return for_wave_passes(a.groups, a.r, MAXE, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
     LaunchRecord t = launch_record(static_cast<int64_t>(ScatterLaunchForm::kRecoverScatter), bn, 256, g0, gn);
     t.k = K, t.r = MAXE, t.first = VAR, t.pol = POL, t.aux = m0;
     trace_launch(t);
     hipLaunchKernelGGL((recover_scatter<K, MAXE, POL, VAR>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
-                       a.addrs + g0 * n, VAR ? v.lens + g0 * n : nullptr, v.dests + g0 * a.k, a.rec_off + g0,
-                       VAR ? v.symlen + g0 : nullptr, a.codebook, gn, a.P, a.k, a.r, m0,
+                       a.addrs + g0 * n, VAR ? a.lens + g0 * n : nullptr, a.dests + g0 * a.k, a.rec_off + g0,
+                       VAR ? a.symlen + g0 : nullptr, a.codebook, gn, a.P, a.k, a.r, m0,
                        static_cast<uint32_t>(kDecodeWaveXcdSwizzle));
   });
 }
 
 }  // namespace
 
-// Which form runs is decided in fec_forms.hpp (scatter_form); this only launches it.
-hipError_t launch_recover_scatter(const ScatterLaunch& a, hipStream_t s) {
-  if (a.g.groups == 0) return hipSuccess;
-  const ScatterForm f = scatter_form(a.g.k, a.g.r, a.g.P, a.lens != nullptr);
+// Which form runs is decided in fec_forms.hpp (table_recover_form); this only launches it.  Every
+// form of the list once without (VAR = false) and once with the length table.
+hipError_t launch_recover_scatter(const TableRecoverLaunch& a, hipStream_t s) {
+  if (a.groups == 0) return hipSuccess;
+  const TableRecoverForm f = table_recover_form(a.k, a.r, a.P, a.lens != nullptr);
   if (!f.supported) return hipErrorInvalidValue;
   if (f.VAR && a.symlen == nullptr) return hipErrorInvalidValue;  // the kernel reads the symbol lengths
-  hipError_t (*run)(const ScatterLaunch&, hipStream_t) = nullptr;
-#define QFEC_SCATTER(KK, MM, PP, VV) \
+  hipError_t (*run)(const TableRecoverLaunch&, hipStream_t) = nullptr;
+#define QFEC_SCATTER(VV, KK, MM, PP) \
   if (f.K == KK && f.MAXE == MM && f.POL == (PP) && f.VAR == VV) run = run_recover_scatter<KK, MM, PP, VV>;
-  QFEC_SCATTER_FORMS(QFEC_SCATTER)
+  QFEC_TABLE_RECOVER_FORMS(QFEC_SCATTER, false)
+  QFEC_TABLE_RECOVER_FORMS(QFEC_SCATTER, true)
 #undef QFEC_SCATTER
   if (run == nullptr) return hipErrorNotSupported;
-  const hipError_t e = run_classify_table<Lens::kNullable>(
-      a.g, a.lens, a.symlen, static_cast<int64_t>(ScatterLaunchForm::kClassifyScatter), s);
+  const hipError_t e =
+      run_classify_table<Lens::kNullable>(a, static_cast<int64_t>(ScatterLaunchForm::kClassifyScatter), s);
   return e != hipSuccess ? e : run(a, s);
 }
 

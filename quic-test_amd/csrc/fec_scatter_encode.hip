@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void encode_scatter(const uint64_t* __restrict
                                                       uint32_t cpp, uint32_t P, uint32_t k, uint32_t r_total,
                                                       uint32_t row0, const Tab* __restrict__ tabs) {
   static_assert(K == 0, "encode_scatter takes k at run time");
-  constexpr int POL = kScatterEncodePol;
+  constexpr int POL = kTableEncodePol;
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nthreads) return;
   const uint32_t g = t / cpp;
@@ -114,12 +114,12 @@ __global__ __launch_bounds__(256) void encode_scatter(const uint64_t* __restrict
 }
 
 template <int R, bool FIRST, bool VAR>
-hipError_t run_encode_scatter(const ScatterEncodeLaunch& a, uint32_t row0, hipStream_t s) {
+hipError_t run_encode_scatter(const TableEncodeLaunch& a, uint32_t row0, hipStream_t s) {
   const uint32_t cpp = (a.P + 15u) / 16u;
   return for_chunks(a.groups, groups_per_launch(cpp), [&](uint64_t g0, uint64_t gn) {
     const uint32_t n = static_cast<uint32_t>(gn * cpp);
     LaunchRecord t = launch_record(static_cast<int64_t>(ScatterEncodeLaunchForm::kEncodeScatter), blocks_for(n), 256, g0, gn);
-    t.k = 0, t.r = R, t.first = FIRST, t.pol = kScatterEncodePol, t.direct = VAR, t.tile = 0, t.aux = row0;
+    t.k = 0, t.r = R, t.first = FIRST, t.pol = kTableEncodePol, t.direct = VAR, t.tile = 0, t.aux = row0;
     trace_launch(t);
     hipLaunchKernelGGL((encode_scatter<0, R, FIRST, VAR>), dim3(blocks_for(n)), dim3(256), 0, s, a.addrs + g0 * a.k,
                        VAR ? a.lens + g0 * a.k : nullptr, a.dests + g0 * a.r,
@@ -130,25 +130,20 @@ hipError_t run_encode_scatter(const ScatterEncodeLaunch& a, uint32_t row0, hipSt
 
 }  // namespace
 
-// The passes of scatter_encode_form (fec_forms.hpp); the first owns the XOR row.  This only
+// The passes of table_encode_form (fec_forms.hpp); the first owns the XOR row.  This only
 // launches what is decided there.
-hipError_t launch_encode_scatter(const ScatterEncodeLaunch& a, hipStream_t s) {
+hipError_t launch_encode_scatter(const TableEncodeLaunch& a, hipStream_t s) {
   if (a.groups == 0) return hipSuccess;
-  const ScatterEncodeForm f = scatter_encode_form(a.k, a.r, a.P, a.lens != nullptr);
+  const TableEncodeForm f = table_encode_form(a.k, a.r, a.P, a.lens != nullptr);
   if (!f.supported) return hipErrorInvalidValue;
-  for (uint32_t p = 0; p < f.passes; ++p) {
-    const uint32_t row0 = p * kScatterEncodeRows;
-    const uint32_t rows = scatter_encode_rows(a.r, p);
-    hipError_t (*run)(const ScatterEncodeLaunch&, uint32_t, hipStream_t) = nullptr;
-#define QFEC_SCATTER_ENCODE(RR, FF, VV) \
-  if (rows == RR && (p == 0) == FF && f.VAR == VV) run = run_encode_scatter<RR, FF, VV>;
+  return for_row_passes(a.r, [&](uint32_t row0, uint32_t rows, bool first) {
+    hipError_t (*run)(const TableEncodeLaunch&, uint32_t, hipStream_t) = nullptr;
+#define QFEC_SCATTER_ENCODE(FF, VV, RR) \
+  if (rows == RR && first == FF && f.VAR == VV) run = run_encode_scatter<RR, FF, VV>;
     QFEC_SCATTER_ENCODE_FORMS(QFEC_SCATTER_ENCODE)
 #undef QFEC_SCATTER_ENCODE
-    if (run == nullptr) return hipErrorNotSupported;
-    const hipError_t e = run(a, row0, s);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    return run == nullptr ? hipErrorNotSupported : run(a, row0, s);
+  });
 }
 
 }  // namespace qfec

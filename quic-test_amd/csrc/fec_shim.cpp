@@ -1715,7 +1715,7 @@ int table_recover_locked(const char* what, FECEncoderCtx* ctx, const uint64_t* d
   rc = get_decode_plan(ctx, k, r, &plan);
   if (rc != FEC_OK) return rc;
   hipStream_t s = pick_stream(ctx, stream);
-  qfec::GatherLaunch a{};
+  qfec::TableRecoverLaunch a{};
   a.addrs = d_shard_addrs;
   a.groups = G;
   a.k = k;
@@ -1733,6 +1733,28 @@ int table_recover_locked(const char* what, FECEncoderCtx* ctx, const uint64_t* d
   return launch(a, s);
 }
 
+// What the three table encodes do between their own NULL checks and their launch: the shape,
+// refused before any lock or device call; then, under the context's lock and on its device, the
+// encode plan's coefficient tables and the stream.  launch(tables, s) fills the call's fields and
+// launches, the lock still held.
+template <typename F>
+int table_encode_locked(const char* what, FECEncoderCtx* ctx, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
+                        void* stream, F launch) {
+  int rc = check_gather_shape(what, G, k, r, P);
+  if (rc != FEC_OK) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard dg(ctx->device);
+  if (!dg.ok) return FEC_ERR_NODEV;
+  const void* tables = nullptr;
+  rc = get_encode_plan(ctx, k, r, &tables);
+  if (rc != FEC_OK) return rc;
+  return launch(tables, pick_stream(ctx, stream));
+}
+
+// The result of a table encode's launch; `call` is the text a failure reports, as `ws_call` above
+// (QFEC_HIP reports the failing expression, and these calls' messages name the stream unpicked).
+int table_encode_done(hipError_t e, const char* call) { return e == hipSuccess ? FEC_OK : hip_fail(e, call); }
+
 }  // namespace
 
 static int fec_recover_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
@@ -1743,7 +1765,7 @@ static int fec_recover_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_
     return FEC_ERR_NULL;
   }
   return table_recover_locked("gather recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out, stream, 1,
-                              kRecOffWorkspaceCall, [&](qfec::GatherLaunch& a, hipStream_t s) {
+                              kRecOffWorkspaceCall, [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
                                 a.out = d_rebuilt;
                                 QFEC_HIP(qfec::launch_recover_gather(a, s));
                                 return FEC_OK;
@@ -1764,13 +1786,10 @@ static int fec_encode_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_p
     set_error("gather encode: %s is NULL", !ctx ? "the context" : !d_packet_addrs ? "d_packet_addrs" : "d_parity");
     return FEC_ERR_NULL;
   }
-  int rc = check_gather_shape("gather encode", G, k, r, P);
-  if (rc != FEC_OK) return rc;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  return encode_dev_locked(ctx, nullptr, d_packet_addrs, qfec::OffsetKind::kAddr, G, k, r, P, d_parity,
-                           pick_stream(ctx, stream));
+  // launch_encode with absolute addresses: encode_dev_locked takes the plan's tables itself
+  return table_encode_locked("gather encode", ctx, G, k, r, P, stream, [&](const void*, hipStream_t s) {
+    return encode_dev_locked(ctx, nullptr, d_packet_addrs, qfec::OffsetKind::kAddr, G, k, r, P, d_parity, s);
+  });
 }
 
 QFEC_EXPORT int fec_encode_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs, uint64_t G, uint32_t k,
@@ -1792,12 +1811,10 @@ static int fec_recover_gather_var_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t
     return FEC_ERR_NULL;
   }
   return table_recover_locked("variable-length gather recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out,
-                              stream, 1, kRecOffWorkspaceCall, [&](qfec::GatherLaunch& g, hipStream_t s) {
-                                g.out = d_rebuilt;
-                                qfec::GatherVarLaunch a{};
-                                a.g = g;
+                              stream, 1, kRecOffWorkspaceCall, [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
+                                a.out = d_rebuilt;
                                 a.lens = d_shard_lens;
-                                a.symlen_out = d_symbol_len_out;
+                                a.symlen = d_symbol_len_out;
                                 QFEC_HIP(qfec::launch_recover_gather_var(a, s));
                                 return FEC_OK;
                               });
@@ -1822,26 +1839,14 @@ static int fec_encode_gather_var_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t*
                                                                              : "d_parity");
     return FEC_ERR_NULL;
   }
-  int rc = check_gather_shape("variable-length gather encode", G, k, r, P);
-  if (rc != FEC_OK) return rc;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  const void* tables = nullptr;
-  rc = get_encode_plan(ctx, k, r, &tables);
-  if (rc != FEC_OK) return rc;
-  qfec::GatherVarEncodeLaunch a{};
-  a.addrs = d_packet_addrs;
-  a.lens = d_packet_lens;
-  a.groups = G;
-  a.k = k;
-  a.r = r;
-  a.P = P;
-  a.parity = d_parity;
-  a.symlen_out = d_symbol_len_out;
-  a.tables = tables;
-  QFEC_HIP(qfec::launch_encode_gather_var(a, pick_stream(ctx, stream)));
-  return FEC_OK;
+  return table_encode_locked("variable-length gather encode", ctx, G, k, r, P, stream,
+                             [&](const void* tables, hipStream_t s) {
+                               // addrs, lens, groups, k, r, P, parity, dests, symlen_out, tables
+                               const qfec::TableEncodeLaunch a{d_packet_addrs, d_packet_lens, G, k, r, P, d_parity, nullptr,
+                                                               d_symbol_len_out, tables};
+                               return table_encode_done(qfec::launch_encode_gather_var(a, s),
+                                                        "qfec::launch_encode_gather_var(a, pick_stream(ctx, stream))");
+                             });
 }
 
 QFEC_EXPORT int fec_encode_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
@@ -1869,12 +1874,10 @@ static int fec_recover_scatter_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d
   return table_recover_locked("scatter recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out, stream,
                               own_symlen ? 2 : 1,
                               "stream_workspace(ctx, s, (own_symlen ? 2 : 1) * G * sizeof(uint32_t), &ws)",
-                              [&](qfec::GatherLaunch& g, hipStream_t s) {
-                                qfec::ScatterLaunch a{};
-                                a.g = g;
+                              [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
                                 a.lens = d_shard_lens;
                                 a.dests = d_dest_addrs;
-                                a.symlen = own_symlen ? g.rec_off + G : d_symbol_len_out;
+                                a.symlen = own_symlen ? a.rec_off + G : d_symbol_len_out;
                                 QFEC_HIP(qfec::launch_recover_scatter(a, s));
                                 return FEC_OK;
                               });
@@ -1900,26 +1903,12 @@ static int fec_encode_scatter_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_
                                                               : "d_dest_addrs (the destination table)");
     return FEC_ERR_NULL;
   }
-  int rc = check_gather_shape("scatter encode", G, k, r, P);
-  if (rc != FEC_OK) return rc;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  const void* tables = nullptr;
-  rc = get_encode_plan(ctx, k, r, &tables);
-  if (rc != FEC_OK) return rc;
-  qfec::ScatterEncodeLaunch a{};
-  a.addrs = d_packet_addrs;
-  a.lens = d_packet_lens;
-  a.dests = d_dest_addrs;
-  a.groups = G;
-  a.k = k;
-  a.r = r;
-  a.P = P;
-  a.symlen_out = d_symbol_len_out;
-  a.tables = tables;
-  QFEC_HIP(qfec::launch_encode_scatter(a, pick_stream(ctx, stream)));
-  return FEC_OK;
+  return table_encode_locked("scatter encode", ctx, G, k, r, P, stream, [&](const void* tables, hipStream_t s) {
+    // addrs, lens, groups, k, r, P, parity, dests, symlen_out, tables
+    const qfec::TableEncodeLaunch a{d_packet_addrs, d_packet_lens, G, k, r, P, nullptr, d_dest_addrs, d_symbol_len_out,
+                                    tables};
+    return table_encode_done(qfec::launch_encode_scatter(a, s), "qfec::launch_encode_scatter(a, pick_stream(ctx, stream))");
+  });
 }
 
 QFEC_EXPORT int fec_encode_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,

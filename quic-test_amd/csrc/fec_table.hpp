@@ -151,10 +151,10 @@ __global__ __launch_bounds__(256) void classify_table(const uint64_t* __restrict
   classify_scan<LENS>(addrs, nullptr, groups, k, r, 0, binom, meta, rec_off, status, masks_out, nullptr);
 }
 
-// The classify of a table recover; `form` is the id the caller's launch trace records for it.
+// The classify of a table recover, with a.lens and a.symlen as LENS reads them; `form` is the id
+// the caller's launch trace records for it.
 template <Lens LENS>
-hipError_t run_classify_table(const GatherLaunch& a, const uint32_t* lens, uint32_t* symlen_out, int64_t form,
-                              hipStream_t s) {
+hipError_t run_classify_table(const TableRecoverLaunch& a, int64_t form, hipStream_t s) {
   const uint64_t n = a.k + a.r;
   return for_chunks(a.groups, max_launch_threads(), [&](uint64_t g0, uint64_t gn) {
     trace_launch(launch_record(form, blocks_for(gn), 256, g0, gn));
@@ -165,8 +165,8 @@ hipError_t run_classify_table(const GatherLaunch& a, const uint32_t* lens, uint3
                          a.binom, a.meta, a.rec_off + g0, status, masks_out);
     } else {
       hipLaunchKernelGGL(classify_table<LENS>, dim3(blocks_for(gn)), dim3(256), 0, s, a.addrs + g0 * n,
-                         lens ? lens + g0 * n : nullptr, gn, a.k, a.r, a.P, a.binom, a.meta, a.rec_off + g0, status,
-                         masks_out, symlen_out ? symlen_out + g0 : nullptr);
+                         a.lens ? a.lens + g0 * n : nullptr, gn, a.k, a.r, a.P, a.binom, a.meta, a.rec_off + g0,
+                         status, masks_out, a.symlen ? a.symlen + g0 : nullptr);
     }
   });
 }

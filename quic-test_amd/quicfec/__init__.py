@@ -204,6 +204,11 @@ def _ptr(a) -> int:
     raise TypeError(f"unsupported buffer type {type(a)!r}")
 
 
+def _opt(a) -> Optional[int]:
+    """_ptr of a nullable argument: None stays None (a NULL pointer)."""
+    return _ptr(a) if a is not None else None
+
+
 def _check(rc: int, what: str, lib: Optional[ctypes.CDLL] = None) -> None:
     if rc != FEC_OK:
         raise FecError(what, rc, last_error(lib))
@@ -318,17 +323,15 @@ class Context:
         """recover_dev from shards wherever they are: d_shard_addrs holds num_groups*(k+r) absolute
         device addresses (u64; data shards, then parity rows; 0 = lost).  d_masks_out (nullable): the
         erasure mask derived for each group."""
-        rc = self.lib.fec_recover_gather_rs_dev(self.handle, _ptr(d_shard_addrs) if d_shard_addrs is not None else None,
-                                                num_groups, k, r, packet_size, _ptr(d_rebuilt),
-                                                _ptr(d_status) if d_status is not None else None,
-                                                _ptr(d_masks_out) if d_masks_out is not None else None, stream)
+        rc = self.lib.fec_recover_gather_rs_dev(self.handle, _opt(d_shard_addrs), num_groups, k, r, packet_size,
+                                                _ptr(d_rebuilt), _opt(d_status), _opt(d_masks_out), stream)
         _check(rc, "fec_recover_gather_rs_dev", self.lib)
 
     def encode_gather_dev(self, d_packet_addrs, num_groups: int, k: int, r: int, packet_size: int, d_parity,
                           stream: Optional[int] = None) -> None:
         """encode_dev from packets wherever they are: num_groups*k absolute device addresses (u64)."""
-        rc = self.lib.fec_encode_gather_rs_dev(self.handle, _ptr(d_packet_addrs) if d_packet_addrs is not None else None,
-                                               num_groups, k, r, packet_size, _ptr(d_parity), stream)
+        rc = self.lib.fec_encode_gather_rs_dev(self.handle, _opt(d_packet_addrs), num_groups, k, r, packet_size,
+                                               _ptr(d_parity), stream)
         _check(rc, "fec_encode_gather_rs_dev", self.lib)
 
     def recover_gather_var_dev(self, d_shard_addrs, d_shard_lens, num_groups: int, k: int, r: int, packet_size: int,
@@ -338,19 +341,17 @@ class Context:
         addresses): shard (g, s) is its first min(len, packet_size) bytes, zero-padded; nothing at or
         past address + len is read.  d_symbol_len_out (nullable, u32 per group): the largest clamped
         length among the group's present entries."""
-        opt = lambda t: _ptr(t) if t is not None else None   # noqa: E731
-        rc = self.lib.fec_recover_gather_var_rs_dev(self.handle, opt(d_shard_addrs), opt(d_shard_lens), num_groups, k, r,
-                                                    packet_size, opt(d_rebuilt), opt(d_status), opt(d_masks_out),
-                                                    opt(d_symbol_len_out), stream)
+        rc = self.lib.fec_recover_gather_var_rs_dev(self.handle, _opt(d_shard_addrs), _opt(d_shard_lens), num_groups, k, r,
+                                                    packet_size, _opt(d_rebuilt), _opt(d_status), _opt(d_masks_out),
+                                                    _opt(d_symbol_len_out), stream)
         _check(rc, "fec_recover_gather_var_rs_dev", self.lib)
 
     def encode_gather_var_dev(self, d_packet_addrs, d_packet_lens, num_groups: int, k: int, r: int, packet_size: int,
                               d_parity, d_symbol_len_out=None, stream: Optional[int] = None) -> None:
         """encode_gather_dev with a u32 length per packet; address 0 = absent (all zero).  Parity rows
         are full packet_size-byte rows; d_symbol_len_out (nullable): each group's repair payload length."""
-        opt = lambda t: _ptr(t) if t is not None else None   # noqa: E731
-        rc = self.lib.fec_encode_gather_var_rs_dev(self.handle, opt(d_packet_addrs), opt(d_packet_lens), num_groups, k, r,
-                                                   packet_size, opt(d_parity), opt(d_symbol_len_out), stream)
+        rc = self.lib.fec_encode_gather_var_rs_dev(self.handle, _opt(d_packet_addrs), _opt(d_packet_lens), num_groups, k, r,
+                                                   packet_size, _opt(d_parity), _opt(d_symbol_len_out), stream)
         _check(rc, "fec_encode_gather_var_rs_dev", self.lib)
 
     def recover_scatter_dev(self, d_shard_addrs, d_shard_lens, d_dest_addrs, num_groups: int, k: int, r: int,
@@ -360,10 +361,9 @@ class Context:
         instead of an output buffer: d_dest_addrs holds num_groups*k absolute device addresses (u64), and
         data shard j of group g, if the call rebuilds it, is written at entry [g*k + j], exactly the
         group's symbol length of it; an entry of 0 = not wanted.  Every other entry is ignored."""
-        opt = lambda t: _ptr(t) if t is not None else None   # noqa: E731
-        rc = self.lib.fec_recover_scatter_rs_dev(self.handle, opt(d_shard_addrs), opt(d_shard_lens), opt(d_dest_addrs),
-                                                 num_groups, k, r, packet_size, opt(d_status), opt(d_masks_out),
-                                                 opt(d_symbol_len_out), stream)
+        rc = self.lib.fec_recover_scatter_rs_dev(self.handle, _opt(d_shard_addrs), _opt(d_shard_lens), _opt(d_dest_addrs),
+                                                 num_groups, k, r, packet_size, _opt(d_status), _opt(d_masks_out),
+                                                 _opt(d_symbol_len_out), stream)
         _check(rc, "fec_recover_scatter_rs_dev", self.lib)
 
     def encode_scatter_dev(self, d_packet_addrs, d_packet_lens, d_dest_addrs, num_groups: int, k: int, r: int,
@@ -372,9 +372,8 @@ class Context:
         table of destinations instead of a parity buffer: d_dest_addrs holds num_groups*r absolute device
         addresses (u64), and parity row i of group g is written at entry [g*r + i], exactly the group's
         symbol length of it; an entry of 0 = not wanted.  A group with no packet present writes nothing."""
-        opt = lambda t: _ptr(t) if t is not None else None   # noqa: E731
-        rc = self.lib.fec_encode_scatter_rs_dev(self.handle, opt(d_packet_addrs), opt(d_packet_lens), opt(d_dest_addrs),
-                                                num_groups, k, r, packet_size, opt(d_symbol_len_out), stream)
+        rc = self.lib.fec_encode_scatter_rs_dev(self.handle, _opt(d_packet_addrs), _opt(d_packet_lens), _opt(d_dest_addrs),
+                                                num_groups, k, r, packet_size, _opt(d_symbol_len_out), stream)
         _check(rc, "fec_encode_scatter_rs_dev", self.lib)
 
     def decode_prepare(self, k: int, r: int) -> int:

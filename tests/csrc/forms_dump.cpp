@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "fec_forms.hpp"
+#include "forms_shapes.hpp"
 
 using namespace qfec;
 
@@ -96,9 +97,9 @@ void encode_query(uint32_t k, uint32_t r, uint32_t P, int off) {
   } else if (f.K > 0) {
     std::printf("encode_v16 k=%d r=%d off=%d first=1 pol=%d tile=%u aux=0\n", f.K, f.R, f.OFF, f.POL, f.tile);
   } else {
-    for (uint32_t row0 = 0; row0 < r; row0 += 8)  // the launcher's passes of up to 8 rows
-      std::printf("%sencode_v16 k=0 r=%u off=%d first=%d pol=%d tile=%u aux=%u", row0 ? " ; " : "", r - row0 < 8 ? r - row0 : 8,
-                  f.OFF, row0 == 0, f.POL, f.tile, row0);
+    for (uint32_t row0 = 0; row0 < r; row0 += kEncodePassRows)  // the launcher's passes of up to 8 rows
+      std::printf("%sencode_v16 k=0 r=%u off=%d first=%d pol=%d tile=%u aux=%u", row0 ? " ; " : "",
+                  encode_pass_rows(r, row0 / kEncodePassRows), f.OFF, row0 == 0, f.POL, f.tile, row0);
     std::printf("\n");
   }
 }
@@ -118,8 +119,7 @@ int main(int argc, char** argv) {
   std::vector<uint32_t> sizes;
   for (uint32_t P = 1; P <= 2100; ++P) sizes.push_back(P);
   for (uint32_t P : {4096u, 8192u, 8193u, 9000u}) sizes.push_back(P);
-  const uint32_t shapes[][2] = {{10, 3}, {10, 1}, {10, 2}, {4, 2}, {20, 5}, {6, 3}, {7, 4}, {12, 6}, {12, 9}, {16, 4}};
-  for (const auto& kr : shapes)
+  for (const auto& kr : kFormsShapes)
     for (uint32_t P : sizes) {
       for (uint32_t scan : {1u, kDecodeScanGroups}) {
         if (!packed_only) decode_query("in_place", kr[0], kr[1], P, scan), decode_query("slots", kr[0], kr[1], P, scan);

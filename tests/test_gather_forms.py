@@ -1,29 +1,18 @@
 """The address-table calls (fec_recover_gather_rs_dev, fec_encode_gather_rs_dev) without a GPU:
 which recover_gather form csrc/fec_forms.hpp decides at every packet size (through
-tests/csrc/gather_forms_dump.cpp, against a table written from DESIGN.md §5b), and the two calls'
-place in the header, the binding and both libraries.
+tests/csrc/table_forms_dump.cpp gather, against a table written from DESIGN.md §5b), and the two
+calls' place in the header, the binding and both libraries.
 """
-import os
 import re
 import subprocess
-from pathlib import Path
 
 import pytest
 
-REPO = Path(__file__).resolve().parent.parent
-CSRC = REPO / "quic-test_amd" / "csrc"
-DUMP_SRC = Path(__file__).parent / "csrc" / "gather_forms_dump.cpp"
+from forms_support import (COMPILED_SHAPES, CSRC, DUMP_SRC, GATHER_POL, MIN_P, POL_NO_COEF_BRANCH, REPO, RUNTIME_ROWS,
+                           SANITIZE, SHAPES, SIZES, _build, _run)
+
 
 # DESIGN.md §5b, "Recover from an address table"
-POL_NT_LOAD, POL_NT_STORE, POL_NO_COEF_BRANCH, POL_COMPACT_OUT = 1, 2, 4, 1024
-GATHER_POL = POL_NT_LOAD | POL_NT_STORE | POL_COMPACT_OUT
-COMPILED_SHAPES = {(10, 3), (10, 2), (10, 1), (4, 2), (20, 5)}
-RUNTIME_ROWS = 8                                    # rows per pass of the runtime-k form
-SHAPES = [(10, 3), (10, 1), (10, 2), (4, 2), (20, 5), (6, 3), (7, 4), (12, 6), (12, 9), (16, 4)]   # forms_dump's ten
-SIZES = list(range(1, 2101)) + [4096, 8192, 9000]
-MIN_P = 16
-
-
 def expected_launches(k, r, P):
     """The launches of one gather recover by the table, or None where the call is refused."""
     if P < MIN_P:
@@ -35,20 +24,6 @@ def expected_launches(k, r, P):
                                   for m0 in range(0, r, RUNTIME_ROWS)]
 
 
-def _build(d, name, flags):
-    exe = d / name
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", *flags, "-I", str(CSRC), str(DUMP_SRC),
-                    str(CSRC / "fec_knobs.cpp"), "-o", str(exe)], check=True)
-    return exe
-
-
-def _run(exe, *args):
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("QUICFEC_")}
-    out = subprocess.run([str(exe), *args], capture_output=True, text=True, timeout=120, env=clean)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return out.stdout.splitlines(), out.stderr
-
-
 @pytest.fixture(scope="module")
 def dump_dir(tmp_path_factory):
     return tmp_path_factory.mktemp("gather_forms_dump")
@@ -56,11 +31,11 @@ def dump_dir(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def dump_lines(dump_dir):
-    return _run(_build(dump_dir, "plain", []))[0]
+    return _run(_build(dump_dir, "plain", DUMP_SRC, [], [CSRC / "fec_knobs.cpp"]), "gather")[0]
 
 
 def test_decided_gather_forms_equal_the_table(dump_lines):
-    """gather_form (csrc/fec_forms.hpp) at every size of the ten shapes against the table above."""
+    """table_recover_form (csrc/fec_forms.hpp) at every size of the ten shapes against the table above."""
     want = []
     for k, r in SHAPES:
         for P in SIZES:
@@ -76,7 +51,7 @@ def test_decided_gather_forms_equal_the_table(dump_lines):
 def test_compiled_gather_forms_are_the_tables(dump_dir, dump_lines):
     """The list the launcher's dispatch is expanded from holds exactly the forms the table can ask
     for: one per compiled shape and the runtime-k one."""
-    compiled, _ = _run(dump_dir / "plain", "--compiled")
+    compiled, _ = _run(dump_dir / "plain", "gather", "--compiled")
     want = {f"recover_gather k={k} r={r} pol={GATHER_POL} aux=0" for k, r in COMPILED_SHAPES}
     want.add(f"recover_gather k=0 r={RUNTIME_ROWS} pol={GATHER_POL | POL_NO_COEF_BRANCH} aux=0")
     assert len(compiled) == len(want) == 6 and set(compiled) == want
@@ -89,12 +64,11 @@ def test_gather_forms_dump_under_sanitizers(dump_dir, dump_lines):
     """The deciding code as a stand-alone host program under AddressSanitizer and UBSan: one run,
     no report, the same lines.  The runtimes are linked into the program itself, so whatever else
     the environment loads into it, their place in the library list is not in question."""
-    exe = _build(dump_dir, "sanitized", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                         "-static-libasan", "-static-libubsan"])
-    lines, err = _run(exe)
+    exe = _build(dump_dir, "sanitized", DUMP_SRC, SANITIZE, [CSRC / "fec_knobs.cpp"])
+    lines, err = _run(exe, "gather")
     assert lines == dump_lines
     assert "runtime error" not in err and "AddressSanitizer" not in err, err[-2000:]
-    assert _run(exe, "--compiled")[0] == _run(dump_dir / "plain", "--compiled")[0]
+    assert _run(exe, "gather", "--compiled")[0] == _run(dump_dir / "plain", "gather", "--compiled")[0]
 
 
 GATHER_CALLS = ("fec_recover_gather_rs_dev", "fec_encode_gather_rs_dev")

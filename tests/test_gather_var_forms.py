@@ -3,33 +3,20 @@ fec_encode_gather_var_rs_dev) without a GPU:
   * the length-masked piece load (csrc/fec_varlen.hpp) against its byte-wise definition, as a
     stand-alone program run plain and under AddressSanitizer + UBSan -- the sanitized run is the
     check of the no-over-read rule (tests/csrc/varlen_window_test.cpp);
-  * which forms csrc/fec_forms.hpp decides at every packet size (tests/csrc/gather_var_forms_dump.cpp)
+  * which forms csrc/fec_forms.hpp decides at every packet size (tests/csrc/table_forms_dump.cpp gather_var)
     against a table written from DESIGN.md §5b;
   * the two calls' place in the header, the binding and both libraries.
 """
-import os
 import re
 import subprocess
-from pathlib import Path
 
 import pytest
 
-REPO = Path(__file__).resolve().parent.parent
-CSRC = REPO / "quic-test_amd" / "csrc"
-TESTS_CSRC = Path(__file__).parent / "csrc"
-SANITIZE = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+from forms_support import (COMPILED_SHAPES, CSRC, DUMP_SRC, ENCODE_POL, GATHER_POL, MIN_P, POL_NO_COEF_BRANCH, REPO,
+                           RUNTIME_ROWS, SANITIZE, SHAPES, SIZES, TESTS_CSRC, _build, _run)
+
 
 # DESIGN.md §5b, "Variable-length address tables"
-POL_NT_LOAD, POL_NT_STORE, POL_NO_COEF_BRANCH, POL_COMPACT_OUT = 1, 2, 4, 1024
-GATHER_POL = POL_NT_LOAD | POL_NT_STORE | POL_COMPACT_OUT
-ENCODE_POL = POL_NT_STORE
-COMPILED_SHAPES = {(10, 3), (10, 2), (10, 1), (4, 2), (20, 5)}
-RUNTIME_ROWS = 8                                    # rows per pass: the runtime-k recover's and the encode's
-SHAPES = [(10, 3), (10, 1), (10, 2), (4, 2), (20, 5), (6, 3), (7, 4), (12, 6), (12, 9), (16, 4)]   # forms_dump's ten
-SIZES = list(range(1, 2101)) + [4096, 8192, 9000]
-MIN_P = 16
-
-
 def expected_recover_launches(k, r, P):
     """The launches of one variable-length gather recover by the table, or None where it is refused."""
     if P < MIN_P:
@@ -47,20 +34,6 @@ def expected_encode_launches(k, r, P):
         return None
     return [f"encode_gather_var k=0 r={min(RUNTIME_ROWS, r - row0)} first={int(row0 == 0)} pol={ENCODE_POL} aux={row0}"
             for row0 in range(0, r, RUNTIME_ROWS)]
-
-
-def _build(d, name, src, flags, extra=()):
-    exe = d / name
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", *flags, "-I", str(CSRC), str(src), *map(str, extra),
-                    "-o", str(exe)], check=True)
-    return exe
-
-
-def _run(exe, *args):
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("QUICFEC_")}
-    out = subprocess.run([str(exe), *args], capture_output=True, text=True, timeout=120, env=clean)
-    assert out.returncode == 0, (out.stdout[-500:], out.stderr[-2000:])
-    return out.stdout.splitlines(), out.stderr
 
 
 @pytest.fixture(scope="module")
@@ -103,17 +76,17 @@ def test_varlen_window_plain_and_under_sanitizers(work_dir):
 # ------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def dump_exe(work_dir):
-    return _build(work_dir, "dump_plain", TESTS_CSRC / "gather_var_forms_dump.cpp", [], [CSRC / "fec_knobs.cpp"])
+    return _build(work_dir, "dump_plain", DUMP_SRC, [], [CSRC / "fec_knobs.cpp"])
 
 
 @pytest.fixture(scope="module")
 def dump_lines(dump_exe):
-    return _run(dump_exe)[0]
+    return _run(dump_exe, "gather_var")[0]
 
 
 def test_decided_gather_var_forms_equal_the_table(dump_lines):
-    """gather_var_form and the encode's pass structure (csrc/fec_forms.hpp) at every size of the ten
-    shapes against the table above."""
+    """table_recover_form and table_encode_form's pass structure (csrc/fec_forms.hpp) at every size
+    of the ten shapes against the table above."""
     want = []
     for k, r in SHAPES:
         for P in SIZES:
@@ -131,7 +104,7 @@ def test_decided_gather_var_forms_equal_the_table(dump_lines):
 def test_compiled_gather_var_forms_are_the_tables(dump_exe, dump_lines):
     """The list the launcher's dispatch is expanded from holds exactly the forms the table can ask
     for: one per compiled shape and the runtime-k one."""
-    compiled, _ = _run(dump_exe, "--compiled")
+    compiled, _ = _run(dump_exe, "gather_var", "--compiled")
     want = {f"recover_gather_var k={k} r={r} pol={GATHER_POL} aux=0" for k, r in COMPILED_SHAPES}
     want.add(f"recover_gather_var k=0 r={RUNTIME_ROWS} pol={GATHER_POL | POL_NO_COEF_BRANCH} aux=0")
     assert len(compiled) == len(want) == 6 and set(compiled) == want
@@ -141,12 +114,25 @@ def test_compiled_gather_var_forms_are_the_tables(dump_exe, dump_lines):
     assert asked == want
 
 
+def test_gather_var_encode_passes_at_every_row_count(dump_exe):
+    """The encode's pass structure at k = 1, P = 1200 and every r in 1..63 (k + r <= 64) against the
+    table: ceil(r / 8) launches, the first with first=1 from row 0, full passes of 8 rows and a last
+    one of the rest -- every row count 1..8 both as the first pass and as a later one."""
+    rows, _ = _run(dump_exe, "gather_var", "--rows")
+    assert rows == [f"encode_var k=1 r={r} P=1200 | " + " ; ".join(expected_encode_launches(1, r, 1200))
+                    for r in range(1, 64)]
+    assert [ln.count("encode_gather_var") for ln in rows] == [-(-r // RUNTIME_ROWS) for r in range(1, 64)]
+    asked = {re.sub(r"aux=\d+", "aux=0", launch) for ln in rows for launch in ln.split(" | ")[1].split(" ; ")}
+    assert asked == {f"encode_gather_var k=0 r={n} first={f} pol={ENCODE_POL} aux=0"
+                     for n in range(1, RUNTIME_ROWS + 1) for f in (0, 1)}
+
+
 def test_gather_var_forms_dump_under_sanitizers(work_dir, dump_exe, dump_lines):
-    exe = _build(work_dir, "dump_sanitized", TESTS_CSRC / "gather_var_forms_dump.cpp", SANITIZE, [CSRC / "fec_knobs.cpp"])
-    lines, err = _run(exe)
+    exe = _build(work_dir, "dump_sanitized", DUMP_SRC, SANITIZE, [CSRC / "fec_knobs.cpp"])
+    lines, err = _run(exe, "gather_var")
     assert lines == dump_lines
     assert "runtime error" not in err and "AddressSanitizer" not in err, err[-2000:]
-    assert _run(exe, "--compiled")[0] == _run(dump_exe, "--compiled")[0]
+    assert _run(exe, "gather_var", "--compiled")[0] == _run(dump_exe, "gather_var", "--compiled")[0]
 
 
 # ------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
     symbol length, as a stand-alone program run plain and under AddressSanitizer + UBSan -- the
     sanitized run is the check that no byte before a destination or at or past destination + L is
     written and that a NULL destination is never dereferenced (tests/csrc/scatter_encode_cut_test.cpp);
-  * which forms csrc/fec_forms.hpp decides at every packet size (tests/csrc/scatter_encode_forms_dump.cpp)
+  * which forms csrc/fec_forms.hpp decides at every packet size (tests/csrc/table_forms_dump.cpp scatter_encode)
     against a table written from DESIGN.md §5b;
   * the call's place in the header, the binding and both libraries, and the trace name.
 """
@@ -13,7 +13,7 @@ from pathlib import Path
 
 import pytest
 
-from test_gather_var_forms import CSRC, ENCODE_POL, MIN_P, REPO, RUNTIME_ROWS, SANITIZE, SHAPES, SIZES, TESTS_CSRC, _build, _run
+from forms_support import CSRC, DUMP_SRC, ENCODE_POL, MIN_P, REPO, RUNTIME_ROWS, SANITIZE, SHAPES, SIZES, TESTS_CSRC, _build, _run
 
 CUT_SIZES = [16, 17, 260, 1025, 1200, 2100]
 
@@ -86,12 +86,12 @@ def test_store_cut_plain_and_under_sanitizers(work_dir):
 # ------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def dump_exe(work_dir):
-    return _build(work_dir, "dump_plain", TESTS_CSRC / "scatter_encode_forms_dump.cpp", [], [CSRC / "fec_knobs.cpp"])
+    return _build(work_dir, "dump_plain", DUMP_SRC, [], [CSRC / "fec_knobs.cpp"])
 
 
 @pytest.fixture(scope="module")
 def dump_lines(dump_exe):
-    return _run(dump_exe)[0]
+    return _run(dump_exe, "scatter_encode")[0]
 
 
 def _line(k, r, P, var):
@@ -100,7 +100,7 @@ def _line(k, r, P, var):
 
 
 def test_decided_scatter_encode_forms_equal_the_table(dump_lines):
-    """scatter_encode_form (csrc/fec_forms.hpp) at every size of the ten shapes, without and with a
+    """table_encode_form (csrc/fec_forms.hpp) at every size of the ten shapes, without and with a
     length table, against the table above: refused below 16, one launch per 8 rows."""
     want = [_line(k, r, P, var) for k, r in SHAPES for P in SIZES for var in (0, 1)]
     assert len(dump_lines) == 2 * len(SHAPES) * len(SIZES)
@@ -115,8 +115,8 @@ def test_compiled_scatter_encode_forms_are_the_tables(dump_exe, dump_lines):
     """The list the launcher's dispatch is expanded from holds exactly the forms the table can ask
     for over every r in 1..63 (k + r <= 64): 1..8 rows as the first pass and as a later one, without
     and with the length table."""
-    compiled, _ = _run(dump_exe, "--compiled")
-    rows, _ = _run(dump_exe, "--rows")
+    compiled, _ = _run(dump_exe, "scatter_encode", "--compiled")
+    rows, _ = _run(dump_exe, "scatter_encode", "--rows")
     assert rows == [_line(1, r, 1200, var) for r in range(1, 64) for var in (0, 1)]
     asked = {re.sub(r"aux=\d+", "aux=0", launch) for ln in rows + dump_lines if not ln.endswith("refused")
              for launch in ln.split(" | ")[1].split(" ; ")}
@@ -127,19 +127,19 @@ def test_compiled_scatter_encode_forms_are_the_tables(dump_exe, dump_lines):
 
 
 def test_scatter_encode_forms_dump_under_sanitizers(work_dir, dump_exe, dump_lines):
-    exe = _build(work_dir, "dump_sanitized", TESTS_CSRC / "scatter_encode_forms_dump.cpp", SANITIZE, [CSRC / "fec_knobs.cpp"])
-    lines, err = _run(exe)
+    exe = _build(work_dir, "dump_sanitized", DUMP_SRC, SANITIZE, [CSRC / "fec_knobs.cpp"])
+    lines, err = _run(exe, "scatter_encode")
     assert lines == dump_lines
     assert "runtime error" not in err and "AddressSanitizer" not in err, err[-2000:]
-    assert _run(exe, "--compiled")[0] == _run(dump_exe, "--compiled")[0]
-    assert _run(exe, "--rows")[0] == _run(dump_exe, "--rows")[0]
+    assert _run(exe, "scatter_encode", "--compiled")[0] == _run(dump_exe, "scatter_encode", "--compiled")[0]
+    assert _run(exe, "scatter_encode", "--rows")[0] == _run(dump_exe, "scatter_encode", "--rows")[0]
 
 
 def test_scatter_encode_launch_ids_equal_the_binding(dump_exe, quicfec_mod):
     """ScatterEncodeLaunchForm (csrc/fec_knobs.hpp) one for one against
     quicfec.SCATTER_ENCODE_LAUNCH_FORMS: by the compiled numbers and by the enum's text; numbered on
     from 25, apart from the four other lists."""
-    ids = {int(ln.split()[1]): ln.split()[0] for ln in _run(dump_exe, "--ids")[0]}
+    ids = {int(ln.split()[1]): ln.split()[0] for ln in _run(dump_exe, "scatter_encode", "--ids")[0]}
     assert ids == quicfec_mod.SCATTER_ENCODE_LAUNCH_FORMS == {25: "encode_scatter"}
     hpp = (CSRC / "fec_knobs.hpp").read_text()
     enum = re.search(r"enum class ScatterEncodeLaunchForm : int64_t \{(.*?)\};", hpp, re.S).group(1)

@@ -3,7 +3,7 @@
     length, as a stand-alone program run plain and under AddressSanitizer + UBSan -- the sanitized
     run is the check that no byte before a destination or at or past destination + L is written and
     that a NULL destination is never dereferenced (tests/csrc/scatter_cut_test.cpp);
-  * which forms csrc/fec_forms.hpp decides at every packet size (tests/csrc/scatter_forms_dump.cpp)
+  * which forms csrc/fec_forms.hpp decides at every packet size (tests/csrc/table_forms_dump.cpp scatter)
     against a table written from DESIGN.md §5b;
   * the call's place in the header, the binding and both libraries, and the trace names.
 """
@@ -13,8 +13,8 @@ from pathlib import Path
 
 import pytest
 
-from test_gather_var_forms import (COMPILED_SHAPES, CSRC, GATHER_POL, MIN_P, POL_NO_COEF_BRANCH, REPO, RUNTIME_ROWS,
-                                   SANITIZE, SHAPES, SIZES, TESTS_CSRC, _build, _run)
+from forms_support import (COMPILED_SHAPES, CSRC, DUMP_SRC, GATHER_POL, MIN_P, POL_NO_COEF_BRANCH, REPO, RUNTIME_ROWS,
+                           SANITIZE, SHAPES, SIZES, TESTS_CSRC, _build, _run)
 
 CUT_SIZES = [16, 17, 260, 1025, 1200, 2100]
 LANES = 64
@@ -90,16 +90,16 @@ def test_store_cut_plain_and_under_sanitizers(work_dir):
 # ------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def dump_exe(work_dir):
-    return _build(work_dir, "dump_plain", TESTS_CSRC / "scatter_forms_dump.cpp", [], [CSRC / "fec_knobs.cpp"])
+    return _build(work_dir, "dump_plain", DUMP_SRC, [], [CSRC / "fec_knobs.cpp"])
 
 
 @pytest.fixture(scope="module")
 def dump_lines(dump_exe):
-    return _run(dump_exe)[0]
+    return _run(dump_exe, "scatter")[0]
 
 
 def test_decided_scatter_forms_equal_the_table(dump_lines):
-    """scatter_form (csrc/fec_forms.hpp) at every size of the ten shapes, without and with a length
+    """table_recover_form (csrc/fec_forms.hpp) at every size of the ten shapes, without and with a length
     table, against the table above."""
     want = []
     for k, r in SHAPES:
@@ -116,7 +116,7 @@ def test_decided_scatter_forms_equal_the_table(dump_lines):
 def test_compiled_scatter_forms_are_the_tables(dump_exe, dump_lines):
     """The list the launcher's dispatch is expanded from holds exactly the forms the table can ask
     for: per compiled shape and for runtime k one without and one with the length table."""
-    compiled, _ = _run(dump_exe, "--compiled")
+    compiled, _ = _run(dump_exe, "scatter", "--compiled")
     want = {f"recover_scatter k={k} r={r} first={v} pol={GATHER_POL} aux=0" for k, r in COMPILED_SHAPES for v in (0, 1)}
     want |= {f"recover_scatter k=0 r={RUNTIME_ROWS} first={v} pol={GATHER_POL | POL_NO_COEF_BRANCH} aux=0" for v in (0, 1)}
     assert len(compiled) == len(want) == 12 and set(compiled) == want
@@ -126,8 +126,8 @@ def test_compiled_scatter_forms_are_the_tables(dump_exe, dump_lines):
 
 
 def test_scatter_forms_dump_under_sanitizers(work_dir, dump_exe, dump_lines):
-    exe = _build(work_dir, "dump_sanitized", TESTS_CSRC / "scatter_forms_dump.cpp", SANITIZE, [CSRC / "fec_knobs.cpp"])
-    lines, err = _run(exe)
+    exe = _build(work_dir, "dump_sanitized", DUMP_SRC, SANITIZE, [CSRC / "fec_knobs.cpp"])
+    lines, err = _run(exe, "scatter")
     assert lines == dump_lines
     assert "runtime error" not in err and "AddressSanitizer" not in err, err[-2000:]
 
@@ -135,7 +135,7 @@ def test_scatter_forms_dump_under_sanitizers(work_dir, dump_exe, dump_lines):
 def test_scatter_launch_ids_equal_the_binding(dump_exe, quicfec_mod):
     """ScatterLaunchForm (csrc/fec_knobs.hpp) one for one against quicfec.SCATTER_LAUNCH_FORMS: by
     the compiled numbers and by the enum's text; numbered on from 23, apart from the other lists."""
-    ids = {int(ln.split()[1]): ln.split()[0] for ln in _run(dump_exe, "--ids")[0]}
+    ids = {int(ln.split()[1]): ln.split()[0] for ln in _run(dump_exe, "scatter", "--ids")[0]}
     assert ids == quicfec_mod.SCATTER_LAUNCH_FORMS == {23: "classify_scatter", 24: "recover_scatter"}
     hpp = (CSRC / "fec_knobs.hpp").read_text()
     enum = re.search(r"enum class ScatterLaunchForm : int64_t \{(.*?)\};", hpp, re.S).group(1)
