@@ -1101,15 +1101,15 @@ bool coalesce_legacy_encode(int device, const uint8_t* slab, const uint32_t* off
   if (env_long("QUICFEC_COALESCE", 1) == 0 || g_shut.load(std::memory_order_acquire)) return false;
   if (num_groups > static_cast<uint64_t>(std::max(0L, env_long("QUICFEC_COALESCE_MAX_GROUPS", 64)))) return false;
   void *sdev = nullptr, *rdev = nullptr;
-  const HostMem sm = classify_host_pointer(slab, &sdev);
-  const HostMem rm = classify_host_pointer(repair_out, &rdev);
-  if (sm == HostMem::kDevice || rm == HostMem::kDevice || classify_host_pointer(offsets, nullptr) == HostMem::kDevice)
+  const Mem sm = classify_ptr(slab, &sdev);
+  const Mem rm = classify_ptr(repair_out, &rdev);
+  if (sm == Mem::kDevice || rm == Mem::kDevice || classify_ptr(offsets) == Mem::kDevice)
     return false;  // device-resident callers batch by themselves
-  const bool repair_pinned = rm == HostMem::kPinned;
+  const bool repair_pinned = rm == Mem::kPinned;
   // The resident encoder: packets addressed in the caller's page-locked slab, or (VRAM ring)
   // copied into the slot from any host memory.
   const bool slab_addressable =
-      sm == HostMem::kPinned && reinterpret_cast<uint64_t>(sdev) + 0xFFFFFFFFull + packet_size <= kServerAddrMask;
+      sm == Mem::kPinned && reinterpret_cast<uint64_t>(sdev) + 0xFFFFFFFFull + packet_size <= kServerAddrMask;
   if (env_long("QUICFEC_RESIDENT", 1) != 0 && Resident::fits(num_groups, packet_size, repair_pinned) &&
       reinterpret_cast<uint64_t>(rdev) <= kServerAddrMask) {
     Resident* r = resident_for(device);
@@ -1129,7 +1129,7 @@ bool coalesce_legacy_encode(int device, const uint8_t* slab, const uint32_t* off
   Coalescer* c = coalescer_for(device, packet_size);
   if (!c || num_groups > c->capacity() / 2) return false;
   const uint64_t t_for = now_ns();
-  *rc = c->encode(slab, sm == HostMem::kPinned ? static_cast<const uint8_t*>(sdev) : nullptr, offsets, num_groups,
+  *rc = c->encode(slab, sm == Mem::kPinned ? static_cast<const uint8_t*>(sdev) : nullptr, offsets, num_groups,
                   repair_out, stream);
   static std::atomic<int> stamps_left{test_knob(TestKnob::kCoalesceStamps, 0) != 0 ? 3 : 0};
   if (stamps_left.load(std::memory_order_relaxed) > 0 && stamps_left.fetch_sub(1) > 0)  // diagnostic

@@ -7,13 +7,12 @@
 #include <cstdint>
 
 #include "fec_hip.h"
+#include "fec_routes.hpp"
 
 namespace qfec {
 
-enum class HostMem { kPageable, kPinned, kDevice };
-
-// Where `p` lives; for page-locked host memory *dev = the address kernels use for it.
-HostMem classify_host_pointer(const void* p, void** dev);
+// Where `p` lives; `dev` (optional): for page-locked host memory, the address kernels use for `p`.
+Mem classify_ptr(const void* p, void** dev = nullptr);
 
 // Row 0 .. r-1 of G groups of k packets at absolute device addresses d_addr[g * k + j] (row 0
 // = XOR), parity row (g, i) at d_parity + (g * r + i) * P; queued on `s`, which belongs to

@@ -33,7 +33,12 @@
 #include "fec_internal.hpp"
 #include "fec_kernels.hpp"
 #include "fec_knobs.hpp"
+#include "fec_routes.hpp"
 #include "gf256.hpp"
+
+using qfec::classify_ptr;
+using qfec::kPipeSlots;
+using qfec::Mem;
 
 #define QFEC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -193,8 +198,6 @@ void parallel_for(uint64_t n, uint64_t min_per_thread, F&& f) {
   for (auto& x : th) x.join();
 }
 
-enum class Mem { kHost, kPinned, kDevice };
-
 // Page-locked buffers this library handed out (fec_alloc_slab / _numa / fec_alloc_repair_buffer).
 // The Go wrapper passes the same two of them to every legacy call (fec_cgo.go:64, :76, :138);
 // finding them here keeps hipPointerGetAttributes -- a runtime lock and a lookup per pointer --
@@ -233,8 +236,10 @@ bool pinned_lookup(const void* p, void** dev) {
   return true;
 }
 
-// `dev` (optional): for page-locked host memory, the address kernels use for `p`.
-Mem classify_ptr(const void* p, void** dev = nullptr) {
+}  // namespace
+
+// fec_internal.hpp (the coalescer classifies its callers' buffers too)
+Mem qfec::classify_ptr(const void* p, void** dev) {
   if (dev) *dev = nullptr;
   if (!p) return Mem::kHost;
   if (pinned_lookup(p, dev)) return Mem::kPinned;
@@ -253,31 +258,17 @@ Mem classify_ptr(const void* p, void** dev = nullptr) {
   return Mem::kHost;
 }
 
-// Host-resident calls up to small_call_bytes() (data + parity bytes) run zero-copy: the
-// kernels address page-locked host memory directly over PCIe -- the caller's buffers when
-// they are page-locked (fec_alloc_slab), else the context's page-locked staging, filled
-// and drained by CPU memcpy.  No DMA copies: one kernel launch and one stream synchronize
-// per call, where the DMA path pays a copy-engine round trip per buffer.  Measured
-// (tools/latency.cpp, k=10 r=3 1200 B, profiles/r01_latency_sweep.txt): one group 33 -> 15 us
-// (legacy fec_encode_batch).  With page-locked buffers zero-copy beats the DMA pipeline at
-// every size (4096 groups: 942 vs 1013 us encode, 947 vs 1281 us decode; 1M groups, 12 GB:
-// encode 52.0 vs 48.7 GiB/s, 2-erasure decode 52.4 vs 34.8, C5 sparse-loss decode 454 vs
-// 243; profiles/r01_e2e_zero_copy.txt), so it has no limit; staged pageable buffers pay a
-// CPU memcpy and break even near 3 MB.  QUICFEC_SMALL_CALL_BYTES overrides both limits
-// (0 = always DMA).
-constexpr uint64_t kZeroCopyPinnedBytes = ~0ull;
+namespace {
 
 // Completion wait of the zero-copy calls.  The runtime's blocking wait: polling
 // hipStreamQuery from the calling thread measured slower (one group: 20 vs 15.5 us;
 // profiles/r01_latency_sweep.txt).
 hipError_t wait_stream(hipStream_t s) { return hipStreamSynchronize(s); }
 
-constexpr uint64_t kZeroCopyStagedBytes = 2ull << 20;
-uint64_t small_call_bytes(bool all_pinned) {  // read per call: tests switch paths in one process
+// The zero-copy limits of this call (fec_routes.hpp); QUICFEC_SMALL_CALL_BYTES overrides both.
+qfec::SmallCallLimits small_call_limits() {  // read per call: tests switch paths in one process
   const char* v = std::getenv("QUICFEC_SMALL_CALL_BYTES");
-  const long long x = v && *v ? std::atoll(v) : -1;
-  if (x >= 0) return static_cast<uint64_t>(x);
-  return all_pinned ? kZeroCopyPinnedBytes : kZeroCopyStagedBytes;
+  return qfec::small_call_limits(v && *v ? std::atoll(v) : -1);
 }
 
 }  // namespace
@@ -289,18 +280,13 @@ struct PipeSlot {
   HostBuf h_in, h_par, h_mask;          // compacted host decode staging
   std::vector<uint64_t> h_groups;        // the groups gathered into this slot's staging
 };
-constexpr int kPipeSlots = 3;
-constexpr uint64_t kPipeChunkBytes = 64ull << 20;  // data bytes per pipelined chunk
 
 // QUICFEC_PIPE_CHUNK_BYTES overrides the chunk size (tests use small chunks to run many).
 uint64_t pipe_chunk_bytes() {
   const char* v = std::getenv("QUICFEC_PIPE_CHUNK_BYTES");
   const long long x = v ? std::atoll(v) : 0;
-  return x > 0 ? static_cast<uint64_t>(x) : kPipeChunkBytes;
+  return x > 0 ? static_cast<uint64_t>(x) : qfec::kPipeChunkBytes;
 }
-// Host-resident decode moves only the groups to rebuild when they are at most 1 in
-// kCompactMaxShare of the batch; above that the whole batch streams through the pipeline.
-constexpr uint64_t kCompactMaxShare = 2;
 
 // A caller stream's decode workspace (stream_workspace).
 struct StreamWorkspace {
@@ -377,6 +363,33 @@ struct FECEncoderCtx {
 };
 
 namespace {
+
+// What every exported call that returns a code is wrapped in: the thread's message cleared, f()
+// run, and a non-zero code's message copied into the context (fec_ctx_last_error).
+template <class F>
+int api_call(FECEncoderCtx* ctx, F&& f) {
+  g_last_error.clear();
+  const int rc = f();
+  if (rc != FEC_OK && ctx != nullptr) {
+    std::lock_guard<std::mutex> lk(ctx->err_mu);
+    ctx->last_error = g_last_error.empty() ? "error code " + std::to_string(rc) : g_last_error;
+  }
+  return rc;
+}
+
+// The context locked and its device bound for the scope.  rc: FEC_OK, or FEC_ERR_NODEV when the
+// device could not be bound -- with the message "<what>: cannot bind device N" for the calls that
+// name themselves, with none for the others.
+struct CtxBound {
+  std::lock_guard<std::mutex> lk;
+  DeviceGuard dg;
+  int rc = FEC_OK;
+  explicit CtxBound(FECEncoderCtx* ctx, const char* what = nullptr) : lk(ctx->mu), dg(ctx->device) {
+    if (dg.ok) return;
+    if (what) set_error("%s: cannot bind device %d", what, ctx->device);
+    rc = FEC_ERR_NODEV;
+  }
+};
 
 // The first kernel launched on a device loads the library's code object there (all kernels of
 // fec_kernels.hip at once), and the resident encoder's first call allocates its page-locked
@@ -625,21 +638,43 @@ qfec::LevelMeta level_meta(const qfec::CodebookLayout& layout, uint32_t r) {
   return m;
 }
 
-int decode_dev_locked(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
-                      const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
-                      uint8_t* d_status, hipStream_t s, DevBuf* rec = nullptr,
-                      uint8_t* d_out = nullptr, double need_share = -1.0, bool compact_out = false,
-                      uint32_t* row_start = nullptr, uint64_t* row_total = nullptr) {
+// One device-resident decode, contiguous layout (decode_dev_locked).  Every pointer is a device
+// address (of device memory, or of page-locked host memory for the zero-copy calls).
+struct DecodeCall {
+  uint8_t* data = nullptr;         // the data shards; rebuilt in place unless `out` is set
+  const uint8_t* parity = nullptr;
+  const uint64_t* masks = nullptr;
+  struct { uint64_t G; uint32_t k, r, P; } shape{};
+  uint8_t* status = nullptr;       // nullable
+  hipStream_t stream = nullptr;
+  DevBuf* rec = nullptr;           // a pipeline slot's record-offset buffer; NULL: the stream's workspace
+  uint8_t* out = nullptr;          // where rebuilt shards are stored; NULL: in place in `data`
+  double need_share = -1.0;        // share of groups to rebuild, from a host scan; < 0: the context's hint
+  bool compact_out = false;        // rebuilt rows one run per group, `data` only read (DecodeLaunch)
+  uint32_t* row_start = nullptr;   // set: packed rows (fec_recover_batch_rs_dev_packed), written
+  uint64_t* row_total = nullptr;   //   with them, nullable: all rows
+};
+
+// Caller holds ctx->mu and the device.
+int decode_dev_locked(FECEncoderCtx* ctx, const DecodeCall& c) {
+  // under the names the failure messages below quote (QFEC_HIP reports the failing expression)
+  const auto [G, k, r, P] = c.shape;
+  const uint64_t* const d_masks = c.masks;
+  uint8_t *const d_status = c.status, *const d_out = c.out;
+  DevBuf* const rec = c.rec;
+  uint32_t* const row_start = c.row_start;
+  uint64_t* const row_total = c.row_total;
+  const hipStream_t s = c.stream;
   DecodePlan* plan = nullptr;
   int rc = get_decode_plan(ctx, k, r, &plan);
   if (rc != FEC_OK) return rc;
   qfec::DecodeLaunch a;
-  a.data = d_data;
-  a.parity = d_parity;
+  a.data = c.data;
+  a.parity = c.parity;
   a.masks = d_masks;
   a.rec_off = nullptr;
   a.out = d_out;
-  a.compact_out = compact_out;
+  a.compact_out = c.compact_out;
   a.status = d_status;
   a.codebook = plan->codebook.as<uint8_t>();
   a.binom = ctx->d_binom.as<uint64_t>();
@@ -652,7 +687,7 @@ int decode_dev_locked(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_pari
   // Groups per wave of the mask-addressed form: the scan form when the caller knows that
   // few groups need a rebuild (need_share, from a host scan of the masks); device-resident
   // callers get one wave per group (the test library's TestKnob::kDecodeScan overrides it).
-  if (need_share < 0.0) need_share = ctx->decode_need_share;
+  const double need_share = c.need_share < 0.0 ? ctx->decode_need_share : c.need_share;
   if (need_share >= 0.0 && need_share < qfec::kDecodeScanMaxShare) a.scan = qfec::kDecodeScanGroups;
   a.scan = static_cast<uint32_t>(qfec::test_knob(qfec::TestKnob::kDecodeScan, a.scan));
   // The kernel form of this call (fec_forms.hpp); what is attached to `a` below -- codebook,
@@ -683,8 +718,8 @@ int decode_dev_locked(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_pari
     }
     if (packed == qfec::PackedForm::kRuns) {
       qfec::RunsLaunch ra{};
-      ra.data = d_data;
-      ra.parity = d_parity;
+      ra.data = c.data;
+      ra.parity = c.parity;
       ra.masks = d_masks;
       ra.groups = G;
       ra.k = k;
@@ -764,51 +799,63 @@ int ensure_pipe(FECEncoderCtx* ctx) {
   return FEC_OK;
 }
 
-// Host-resident batches: chunks of ~64 MB of data flow H2D -> kernel -> D2H, chunk c on
-// pipeline slot c % 3, so the copy engines (H2D and D2H run on separate DMA engines) and
-// the kernels of neighbouring chunks overlap.  Page-locked host buffers (fec_alloc_slab)
-// make the copies asynchronous; pageable ones still work, with less overlap.
-int encode_host_pipelined(FECEncoderCtx* ctx, const uint8_t* data, uint64_t G, uint32_t k, uint32_t r,
-                          uint32_t P, uint8_t* parity_out) {
+int sync_slot(PipeSlot& p) {
+  QFEC_HIP(hipStreamSynchronize(p.s));
+  return FEC_OK;
+}
+
+// The chunk pipeline of the host-resident batches: N groups of in_g data bytes each in chunks of
+// ~64 MB of data (fec_routes.hpp), chunk c on pipeline slot c % 3.  ensure(p, cg) grows slot p's
+// buffers for chunks of cg groups; body(sl, first, n) queues the groups [first, first + n) on slot
+// sl; retire(p) waits for slot p's chunk and finishes it: for every slot at the end of the call
+// and, with retire_before_refill, before a slot takes its next chunk.
+template <class Ensure, class Body, class Retire>
+int run_pipeline(FECEncoderCtx* ctx, uint64_t N, uint64_t in_g, bool retire_before_refill, Ensure ensure, Body body,
+                 Retire retire) {
   int rc = ensure_pipe(ctx);
   if (rc != FEC_OK) return rc;
   PipeDrain drain{ctx};
-  const uint64_t in_g = uint64_t(k) * P, out_g = uint64_t(r) * P;
-  uint64_t cg = pipe_chunk_bytes() / in_g;
-  cg = cg == 0 ? 1 : (cg > G ? G : cg);
-  for (auto& p : ctx->pipe) {
-    QFEC_HIP(p.in.ensure(cg * in_g));
-    QFEC_HIP(p.par.ensure(cg * out_g));
-  }
+  const uint64_t cg = qfec::pipe_chunk_groups(pipe_chunk_bytes(), in_g, N);
+  for (auto& p : ctx->pipe)
+    if ((rc = ensure(p, cg)) != FEC_OK) return rc;
   uint64_t c = 0;
-  for (uint64_t g0 = 0; g0 < G; g0 += cg, ++c) {
+  for (uint64_t first = 0; first < N; first += cg, ++c) {
     PipeSlot& sl = ctx->pipe[c % kPipeSlots];
-    const uint64_t n = (G - g0 < cg) ? G - g0 : cg;
-    QFEC_HIP(hipMemcpyAsync(sl.in.ptr, data + g0 * in_g, n * in_g, hipMemcpyHostToDevice, sl.s));
-    rc = encode_dev_locked(ctx, sl.in.as<uint8_t>(), nullptr, qfec::OffsetKind::kNone, n, k, r, P,
-                           sl.par.as<uint8_t>(), sl.s);
-    if (rc != FEC_OK) return rc;
-    QFEC_HIP(hipMemcpyAsync(parity_out + g0 * out_g, sl.par.ptr, n * out_g, hipMemcpyDeviceToHost, sl.s));
+    if (retire_before_refill && (rc = retire(sl)) != FEC_OK) return rc;
+    if ((rc = body(sl, first, N - first < cg ? N - first : cg)) != FEC_OK) return rc;
   }
-  for (auto& p : ctx->pipe) QFEC_HIP(hipStreamSynchronize(p.s));
+  for (auto& p : ctx->pipe)
+    if ((rc = retire(p)) != FEC_OK) return rc;
   drain.done = true;
   return FEC_OK;
 }
 
+// Host-resident batches: H2D -> kernel -> D2H per chunk.  Page-locked host buffers
+// (fec_alloc_slab) make the copies asynchronous; pageable ones still work, with less overlap.
+int encode_host_pipelined(FECEncoderCtx* ctx, const uint8_t* data, uint64_t G, uint32_t k, uint32_t r,
+                          uint32_t P, uint8_t* parity_out) {
+  const uint64_t in_g = uint64_t(k) * P, out_g = uint64_t(r) * P;
+  return run_pipeline(
+      ctx, G, in_g, false,
+      [&](PipeSlot& p, uint64_t cg) {
+        QFEC_HIP(p.in.ensure(cg * in_g));
+        QFEC_HIP(p.par.ensure(cg * out_g));
+        return FEC_OK;
+      },
+      [&](PipeSlot& sl, uint64_t g0, uint64_t n) {
+        QFEC_HIP(hipMemcpyAsync(sl.in.ptr, data + g0 * in_g, n * in_g, hipMemcpyHostToDevice, sl.s));
+        const int rc = encode_dev_locked(ctx, sl.in.as<uint8_t>(), nullptr, qfec::OffsetKind::kNone, n, k, r, P,
+                                         sl.par.as<uint8_t>(), sl.s);
+        if (rc != FEC_OK) return rc;
+        QFEC_HIP(hipMemcpyAsync(parity_out + g0 * out_g, sl.par.ptr, n * out_g, hipMemcpyDeviceToHost, sl.s));
+        return FEC_OK;
+      },
+      sync_slot);
+}
+
 int decode_host_pipelined(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* parity, const uint64_t* masks,
                           uint64_t G, uint32_t k, uint32_t r, uint32_t P, uint8_t* status_out) {
-  int rc = ensure_pipe(ctx);
-  if (rc != FEC_OK) return rc;
-  PipeDrain drain{ctx};
   const uint64_t in_g = uint64_t(k) * P, par_g = uint64_t(r) * P;
-  uint64_t cg = pipe_chunk_bytes() / in_g;
-  cg = cg == 0 ? 1 : (cg > G ? G : cg);
-  for (auto& p : ctx->pipe) {
-    QFEC_HIP(p.in.ensure(cg * in_g));
-    QFEC_HIP(p.par.ensure(cg * par_g));
-    QFEC_HIP(p.mask.ensure(cg * 8));
-    QFEC_HIP(p.status.ensure(cg));
-  }
   // Page-locked data: the kernel stores the rebuilt shards straight into host memory
   // (zero-copy PCIe writes of ~e*P bytes per group) instead of a D2H of the whole chunk.
   uint8_t* host_dev = nullptr;
@@ -820,23 +867,31 @@ int decode_host_pipelined(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* pari
     else
       (void)hipGetLastError();
   }
-  uint64_t c = 0;
-  for (uint64_t g0 = 0; g0 < G; g0 += cg, ++c) {
-    PipeSlot& sl = ctx->pipe[c % kPipeSlots];
-    const uint64_t n = (G - g0 < cg) ? G - g0 : cg;
-    QFEC_HIP(hipMemcpyAsync(sl.in.ptr, data + g0 * in_g, n * in_g, hipMemcpyHostToDevice, sl.s));
-    QFEC_HIP(hipMemcpyAsync(sl.par.ptr, parity + g0 * par_g, n * par_g, hipMemcpyHostToDevice, sl.s));
-    QFEC_HIP(hipMemcpyAsync(sl.mask.ptr, masks + g0, n * 8, hipMemcpyHostToDevice, sl.s));
-    rc = decode_dev_locked(ctx, sl.in.as<uint8_t>(), sl.par.as<uint8_t>(), sl.mask.as<uint64_t>(), n, k, r, P,
-                           sl.status.as<uint8_t>(), sl.s, &sl.rec, host_dev ? host_dev + g0 * in_g : nullptr);
-    if (rc != FEC_OK) return rc;
-    if (!host_dev)
-      QFEC_HIP(hipMemcpyAsync(data + g0 * in_g, sl.in.ptr, n * in_g, hipMemcpyDeviceToHost, sl.s));
-    QFEC_HIP(hipMemcpyAsync(status_out + g0, sl.status.ptr, n, hipMemcpyDeviceToHost, sl.s));
-  }
-  for (auto& p : ctx->pipe) QFEC_HIP(hipStreamSynchronize(p.s));
-  drain.done = true;
-  return FEC_OK;
+  return run_pipeline(
+      ctx, G, in_g, false,
+      [&](PipeSlot& p, uint64_t cg) {
+        QFEC_HIP(p.in.ensure(cg * in_g));
+        QFEC_HIP(p.par.ensure(cg * par_g));
+        QFEC_HIP(p.mask.ensure(cg * 8));
+        QFEC_HIP(p.status.ensure(cg));
+        return FEC_OK;
+      },
+      [&](PipeSlot& sl, uint64_t g0, uint64_t n) {
+        QFEC_HIP(hipMemcpyAsync(sl.in.ptr, data + g0 * in_g, n * in_g, hipMemcpyHostToDevice, sl.s));
+        QFEC_HIP(hipMemcpyAsync(sl.par.ptr, parity + g0 * par_g, n * par_g, hipMemcpyHostToDevice, sl.s));
+        QFEC_HIP(hipMemcpyAsync(sl.mask.ptr, masks + g0, n * 8, hipMemcpyHostToDevice, sl.s));
+        DecodeCall c;
+        c.data = sl.in.as<uint8_t>(), c.parity = sl.par.as<uint8_t>(), c.masks = sl.mask.as<uint64_t>();
+        c.shape = {n, k, r, P}, c.status = sl.status.as<uint8_t>(), c.stream = sl.s, c.rec = &sl.rec;
+        c.out = host_dev ? host_dev + g0 * in_g : nullptr;
+        const int rc = decode_dev_locked(ctx, c);
+        if (rc != FEC_OK) return rc;
+        if (!host_dev)
+          QFEC_HIP(hipMemcpyAsync(data + g0 * in_g, sl.in.ptr, n * in_g, hipMemcpyDeviceToHost, sl.s));
+        QFEC_HIP(hipMemcpyAsync(status_out + g0, sl.status.ptr, n, hipMemcpyDeviceToHost, sl.s));
+        return FEC_OK;
+      },
+      sync_slot);
 }
 
 // Host-resident decode when few groups lost data shards (e.g. the satellite profile, iid
@@ -849,25 +904,9 @@ int decode_host_pipelined(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* pari
 // else needs no device work.
 int decode_host_compacted(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* parity, const uint64_t* masks,
                           const std::vector<uint64_t>& need, uint32_t k, uint32_t r, uint32_t P) {
-  int rc = ensure_pipe(ctx);
-  if (rc != FEC_OK) return rc;
-  PipeDrain drain{ctx};
-  const uint64_t N = need.size();
   const uint64_t in_g = uint64_t(k) * P, par_g = uint64_t(r) * P;
-  uint64_t cg = pipe_chunk_bytes() / in_g;
-  cg = cg == 0 ? 1 : (cg > N ? N : cg);
-  for (auto& p : ctx->pipe) {
-    QFEC_HIP(p.in.ensure(cg * in_g));
-    QFEC_HIP(p.par.ensure(cg * par_g));
-    QFEC_HIP(p.mask.ensure(cg * 8));
-    QFEC_HIP(p.h_in.ensure(cg * in_g));
-    QFEC_HIP(p.h_par.ensure(cg * par_g));
-    QFEC_HIP(p.h_mask.ensure(cg * 8));
-    p.h_groups.clear();
-  }
-  const uint64_t kmask = (1ull << k) - 1;
   // Rebuilt packets of the slot's last chunk: D2H landed in h_in; copy the erased ones out.
-  auto scatter = [&](PipeSlot& sl) -> int {
+  const auto scatter = [&](PipeSlot& sl) {
     if (sl.h_groups.empty()) return FEC_OK;
     QFEC_HIP(hipStreamSynchronize(sl.s));
     const uint8_t* src = sl.h_in.as<uint8_t>();
@@ -875,48 +914,52 @@ int decode_host_compacted(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* pari
     parallel_for(sl.h_groups.size(), 512, [&](uint64_t b, uint64_t e) {
       for (uint64_t i = b; i < e; ++i) {
         const uint64_t g = gl[i];
-        for (uint64_t lost = masks[g] & kmask; lost; lost &= lost - 1) {
-          const uint32_t j = static_cast<uint32_t>(__builtin_ctzll(lost));
+        qfec::for_each_lost(masks[g], k, [&](uint32_t j) {
           std::memcpy(data + g * in_g + uint64_t(j) * P, src + i * in_g + uint64_t(j) * P, P);
-        }
+        });
       }
     });
     sl.h_groups.clear();
     return FEC_OK;
   };
-  uint64_t c = 0;
-  for (uint64_t i0 = 0; i0 < N; i0 += cg, ++c) {
-    PipeSlot& sl = ctx->pipe[c % kPipeSlots];
-    rc = scatter(sl);
-    if (rc != FEC_OK) return rc;
-    const uint64_t n = (N - i0 < cg) ? N - i0 : cg;
-    const uint64_t* gl = need.data() + i0;
-    uint8_t* hi = sl.h_in.as<uint8_t>();
-    uint8_t* hp = sl.h_par.as<uint8_t>();
-    uint64_t* hm = sl.h_mask.as<uint64_t>();
-    parallel_for(n, 512, [&](uint64_t b, uint64_t e) {
-      for (uint64_t i = b; i < e; ++i) {
-        const uint64_t g = gl[i];
-        std::memcpy(hi + i * in_g, data + g * in_g, in_g);
-        std::memcpy(hp + i * par_g, parity + g * par_g, par_g);
-        hm[i] = masks[g];
-      }
-    });
-    sl.h_groups.assign(gl, gl + n);
-    QFEC_HIP(hipMemcpyAsync(sl.in.ptr, hi, n * in_g, hipMemcpyHostToDevice, sl.s));
-    QFEC_HIP(hipMemcpyAsync(sl.par.ptr, hp, n * par_g, hipMemcpyHostToDevice, sl.s));
-    QFEC_HIP(hipMemcpyAsync(sl.mask.ptr, hm, n * 8, hipMemcpyHostToDevice, sl.s));
-    rc = decode_dev_locked(ctx, sl.in.as<uint8_t>(), sl.par.as<uint8_t>(), sl.mask.as<uint64_t>(), n, k, r, P,
-                           nullptr, sl.s, &sl.rec);
-    if (rc != FEC_OK) return rc;
-    QFEC_HIP(hipMemcpyAsync(hi, sl.in.ptr, n * in_g, hipMemcpyDeviceToHost, sl.s));
-  }
-  for (auto& p : ctx->pipe) {
-    rc = scatter(p);
-    if (rc != FEC_OK) return rc;
-  }
-  drain.done = true;
-  return FEC_OK;
+  return run_pipeline(
+      ctx, need.size(), in_g, /*retire_before_refill=*/true,
+      [&](PipeSlot& p, uint64_t cg) {
+        QFEC_HIP(p.in.ensure(cg * in_g));
+        QFEC_HIP(p.par.ensure(cg * par_g));
+        QFEC_HIP(p.mask.ensure(cg * 8));
+        QFEC_HIP(p.h_in.ensure(cg * in_g));
+        QFEC_HIP(p.h_par.ensure(cg * par_g));
+        QFEC_HIP(p.h_mask.ensure(cg * 8));
+        p.h_groups.clear();
+        return FEC_OK;
+      },
+      [&](PipeSlot& sl, uint64_t i0, uint64_t n) {
+        const uint64_t* gl = need.data() + i0;
+        uint8_t* hi = sl.h_in.as<uint8_t>();
+        uint8_t* hp = sl.h_par.as<uint8_t>();
+        uint64_t* hm = sl.h_mask.as<uint64_t>();
+        parallel_for(n, 512, [&](uint64_t b, uint64_t e) {
+          for (uint64_t i = b; i < e; ++i) {
+            const uint64_t g = gl[i];
+            std::memcpy(hi + i * in_g, data + g * in_g, in_g);
+            std::memcpy(hp + i * par_g, parity + g * par_g, par_g);
+            hm[i] = masks[g];
+          }
+        });
+        sl.h_groups.assign(gl, gl + n);
+        QFEC_HIP(hipMemcpyAsync(sl.in.ptr, hi, n * in_g, hipMemcpyHostToDevice, sl.s));
+        QFEC_HIP(hipMemcpyAsync(sl.par.ptr, hp, n * par_g, hipMemcpyHostToDevice, sl.s));
+        QFEC_HIP(hipMemcpyAsync(sl.mask.ptr, hm, n * 8, hipMemcpyHostToDevice, sl.s));
+        DecodeCall c;
+        c.data = sl.in.as<uint8_t>(), c.parity = sl.par.as<uint8_t>(), c.masks = sl.mask.as<uint64_t>();
+        c.shape = {n, k, r, P}, c.stream = sl.s, c.rec = &sl.rec;
+        const int rc = decode_dev_locked(ctx, c);
+        if (rc != FEC_OK) return rc;
+        QFEC_HIP(hipMemcpyAsync(hi, sl.in.ptr, n * in_g, hipMemcpyDeviceToHost, sl.s));
+        return FEC_OK;
+      },
+      scatter);
 }
 
 // Zero-copy view of a host buffer for a kernel: its own device address when page-locked,
@@ -936,7 +979,7 @@ int zc_view(HostBuf& stage, const void* host, Mem m, void* dev, uint64_t bytes, 
   return FEC_OK;
 }
 
-// Small host-resident encode, zero-copy (see small_call_bytes).  Caller holds ctx->mu.
+// Small host-resident encode, zero-copy (fec_routes.hpp).  Caller holds ctx->mu.
 int encode_host_zero_copy(FECEncoderCtx* ctx, const uint8_t* data, Mem dmem, void* ddev, uint64_t G, uint32_t k,
                           uint32_t r, uint32_t P, uint8_t* parity_out, Mem omem, void* odev) {
   const uint64_t in_bytes = G * k * uint64_t(P), out_bytes = G * r * uint64_t(P);
@@ -964,18 +1007,19 @@ int decode_host_zero_copy(FECEncoderCtx* ctx, uint8_t* data, Mem dmem, void* dde
   if (rc != FEC_OK) return rc;
   QFEC_HIP(ctx->z_aux.ensure(G * 8));
   std::memcpy(ctx->z_aux.ptr, masks, G * 8);
-  rc = decode_dev_locked(ctx, d, p, ctx->z_aux.dev_as<uint64_t>(), G, k, r, P, nullptr, ctx->stream, nullptr,
-                         nullptr, need_share);
+  DecodeCall c;
+  c.data = d, c.parity = p, c.masks = ctx->z_aux.dev_as<uint64_t>();
+  c.shape = {G, k, r, P}, c.stream = ctx->stream, c.need_share = need_share;
+  rc = decode_dev_locked(ctx, c);
   if (rc != FEC_OK) return rc;
   QFEC_HIP(wait_stream(ctx->stream));
   if (d_staged) {  // only erased data packets changed (unrecoverable groups: untouched bytes)
-    const uint64_t kmask = (1ull << k) - 1;
     const uint8_t* z = ctx->z_in.as<uint8_t>();
     for (uint64_t g = 0; g < G; ++g)
-      for (uint64_t lost = masks[g] & kmask; lost; lost &= lost - 1) {
-        const uint64_t o = g * in_g + uint64_t(__builtin_ctzll(lost)) * P;
+      qfec::for_each_lost(masks[g], k, [&](uint32_t j) {
+        const uint64_t o = g * in_g + uint64_t(j) * P;
         std::memcpy(data + o, z + o, P);
-      }
+      });
   }
   return FEC_OK;
 }
@@ -1001,10 +1045,9 @@ void xor_packets_gpu(const uint8_t* packets[], size_t n, size_t packet_size, uin
   }
   FECEncoderCtx* ctx = default_ctx();
   if (!ctx) return;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
+  CtxBound bound(ctx);  // a device that does not bind shows in the calls below
   const uint32_t P = static_cast<uint32_t>(packet_size);
-  if ((n + 1) * uint64_t(packet_size) <= small_call_bytes(false)) {
+  if ((n + 1) * uint64_t(packet_size) <= small_call_limits().staged) {
     // Host packets: gather them into page-locked staging and run zero-copy.
     bool host = classify_ptr(repair) != Mem::kDevice;
     for (size_t p = 0; p < n && host; ++p) host = classify_ptr(packets[p]) != Mem::kDevice;
@@ -1045,15 +1088,6 @@ void xor_packets_gpu(const uint8_t* packets[], size_t n, size_t packet_size, uin
       hipStreamSynchronize(ctx->stream) != hipSuccess) {
     set_error("xor_packets: D2H copy failed");
   }
-}
-
-// Non-zero codes copy the thread's message into the context (fec_ctx_last_error).
-int record_ctx_error(FECEncoderCtx* ctx, int rc) {
-  if (rc != FEC_OK && ctx != nullptr) {
-    std::lock_guard<std::mutex> lk(ctx->err_mu);
-    ctx->last_error = g_last_error.empty() ? "error code " + std::to_string(rc) : g_last_error;
-  }
-  return rc;
 }
 
 }  // namespace
@@ -1150,25 +1184,10 @@ QFEC_EXPORT void fec_free_repair_buffer(void* ptr) { fec_free_slab(ptr); }
 // What fec_coalesce.cpp borrows (fec_internal.hpp).
 namespace qfec {
 
-HostMem classify_host_pointer(const void* p, void** dev) {
-  switch (classify_ptr(p, dev)) {
-    case Mem::kDevice:
-      return HostMem::kDevice;
-    case Mem::kPinned:
-      return HostMem::kPinned;
-    default:
-      return HostMem::kPageable;
-  }
-}
-
 int encode_addr_batch(FECEncoderCtx* ctx, const uint64_t* d_addr, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
                       uint8_t* d_parity, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) {
-    set_error("fec_encode_batch: cannot bind device %d", ctx->device);
-    return FEC_ERR_NODEV;
-  }
+  CtxBound bound(ctx, "fec_encode_batch");
+  if (bound.rc != FEC_OK) return bound.rc;
   return encode_dev_locked(ctx, nullptr, d_addr, OffsetKind::kAddr, G, k, r, P, d_parity, s);
 }
 
@@ -1176,112 +1195,104 @@ void set_last_error(const char* msg) { g_last_error = msg ? msg : ""; }
 
 }  // namespace qfec
 
-static int fec_encode_batch_impl(FECEncoderCtx* ctx, const uint8_t* slab, const uint32_t* offsets,
-                                 uint32_t num_groups, uint32_t packet_size, uint8_t* repair_out) {
-  // fec_xor_simd.cpp:564-570, same order
-  if (ctx == nullptr || slab == nullptr || offsets == nullptr || repair_out == nullptr) return -1;
-  if (num_groups == 0 || packet_size == 0) return 0;
-  // Small host-resident calls -- the reference's one group per call from each stream's own
-  // context -- share launches with every other context's (fec_coalesce.cpp).
-  int crc = 0;
-  if (qfec::coalesce_legacy_encode(ctx->device, slab, offsets, num_groups, packet_size, repair_out, &crc, ctx->stream))
-    return crc;
-  constexpr uint32_t kPackets = 10;  // fec_xor_simd.cpp:580
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) {
-    set_error("fec_encode_batch: cannot bind device %d", ctx->device);
-    return FEC_ERR_NODEV;
-  }
-  const uint64_t noff = uint64_t(num_groups) * kPackets;
-  const uint64_t P = packet_size;
-  void *slab_dev = nullptr, *out_dev = nullptr;
-  const Mem slab_mem = classify_ptr(slab, &slab_dev);
-  const Mem off_mem = classify_ptr(offsets);
-  const Mem out_mem = classify_ptr(repair_out, &out_dev);
-  hipStream_t s = ctx->stream;
-
-  const uint8_t* d_slab = slab;
-  const uint32_t* d_offsets = offsets;
-  if (slab_mem != Mem::kDevice || off_mem != Mem::kDevice) {
-    // Host offsets: read them here to size the slab window.
-    std::vector<uint32_t> host_off;
-    const uint32_t* hoff = offsets;
-    if (off_mem == Mem::kDevice) {
-      host_off.resize(noff);
-      QFEC_HIP(hipMemcpy(host_off.data(), offsets, noff * 4, hipMemcpyDeviceToHost));
-      hoff = host_off.data();
-    }
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    for (uint64_t i = 0; i < noff; ++i) {
-      lo = hoff[i] < lo ? hoff[i] : lo;
-      hi = hoff[i] > hi ? hoff[i] : hi;
-    }
-    const uint64_t span = uint64_t(hi) + P - lo;
-    const uint64_t small = small_call_bytes(slab_mem == Mem::kPinned && out_mem == Mem::kPinned);
-    if (slab_mem != Mem::kDevice && out_mem != Mem::kDevice && (noff + num_groups) * P <= small &&
-        (slab_mem == Mem::kPinned || span <= small)) {
-      // Small call, zero-copy: offsets (rebased to the staged window unless the slab is
-      // page-locked) and the slab window in page-locked memory, read by the kernel over PCIe.
-      QFEC_HIP(ctx->z_aux.ensure(noff * 4));
-      uint32_t* zo = ctx->z_aux.as<uint32_t>();
-      const uint8_t* zs = static_cast<const uint8_t*>(slab_dev);
-      if (slab_mem == Mem::kPinned && zs) {
-        std::memcpy(zo, hoff, noff * 4);
-      } else {
-        QFEC_HIP(ctx->z_in.ensure(span));
-        std::memcpy(ctx->z_in.ptr, slab + lo, span);
-        for (uint64_t i = 0; i < noff; ++i) zo[i] = hoff[i] - lo;
-        zs = ctx->z_in.dev_as<uint8_t>();
-      }
-      uint8_t* zr = nullptr;
-      bool out_staged = false;
-      int rc = zc_view(ctx->z_out, repair_out, out_mem, out_dev, uint64_t(num_groups) * P, false, &zr, &out_staged);
-      if (rc == FEC_OK)
-        rc = encode_dev_locked(ctx, zs, ctx->z_aux.dev_as<uint32_t>(), qfec::OffsetKind::kU32, num_groups, kPackets,
-                               1, packet_size, zr, s);
-      if (rc != FEC_OK) return rc;
-      QFEC_HIP(wait_stream(s));
-      if (out_staged) std::memcpy(repair_out, ctx->z_out.ptr, uint64_t(num_groups) * P);
-      return 0;
-    }
-    if (slab_mem == Mem::kDevice) {
-      if (off_mem != Mem::kDevice) {
-        QFEC_HIP(ctx->d_off.ensure(noff * 4));
-        QFEC_HIP(hipMemcpyAsync(ctx->d_off.ptr, hoff, noff * 4, hipMemcpyHostToDevice, s));
-        d_offsets = ctx->d_off.as<uint32_t>();
-      }
-    } else {
-      // Copy the window [lo, hi + P) of the host slab; rebase offsets to it.
-      std::vector<uint32_t> rebased(noff);
-      for (uint64_t i = 0; i < noff; ++i) rebased[i] = hoff[i] - lo;
-      QFEC_HIP(ctx->d_in.ensure(span));
-      QFEC_HIP(ctx->d_off.ensure(noff * 4));
-      QFEC_HIP(hipMemcpyAsync(ctx->d_in.ptr, slab + lo, span, hipMemcpyHostToDevice, s));
-      QFEC_HIP(hipMemcpyAsync(ctx->d_off.ptr, rebased.data(), noff * 4, hipMemcpyHostToDevice, s));
-      QFEC_HIP(hipStreamSynchronize(s));  // `rebased` dies at scope end
-      d_slab = ctx->d_in.as<uint8_t>();
-      d_offsets = ctx->d_off.as<uint32_t>();
-    }
-  }
-  uint8_t* d_repair = repair_out;
-  if (out_mem != Mem::kDevice) {
-    QFEC_HIP(ctx->d_out.ensure(uint64_t(num_groups) * P));
-    d_repair = ctx->d_out.as<uint8_t>();
-  }
-  const int rc = encode_dev_locked(ctx, d_slab, d_offsets, qfec::OffsetKind::kU32, num_groups,
-                                   kPackets, 1, packet_size, d_repair, s);
-  if (rc != FEC_OK) return rc;
-  if (out_mem != Mem::kDevice)
-    QFEC_HIP(hipMemcpyAsync(repair_out, d_repair, uint64_t(num_groups) * P, hipMemcpyDeviceToHost, s));
-  QFEC_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
 QFEC_EXPORT int fec_encode_batch(FECEncoderCtx* ctx, const uint8_t* slab, const uint32_t* offsets,
                                  uint32_t num_groups, uint32_t packet_size, uint8_t* repair_out) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_encode_batch_impl(ctx, slab, offsets, num_groups, packet_size, repair_out));
+  return api_call(ctx, [&]() -> int {
+    // fec_xor_simd.cpp:564-570, same order
+    if (ctx == nullptr || slab == nullptr || offsets == nullptr || repair_out == nullptr) return -1;
+    if (num_groups == 0 || packet_size == 0) return 0;
+    // Small host-resident calls -- the reference's one group per call from each stream's own
+    // context -- share launches with every other context's (fec_coalesce.cpp).
+    int crc = 0;
+    if (qfec::coalesce_legacy_encode(ctx->device, slab, offsets, num_groups, packet_size, repair_out, &crc, ctx->stream))
+      return crc;
+    constexpr uint32_t kPackets = 10;  // fec_xor_simd.cpp:580
+    CtxBound bound(ctx, "fec_encode_batch");
+    if (bound.rc != FEC_OK) return bound.rc;
+    const uint64_t noff = uint64_t(num_groups) * kPackets;
+    const uint64_t P = packet_size;
+    void *slab_dev = nullptr, *out_dev = nullptr;
+    const Mem slab_mem = classify_ptr(slab, &slab_dev);
+    const Mem off_mem = classify_ptr(offsets);
+    const Mem out_mem = classify_ptr(repair_out, &out_dev);
+    hipStream_t s = ctx->stream;
+    // A host slab: its offsets are read here (brought back when they are on the device) to size
+    // the slab window.
+    std::vector<uint32_t> host_off;
+    const uint32_t* hoff = offsets;
+    qfec::OffsetWindow<uint32_t> win{};
+    if (slab_mem != Mem::kDevice) {
+      if (off_mem == Mem::kDevice) {
+        host_off.resize(noff);
+        QFEC_HIP(hipMemcpy(host_off.data(), offsets, noff * 4, hipMemcpyDeviceToHost));
+        hoff = host_off.data();
+      }
+      win = qfec::offset_window(hoff, noff, P);
+    }
+    const uint32_t lo = win.lo;
+    const uint64_t span = win.span;
+    const qfec::LegacyEncodeRoute route =
+        qfec::legacy_encode_route(slab_mem, out_mem, (noff + num_groups) * P, span, small_call_limits());
+    switch (route.route) {
+      case qfec::EncodeRoute::kZeroCopy: {
+        // offsets (rebased to the staged window unless the slab is page-locked) and the slab window
+        // in page-locked memory, read by the kernel over PCIe
+        QFEC_HIP(ctx->z_aux.ensure(noff * 4));
+        uint32_t* zo = ctx->z_aux.as<uint32_t>();
+        const uint8_t* zs = static_cast<const uint8_t*>(slab_dev);
+        if (route.rebase) {
+          QFEC_HIP(ctx->z_in.ensure(span));
+          std::memcpy(ctx->z_in.ptr, slab + lo, span);
+          qfec::rebase_offsets(hoff, noff, lo, zo);
+          zs = ctx->z_in.dev_as<uint8_t>();
+        } else {
+          std::memcpy(zo, hoff, noff * 4);
+        }
+        uint8_t* zr = nullptr;
+        bool out_staged = false;
+        int rc = zc_view(ctx->z_out, repair_out, out_mem, out_dev, uint64_t(num_groups) * P, false, &zr, &out_staged);
+        if (rc == FEC_OK)
+          rc = encode_dev_locked(ctx, zs, ctx->z_aux.dev_as<uint32_t>(), qfec::OffsetKind::kU32, num_groups, kPackets,
+                                 1, packet_size, zr, s);
+        if (rc != FEC_OK) return rc;
+        QFEC_HIP(wait_stream(s));
+        if (out_staged) std::memcpy(repair_out, ctx->z_out.ptr, uint64_t(num_groups) * P);
+        return 0;
+      }
+      default: {  // kStaged
+        const uint8_t* d_slab = slab;
+        const uint32_t* d_offsets = offsets;
+        if (route.rebase) {
+          // Copy the window [lo, hi + P) of the host slab; rebase offsets to it.
+          std::vector<uint32_t> rebased(noff);
+          qfec::rebase_offsets(hoff, noff, lo, rebased.data());
+          QFEC_HIP(ctx->d_in.ensure(span));
+          QFEC_HIP(ctx->d_off.ensure(noff * 4));
+          QFEC_HIP(hipMemcpyAsync(ctx->d_in.ptr, slab + lo, span, hipMemcpyHostToDevice, s));
+          QFEC_HIP(hipMemcpyAsync(ctx->d_off.ptr, rebased.data(), noff * 4, hipMemcpyHostToDevice, s));
+          QFEC_HIP(hipStreamSynchronize(s));  // `rebased` dies at scope end
+          d_slab = ctx->d_in.as<uint8_t>();
+          d_offsets = ctx->d_off.as<uint32_t>();
+        } else if (off_mem != Mem::kDevice) {
+          QFEC_HIP(ctx->d_off.ensure(noff * 4));
+          QFEC_HIP(hipMemcpyAsync(ctx->d_off.ptr, hoff, noff * 4, hipMemcpyHostToDevice, s));
+          d_offsets = ctx->d_off.as<uint32_t>();
+        }
+        uint8_t* d_repair = repair_out;
+        if (out_mem != Mem::kDevice) {
+          QFEC_HIP(ctx->d_out.ensure(uint64_t(num_groups) * P));
+          d_repair = ctx->d_out.as<uint8_t>();
+        }
+        const int rc = encode_dev_locked(ctx, d_slab, d_offsets, qfec::OffsetKind::kU32, num_groups, kPackets, 1,
+                                         packet_size, d_repair, s);
+        if (rc != FEC_OK) return rc;
+        if (out_mem != Mem::kDevice)
+          QFEC_HIP(hipMemcpyAsync(repair_out, d_repair, uint64_t(num_groups) * P, hipMemcpyDeviceToHost, s));
+        QFEC_HIP(hipStreamSynchronize(s));
+        return 0;
+      }
+    }
+  });
 }
 
 QFEC_EXPORT xor_impl_fn fec_select_xor_impl(void) { return xor_packets_gpu; }
@@ -1368,28 +1379,13 @@ int check_shape(uint64_t G, uint32_t k, uint32_t r, uint32_t P, bool decode) {
   return FEC_OK;
 }
 
-}  // namespace
-
-static int fec_encode_batch_rs_impl(FECEncoderCtx* ctx, const uint8_t* data, const uint64_t* offsets,
-                                    uint64_t G, uint32_t k, uint32_t r, uint32_t P, uint8_t* parity_out) {
-  if (!ctx || !data || !parity_out) return FEC_ERR_NULL;
-  int rc = check_shape(G, k, r, P, false);
-  if (rc != FEC_OK) return rc;
-  if (G == 0) return FEC_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
+// fec_encode_batch_rs with a buffer on the device or packets at offsets: whatever is on the host
+// goes through the context's device buffers in one shot (a host slab: its window, offsets rebased).
+int encode_staged(FECEncoderCtx* ctx, const uint8_t* data, Mem dmem, const uint64_t* offsets, uint64_t G, uint32_t k,
+                  uint32_t r, uint32_t P, uint8_t* parity_out, Mem omem) {
   hipStream_t s = ctx->stream;
   const uint64_t nin = G * k;
   const uint64_t out_bytes = G * r * uint64_t(P);
-  void *ddev = nullptr, *odev = nullptr;
-  const Mem dmem = classify_ptr(data, &ddev);
-  const Mem omem = classify_ptr(parity_out, &odev);
-  if (!offsets && dmem != Mem::kDevice && omem != Mem::kDevice) {
-    if (nin * P + out_bytes <= small_call_bytes(dmem == Mem::kPinned && omem == Mem::kPinned))
-      return encode_host_zero_copy(ctx, data, dmem, ddev, G, k, r, P, parity_out, omem, odev);
-    return encode_host_pipelined(ctx, data, G, k, r, P, parity_out);
-  }
   const uint8_t* d_data = data;
   const void* d_off = nullptr;
   qfec::OffsetKind ok = qfec::OffsetKind::kNone;
@@ -1404,11 +1400,6 @@ static int fec_encode_batch_rs_impl(FECEncoderCtx* ctx, const uint8_t* data, con
       QFEC_HIP(hipMemcpy(host_off.data(), offsets, nin * 8, hipMemcpyDeviceToHost));
       hoff = host_off.data();
     }
-    uint64_t lo = ~0ull, hi = 0;
-    for (uint64_t i = 0; i < nin; ++i) {
-      lo = hoff[i] < lo ? hoff[i] : lo;
-      hi = hoff[i] > hi ? hoff[i] : hi;
-    }
     if (dmem == Mem::kDevice) {
       if (offmem != Mem::kDevice) {
         QFEC_HIP(ctx->d_off.ensure(nin * 8));
@@ -1419,9 +1410,9 @@ static int fec_encode_batch_rs_impl(FECEncoderCtx* ctx, const uint8_t* data, con
         d_off = offsets;
       }
     } else {
-      const uint64_t span = hi + P - lo;
+      const auto [lo, hi, span] = qfec::offset_window(hoff, nin, P);
       rebased.resize(nin);
-      for (uint64_t i = 0; i < nin; ++i) rebased[i] = hoff[i] - lo;
+      qfec::rebase_offsets(hoff, nin, lo, rebased.data());
       QFEC_HIP(ctx->d_in.ensure(span));
       QFEC_HIP(ctx->d_off.ensure(nin * 8));
       QFEC_HIP(hipMemcpyAsync(ctx->d_in.ptr, data + lo, span, hipMemcpyHostToDevice, s));
@@ -1441,7 +1432,7 @@ static int fec_encode_batch_rs_impl(FECEncoderCtx* ctx, const uint8_t* data, con
     QFEC_HIP(ctx->d_out.ensure(out_bytes));
     d_par = ctx->d_out.as<uint8_t>();
   }
-  rc = encode_dev_locked(ctx, d_data, d_off, ok, G, k, r, P, d_par, s);
+  const int rc = encode_dev_locked(ctx, d_data, d_off, ok, G, k, r, P, d_par, s);
   if (rc != FEC_OK) return rc;
   if (omem != Mem::kDevice)
     QFEC_HIP(hipMemcpyAsync(parity_out, d_par, out_bytes, hipMemcpyDeviceToHost, s));
@@ -1449,91 +1440,39 @@ static int fec_encode_batch_rs_impl(FECEncoderCtx* ctx, const uint8_t* data, con
   return FEC_OK;
 }
 
-QFEC_EXPORT int fec_encode_batch_rs(FECEncoderCtx* ctx, const uint8_t* data, const uint64_t* offsets,
-                                    uint64_t G, uint32_t k, uint32_t r, uint32_t P, uint8_t* parity_out) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_encode_batch_rs_impl(ctx, data, offsets, G, k, r, P, parity_out));
-}
-
-static int fec_decode_batch_rs_impl(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* parity,
-                                    const uint64_t* masks, uint64_t G, uint32_t k, uint32_t r,
-                                    uint32_t P, uint8_t* status_out, uint64_t* unrecoverable_out) {
-  if (!ctx || !data || !parity || !masks) return FEC_ERR_NULL;
-  int rc = check_shape(G, k, r, P, true);
-  if (rc != FEC_OK) return rc;
-  if (unrecoverable_out) *unrecoverable_out = 0;
-  if (G == 0) return FEC_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
+// fec_decode_batch_rs with a buffer on the device: the others go through the context's device
+// buffers in one shot, and the statuses come back from the kernel.
+int decode_staged(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* parity, const uint64_t* masks,
+                  const qfec::DecodeMem& mem, uint64_t G, uint32_t k, uint32_t r, uint32_t P, uint8_t* status_out,
+                  uint64_t* unrecoverable_out) {
   hipStream_t s = ctx->stream;
   const uint64_t data_bytes = G * k * uint64_t(P);
   const uint64_t par_bytes = G * r * uint64_t(P);
-  void *ddev = nullptr, *pdev = nullptr;
-  const Mem dmem = classify_ptr(data, &ddev), pmem = classify_ptr(parity, &pdev), mmem = classify_ptr(masks);
-  if (dmem != Mem::kDevice && pmem != Mem::kDevice && mmem != Mem::kDevice &&
-      (!status_out || classify_ptr(status_out) != Mem::kDevice)) {
-    std::vector<uint8_t> st_local;
-    uint8_t* st = status_out;
-    if (!st) {
-      st_local.resize(G);
-      st = st_local.data();
-    }
-    // Which groups need work: lost data shards, and no more than the surviving parity rows
-    // (the classify rule, fec_kernels.hip); status is known on the host from the masks.
-    const uint64_t kmask = (1ull << k) - 1, rmask = (r >= 64) ? ~0ull : ((1ull << r) - 1);
-    std::vector<uint64_t> need;
-    uint64_t bad = 0;
-    for (uint64_t g = 0; g < G; ++g) {
-      const uint64_t m = masks[g];
-      const uint32_t e = static_cast<uint32_t>(__builtin_popcountll(m & kmask));
-      const uint32_t alive = r - static_cast<uint32_t>(__builtin_popcountll((m >> k) & rmask));
-      const bool unrec = e > 0 && e > alive;
-      bad += unrec;
-      if (e > 0 && !unrec) need.push_back(g);
-    }
-    const bool small = data_bytes + par_bytes <= small_call_bytes(dmem == Mem::kPinned && pmem == Mem::kPinned);
-    if (small || need.size() * kCompactMaxShare <= G) {
-      // few groups to rebuild: move only those (statuses from the host scan); a small call
-      // runs zero-copy
-      for (uint64_t g = 0; g < G; ++g) {
-        const uint64_t m = masks[g];
-        const uint32_t e = static_cast<uint32_t>(__builtin_popcountll(m & kmask));
-        st[g] = (e > 0 && e > r - static_cast<uint32_t>(__builtin_popcountll((m >> k) & rmask))) ? 1 : 0;
-      }
-      if (!need.empty())
-        rc = small ? decode_host_zero_copy(ctx, data, dmem, ddev, parity, pmem, pdev, masks, G, k, r, P,
-                                           double(need.size()) / double(G))
-                   : decode_host_compacted(ctx, data, parity, masks, need, k, r, P);
-    } else {
-      rc = decode_host_pipelined(ctx, data, parity, masks, G, k, r, P, st);
-    }
-    if (rc != FEC_OK) return rc;
-    if (unrecoverable_out) *unrecoverable_out = bad;
-    return FEC_OK;
-  }
   uint8_t* d_data = data;
   const uint8_t* d_par = parity;
   const uint64_t* d_masks = masks;
-  if (dmem != Mem::kDevice) {
+  if (mem.data != Mem::kDevice) {
     QFEC_HIP(ctx->d_in.ensure(data_bytes));
     QFEC_HIP(hipMemcpyAsync(ctx->d_in.ptr, data, data_bytes, hipMemcpyHostToDevice, s));
     d_data = ctx->d_in.as<uint8_t>();
   }
-  if (pmem != Mem::kDevice) {
+  if (mem.parity != Mem::kDevice) {
     QFEC_HIP(ctx->d_out.ensure(par_bytes));
     QFEC_HIP(hipMemcpyAsync(ctx->d_out.ptr, parity, par_bytes, hipMemcpyHostToDevice, s));
     d_par = ctx->d_out.as<uint8_t>();
   }
-  if (mmem != Mem::kDevice) {
+  if (mem.masks != Mem::kDevice) {
     QFEC_HIP(ctx->d_mask.ensure(G * 8));
     QFEC_HIP(hipMemcpyAsync(ctx->d_mask.ptr, masks, G * 8, hipMemcpyHostToDevice, s));
     d_masks = ctx->d_mask.as<uint64_t>();
   }
   QFEC_HIP(ctx->d_status.ensure(G));
-  rc = decode_dev_locked(ctx, d_data, d_par, d_masks, G, k, r, P, ctx->d_status.as<uint8_t>(), s);
+  DecodeCall c;
+  c.data = d_data, c.parity = d_par, c.masks = d_masks;
+  c.shape = {G, k, r, P}, c.status = ctx->d_status.as<uint8_t>(), c.stream = s;
+  const int rc = decode_dev_locked(ctx, c);
   if (rc != FEC_OK) return rc;
-  if (dmem != Mem::kDevice)
+  if (mem.data != Mem::kDevice)
     QFEC_HIP(hipMemcpyAsync(data, d_data, data_bytes, hipMemcpyDeviceToHost, s));
   std::vector<uint8_t> st(G);
   QFEC_HIP(hipMemcpyAsync(st.data(), ctx->d_status.ptr, G, hipMemcpyDeviceToHost, s));
@@ -1545,115 +1484,164 @@ static int fec_decode_batch_rs_impl(FECEncoderCtx* ctx, uint8_t* data, const uin
   return FEC_OK;
 }
 
+}  // namespace
+
+QFEC_EXPORT int fec_encode_batch_rs(FECEncoderCtx* ctx, const uint8_t* data, const uint64_t* offsets,
+                                    uint64_t G, uint32_t k, uint32_t r, uint32_t P, uint8_t* parity_out) {
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !data || !parity_out) return FEC_ERR_NULL;
+    const int rc = check_shape(G, k, r, P, false);
+    if (rc != FEC_OK) return rc;
+    if (G == 0) return FEC_OK;
+    CtxBound bound(ctx);
+    if (bound.rc != FEC_OK) return bound.rc;
+    void *ddev = nullptr, *odev = nullptr;
+    const Mem dmem = classify_ptr(data, &ddev);
+    const Mem omem = classify_ptr(parity_out, &odev);
+    switch (qfec::encode_route(dmem, omem, offsets != nullptr, G * (k + r) * uint64_t(P), small_call_limits())) {
+      case qfec::EncodeRoute::kZeroCopy:
+        return encode_host_zero_copy(ctx, data, dmem, ddev, G, k, r, P, parity_out, omem, odev);
+      case qfec::EncodeRoute::kPipelined:
+        return encode_host_pipelined(ctx, data, G, k, r, P, parity_out);
+      case qfec::EncodeRoute::kStaged:
+        return encode_staged(ctx, data, dmem, offsets, G, k, r, P, parity_out, omem);
+    }
+    return FEC_ERR_RANGE;  // not reached
+  });
+}
+
 QFEC_EXPORT int fec_decode_batch_rs(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* parity,
                                     const uint64_t* masks, uint64_t G, uint32_t k, uint32_t r,
                                     uint32_t P, uint8_t* status_out, uint64_t* unrecoverable_out) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_decode_batch_rs_impl(ctx, data, parity, masks, G, k, r, P, status_out, unrecoverable_out));
-}
-
-static int fec_encode_batch_rs_dev_impl(FECEncoderCtx* ctx, const uint8_t* d_data, uint64_t G,
-                                        uint32_t k, uint32_t r, uint32_t P, uint8_t* d_parity,
-                                        void* stream) {
-  if (!ctx || !d_data || !d_parity) return FEC_ERR_NULL;
-  int rc = check_shape(G, k, r, P, false);
-  if (rc != FEC_OK) return rc;
-  if (G == 0) return FEC_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  return encode_dev_locked(ctx, d_data, nullptr, qfec::OffsetKind::kNone, G, k, r, P, d_parity,
-                           pick_stream(ctx, stream));
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !data || !parity || !masks) return FEC_ERR_NULL;
+    int rc = check_shape(G, k, r, P, true);
+    if (rc != FEC_OK) return rc;
+    if (unrecoverable_out) *unrecoverable_out = 0;
+    if (G == 0) return FEC_OK;
+    CtxBound bound(ctx);
+    if (bound.rc != FEC_OK) return bound.rc;
+    void *ddev = nullptr, *pdev = nullptr;
+    qfec::DecodeMem mem{classify_ptr(data, &ddev), classify_ptr(parity, &pdev), classify_ptr(masks), Mem::kHost};
+    if (status_out && mem.host_resident()) mem.status = classify_ptr(status_out);  // else it decides nothing
+    // Host-resident: the masks are read here, once -- every status, the unrecoverable count and
+    // which groups need work: lost data shards, and no more than the surviving parity rows.
+    std::vector<uint8_t> st_local;
+    uint8_t* st = status_out;
+    std::vector<uint64_t> need;
+    uint64_t bad = 0;
+    if (mem.host_resident()) {
+      if (!st) {
+        st_local.resize(G);
+        st = st_local.data();
+      }
+      for (uint64_t g = 0; g < G; ++g) {
+        const qfec::MaskLosses ml = qfec::mask_losses(masks[g], k, r);
+        st[g] = ml.unrecoverable ? 1 : 0;
+        bad += ml.unrecoverable;
+        if (ml.lost > 0 && !ml.unrecoverable) need.push_back(g);
+      }
+    }
+    switch (qfec::decode_route(mem, G * (k + r) * uint64_t(P), G, need.size(), small_call_limits())) {
+      case qfec::DecodeRoute::kNothing:
+        break;
+      case qfec::DecodeRoute::kZeroCopy:
+        rc = decode_host_zero_copy(ctx, data, mem.data, ddev, parity, mem.parity, pdev, masks, G, k, r, P,
+                                   double(need.size()) / double(G));
+        break;
+      case qfec::DecodeRoute::kCompacted:
+        rc = decode_host_compacted(ctx, data, parity, masks, need, k, r, P);
+        break;
+      case qfec::DecodeRoute::kPipelined:  // the kernel's statuses land over the scan's: the same rule
+        rc = decode_host_pipelined(ctx, data, parity, masks, G, k, r, P, st);
+        break;
+      case qfec::DecodeRoute::kStaged:
+        return decode_staged(ctx, data, parity, masks, mem, G, k, r, P, status_out, unrecoverable_out);
+    }
+    if (rc != FEC_OK) return rc;
+    if (unrecoverable_out) *unrecoverable_out = bad;
+    return FEC_OK;
+  });
 }
 
 QFEC_EXPORT int fec_encode_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, uint64_t G,
                                         uint32_t k, uint32_t r, uint32_t P, uint8_t* d_parity,
                                         void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_encode_batch_rs_dev_impl(ctx, d_data, G, k, r, P, d_parity, stream));
-}
-
-static int fec_decode_batch_rs_dev_impl(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
-                                        const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r,
-                                        uint32_t P, uint8_t* d_status, void* stream) {
-  if (!ctx || !d_data || !d_parity || !d_masks) return FEC_ERR_NULL;
-  int rc = check_shape(G, k, r, P, true);
-  if (rc != FEC_OK) return rc;
-  if (G == 0) return FEC_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  return decode_dev_locked(ctx, d_data, d_parity, d_masks, G, k, r, P, d_status,
-                           pick_stream(ctx, stream));
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_data || !d_parity) return FEC_ERR_NULL;
+    const int rc = check_shape(G, k, r, P, false);
+    if (rc != FEC_OK) return rc;
+    if (G == 0) return FEC_OK;
+    CtxBound bound(ctx);
+    if (bound.rc != FEC_OK) return bound.rc;
+    return encode_dev_locked(ctx, d_data, nullptr, qfec::OffsetKind::kNone, G, k, r, P, d_parity,
+                             pick_stream(ctx, stream));
+  });
 }
 
 QFEC_EXPORT int fec_decode_batch_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
                                         const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r,
                                         uint32_t P, uint8_t* d_status, void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_decode_batch_rs_dev_impl(ctx, d_data, d_parity, d_masks, G, k, r, P, d_status, stream));
-}
-
-static int fec_recover_batch_rs_dev_impl(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
-                                         const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
-                                         uint8_t* d_rebuilt, uint8_t* d_status, void* stream) {
-  if (!ctx || !d_data || !d_parity || !d_masks || !d_rebuilt) return FEC_ERR_NULL;
-  int rc = check_shape(G, k, r, P, true);
-  if (rc != FEC_OK) return rc;
-  if (G == 0) return FEC_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  // the kernels only read `data` when the output is compact
-  return decode_dev_locked(ctx, const_cast<uint8_t*>(d_data), d_parity, d_masks, G, k, r, P, d_status,
-                           pick_stream(ctx, stream), nullptr, d_rebuilt, -1.0, /*compact_out=*/true);
-}
-
-static int fec_recover_batch_rs_dev_packed_impl(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
-                                                const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r,
-                                                uint32_t P, uint8_t* d_rebuilt, uint32_t* d_row_start,
-                                                uint64_t* d_total, uint8_t* d_status, void* stream) {
-  if (!ctx || !d_data || !d_parity || !d_masks || !d_rebuilt || !d_row_start) return FEC_ERR_NULL;
-  int rc = check_shape(G, k, r, P, true);
-  if (rc != FEC_OK) return rc;
-  if (G * r >= (1ull << 32)) {
-    set_error("packed recover: %llu groups x %u rows exceed 32-bit row indices", static_cast<unsigned long long>(G), r);
-    return FEC_ERR_RANGE;
-  }
-  if (G == 0) {
-    if (d_total) {
-      std::lock_guard<std::mutex> lk(ctx->mu);
-      DeviceGuard dg(ctx->device);
-      if (!dg.ok) return FEC_ERR_NODEV;
-      QFEC_HIP(hipMemsetAsync(d_total, 0, sizeof(uint64_t), pick_stream(ctx, stream)));
-    }
-    return FEC_OK;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  // decode_dev_locked checks the form first and only then launches the row prefix, so an
-  // unsupported shape returns FEC_ERR_RANGE with d_row_start / d_total untouched
-  return decode_dev_locked(ctx, const_cast<uint8_t*>(d_data), d_parity, d_masks, G, k, r, P, d_status,
-                           pick_stream(ctx, stream), nullptr, d_rebuilt, -1.0, /*compact_out=*/true, d_row_start,
-                           d_total);
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_data || !d_parity || !d_masks) return FEC_ERR_NULL;
+    const int rc = check_shape(G, k, r, P, true);
+    if (rc != FEC_OK) return rc;
+    if (G == 0) return FEC_OK;
+    CtxBound bound(ctx);
+    if (bound.rc != FEC_OK) return bound.rc;
+    DecodeCall c;
+    c.data = d_data, c.parity = d_parity, c.masks = d_masks;
+    c.shape = {G, k, r, P}, c.status = d_status, c.stream = pick_stream(ctx, stream);
+    return decode_dev_locked(ctx, c);
+  });
 }
 
 QFEC_EXPORT int fec_recover_batch_rs_dev_packed(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
                                                 const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r,
                                                 uint32_t P, uint8_t* d_rebuilt, uint32_t* d_row_start,
                                                 uint64_t* d_total, uint8_t* d_status, void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_recover_batch_rs_dev_packed_impl(ctx, d_data, d_parity, d_masks, G, k, r, P, d_rebuilt,
-                                                                    d_row_start, d_total, d_status, stream));
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_data || !d_parity || !d_masks || !d_rebuilt || !d_row_start) return FEC_ERR_NULL;
+    const int rc = check_shape(G, k, r, P, true);
+    if (rc != FEC_OK) return rc;
+    if (G * r >= (1ull << 32)) {
+      set_error("packed recover: %llu groups x %u rows exceed 32-bit row indices", static_cast<unsigned long long>(G), r);
+      return FEC_ERR_RANGE;
+    }
+    if (G == 0 && !d_total) return FEC_OK;
+    CtxBound bound(ctx);
+    if (bound.rc != FEC_OK) return bound.rc;
+    if (G == 0) {
+      QFEC_HIP(hipMemsetAsync(d_total, 0, sizeof(uint64_t), pick_stream(ctx, stream)));
+      return FEC_OK;
+    }
+    // decode_dev_locked checks the form first and only then launches the row prefix, so an
+    // unsupported shape returns FEC_ERR_RANGE with d_row_start / d_total untouched
+    DecodeCall c;
+    c.data = const_cast<uint8_t*>(d_data);  // the kernels only read `data` when the output is compact
+    c.parity = d_parity, c.masks = d_masks, c.out = d_rebuilt, c.compact_out = true;
+    c.shape = {G, k, r, P}, c.status = d_status, c.stream = pick_stream(ctx, stream);
+    c.row_start = d_row_start, c.row_total = d_total;
+    return decode_dev_locked(ctx, c);
+  });
 }
 
 QFEC_EXPORT int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
                                          const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
                                          uint8_t* d_rebuilt, uint8_t* d_status, void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_recover_batch_rs_dev_impl(ctx, d_data, d_parity, d_masks, G, k, r, P, d_rebuilt,
-                                                             d_status, stream));
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_data || !d_parity || !d_masks || !d_rebuilt) return FEC_ERR_NULL;
+    const int rc = check_shape(G, k, r, P, true);
+    if (rc != FEC_OK) return rc;
+    if (G == 0) return FEC_OK;
+    CtxBound bound(ctx);
+    if (bound.rc != FEC_OK) return bound.rc;
+    DecodeCall c;
+    c.data = const_cast<uint8_t*>(d_data);  // the kernels only read `data` when the output is compact
+    c.parity = d_parity, c.masks = d_masks, c.out = d_rebuilt, c.compact_out = true;
+    c.shape = {G, k, r, P}, c.status = d_status, c.stream = pick_stream(ctx, stream);
+    return decode_dev_locked(ctx, c);
+  });
 }
 
 // ---- address-table calls: shards / packets wherever they are in device memory ----
@@ -1708,9 +1696,8 @@ int table_recover_locked(const char* what, FECEncoderCtx* ctx, const uint64_t* d
               "fec_recover_batch_rs_dev)", what, k, r, static_cast<unsigned long long>(kCodebookCap));
     return FEC_ERR_RANGE;
   }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
+  CtxBound bound(ctx);
+  if (bound.rc != FEC_OK) return bound.rc;
   DecodePlan* plan = nullptr;
   rc = get_decode_plan(ctx, k, r, &plan);
   if (rc != FEC_OK) return rc;
@@ -1742,9 +1729,8 @@ int table_encode_locked(const char* what, FECEncoderCtx* ctx, uint64_t G, uint32
                         void* stream, F launch) {
   int rc = check_gather_shape(what, G, k, r, P);
   if (rc != FEC_OK) return rc;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
+  CtxBound bound(ctx);
+  if (bound.rc != FEC_OK) return bound.rc;
   const void* tables = nullptr;
   rc = get_encode_plan(ctx, k, r, &tables);
   if (rc != FEC_OK) return rc;
@@ -1757,223 +1743,172 @@ int table_encode_done(hipError_t e, const char* call) { return e == hipSuccess ?
 
 }  // namespace
 
-static int fec_recover_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
-                                          uint32_t r, uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
-                                          uint64_t* d_masks_out, void* stream) {
-  if (!ctx || !d_shard_addrs || !d_rebuilt) {
-    set_error("gather recover: %s is NULL", !ctx ? "the context" : !d_shard_addrs ? "d_shard_addrs" : "d_rebuilt");
-    return FEC_ERR_NULL;
-  }
-  return table_recover_locked("gather recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out, stream, 1,
-                              kRecOffWorkspaceCall, [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
-                                a.out = d_rebuilt;
-                                QFEC_HIP(qfec::launch_recover_gather(a, s));
-                                return FEC_OK;
-                              });
-}
-
 QFEC_EXPORT int fec_recover_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
                                           uint32_t r, uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
                                           uint64_t* d_masks_out, void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_recover_gather_rs_dev_impl(ctx, d_shard_addrs, G, k, r, P, d_rebuilt, d_status,
-                                                              d_masks_out, stream));
-}
-
-static int fec_encode_gather_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs, uint64_t G, uint32_t k,
-                                         uint32_t r, uint32_t P, uint8_t* d_parity, void* stream) {
-  if (!ctx || !d_packet_addrs || !d_parity) {
-    set_error("gather encode: %s is NULL", !ctx ? "the context" : !d_packet_addrs ? "d_packet_addrs" : "d_parity");
-    return FEC_ERR_NULL;
-  }
-  // launch_encode with absolute addresses: encode_dev_locked takes the plan's tables itself
-  return table_encode_locked("gather encode", ctx, G, k, r, P, stream, [&](const void*, hipStream_t s) {
-    return encode_dev_locked(ctx, nullptr, d_packet_addrs, qfec::OffsetKind::kAddr, G, k, r, P, d_parity, s);
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_shard_addrs || !d_rebuilt) {
+      set_error("gather recover: %s is NULL", !ctx ? "the context" : !d_shard_addrs ? "d_shard_addrs" : "d_rebuilt");
+      return FEC_ERR_NULL;
+    }
+    return table_recover_locked("gather recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out, stream, 1,
+                                kRecOffWorkspaceCall, [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
+                                  a.out = d_rebuilt;
+                                  QFEC_HIP(qfec::launch_recover_gather(a, s));
+                                  return FEC_OK;
+                                });
   });
 }
 
 QFEC_EXPORT int fec_encode_gather_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs, uint64_t G, uint32_t k,
                                          uint32_t r, uint32_t P, uint8_t* d_parity, void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_encode_gather_rs_dev_impl(ctx, d_packet_addrs, G, k, r, P, d_parity, stream));
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_packet_addrs || !d_parity) {
+      set_error("gather encode: %s is NULL", !ctx ? "the context" : !d_packet_addrs ? "d_packet_addrs" : "d_parity");
+      return FEC_ERR_NULL;
+    }
+    // launch_encode with absolute addresses: encode_dev_locked takes the plan's tables itself
+    return table_encode_locked("gather encode", ctx, G, k, r, P, stream, [&](const void*, hipStream_t s) {
+      return encode_dev_locked(ctx, nullptr, d_packet_addrs, qfec::OffsetKind::kAddr, G, k, r, P, d_parity, s);
+    });
+  });
 }
 
 // ---- the same with a length per table entry (fec_gather_var.hip) ----
-static int fec_recover_gather_var_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
-                                              const uint32_t* d_shard_lens, uint64_t G, uint32_t k, uint32_t r,
-                                              uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
-                                              uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream) {
-  if (!ctx || !d_shard_addrs || !d_shard_lens || !d_rebuilt) {
-    set_error("variable-length gather recover: %s is NULL", !ctx             ? "the context"
-                                                            : !d_shard_addrs ? "d_shard_addrs"
-                                                            : !d_shard_lens  ? "d_shard_lens (the length table)"
-                                                                             : "d_rebuilt");
-    return FEC_ERR_NULL;
-  }
-  return table_recover_locked("variable-length gather recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out,
-                              stream, 1, kRecOffWorkspaceCall, [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
-                                a.out = d_rebuilt;
-                                a.lens = d_shard_lens;
-                                a.symlen = d_symbol_len_out;
-                                QFEC_HIP(qfec::launch_recover_gather_var(a, s));
-                                return FEC_OK;
-                              });
-}
-
 QFEC_EXPORT int fec_recover_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
                                               const uint32_t* d_shard_lens, uint64_t G, uint32_t k, uint32_t r,
                                               uint32_t P, uint8_t* d_rebuilt, uint8_t* d_status,
                                               uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_recover_gather_var_rs_dev_impl(ctx, d_shard_addrs, d_shard_lens, G, k, r, P, d_rebuilt,
-                                                                  d_status, d_masks_out, d_symbol_len_out, stream));
-}
-
-static int fec_encode_gather_var_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
-                                             const uint32_t* d_packet_lens, uint64_t G, uint32_t k, uint32_t r,
-                                             uint32_t P, uint8_t* d_parity, uint32_t* d_symbol_len_out, void* stream) {
-  if (!ctx || !d_packet_addrs || !d_packet_lens || !d_parity) {
-    set_error("variable-length gather encode: %s is NULL", !ctx              ? "the context"
-                                                           : !d_packet_addrs ? "d_packet_addrs"
-                                                           : !d_packet_lens  ? "d_packet_lens (the length table)"
-                                                                             : "d_parity");
-    return FEC_ERR_NULL;
-  }
-  return table_encode_locked("variable-length gather encode", ctx, G, k, r, P, stream,
-                             [&](const void* tables, hipStream_t s) {
-                               // addrs, lens, groups, k, r, P, parity, dests, symlen_out, tables
-                               const qfec::TableEncodeLaunch a{d_packet_addrs, d_packet_lens, G, k, r, P, d_parity, nullptr,
-                                                               d_symbol_len_out, tables};
-                               return table_encode_done(qfec::launch_encode_gather_var(a, s),
-                                                        "qfec::launch_encode_gather_var(a, pick_stream(ctx, stream))");
-                             });
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_shard_addrs || !d_shard_lens || !d_rebuilt) {
+      set_error("variable-length gather recover: %s is NULL", !ctx             ? "the context"
+                                                              : !d_shard_addrs ? "d_shard_addrs"
+                                                              : !d_shard_lens  ? "d_shard_lens (the length table)"
+                                                                               : "d_rebuilt");
+      return FEC_ERR_NULL;
+    }
+    return table_recover_locked("variable-length gather recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out,
+                                stream, 1, kRecOffWorkspaceCall, [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
+                                  a.out = d_rebuilt;
+                                  a.lens = d_shard_lens;
+                                  a.symlen = d_symbol_len_out;
+                                  QFEC_HIP(qfec::launch_recover_gather_var(a, s));
+                                  return FEC_OK;
+                                });
+  });
 }
 
 QFEC_EXPORT int fec_encode_gather_var_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
                                              const uint32_t* d_packet_lens, uint64_t G, uint32_t k, uint32_t r,
                                              uint32_t P, uint8_t* d_parity, uint32_t* d_symbol_len_out, void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_encode_gather_var_rs_dev_impl(ctx, d_packet_addrs, d_packet_lens, G, k, r, P, d_parity,
-                                                                 d_symbol_len_out, stream));
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_packet_addrs || !d_packet_lens || !d_parity) {
+      set_error("variable-length gather encode: %s is NULL", !ctx              ? "the context"
+                                                             : !d_packet_addrs ? "d_packet_addrs"
+                                                             : !d_packet_lens  ? "d_packet_lens (the length table)"
+                                                                               : "d_parity");
+      return FEC_ERR_NULL;
+    }
+    return table_encode_locked("variable-length gather encode", ctx, G, k, r, P, stream,
+                               [&](const void* tables, hipStream_t s) {
+                                 // addrs, lens, groups, k, r, P, parity, dests, symlen_out, tables
+                                 const qfec::TableEncodeLaunch a{d_packet_addrs, d_packet_lens, G, k, r, P, d_parity, nullptr,
+                                                                 d_symbol_len_out, tables};
+                                 return table_encode_done(qfec::launch_encode_gather_var(a, s),
+                                                          "qfec::launch_encode_gather_var(a, pick_stream(ctx, stream))");
+                               });
+  });
 }
 
 // ---- the recover with a table of destinations (fec_scatter.hip) ----
-static int fec_recover_scatter_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
-                                           const uint32_t* d_shard_lens, const uint64_t* d_dest_addrs, uint64_t G,
-                                           uint32_t k, uint32_t r, uint32_t P, uint8_t* d_status,
-                                           uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream) {
-  if (!ctx || !d_shard_addrs || !d_dest_addrs) {
-    set_error("scatter recover: %s is NULL", !ctx             ? "the context"
-                                             : !d_shard_addrs ? "d_shard_addrs"
-                                                              : "d_dest_addrs (the destination table)");
-    return FEC_ERR_NULL;
-  }
-  // behind the record offsets the symbol lengths the kernel cuts its stores at, when there is a
-  // length table and the caller asks for none
-  const bool own_symlen = d_shard_lens != nullptr && d_symbol_len_out == nullptr;
-  return table_recover_locked("scatter recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out, stream,
-                              own_symlen ? 2 : 1,
-                              "stream_workspace(ctx, s, (own_symlen ? 2 : 1) * G * sizeof(uint32_t), &ws)",
-                              [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
-                                a.lens = d_shard_lens;
-                                a.dests = d_dest_addrs;
-                                a.symlen = own_symlen ? a.rec_off + G : d_symbol_len_out;
-                                QFEC_HIP(qfec::launch_recover_scatter(a, s));
-                                return FEC_OK;
-                              });
-}
-
 QFEC_EXPORT int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
                                            const uint32_t* d_shard_lens, const uint64_t* d_dest_addrs, uint64_t G,
                                            uint32_t k, uint32_t r, uint32_t P, uint8_t* d_status,
                                            uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_recover_scatter_rs_dev_impl(ctx, d_shard_addrs, d_shard_lens, d_dest_addrs, G, k, r, P,
-                                                               d_status, d_masks_out, d_symbol_len_out, stream));
-}
-
-// ---- the encode with a table of destinations (fec_scatter_encode.hip) ----
-static int fec_encode_scatter_rs_dev_impl(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
-                                          const uint32_t* d_packet_lens, const uint64_t* d_dest_addrs, uint64_t G,
-                                          uint32_t k, uint32_t r, uint32_t P, uint32_t* d_symbol_len_out,
-                                          void* stream) {
-  if (!ctx || !d_packet_addrs || !d_dest_addrs) {
-    set_error("scatter encode: %s is NULL", !ctx              ? "the context"
-                                            : !d_packet_addrs ? "d_packet_addrs"
-                                                              : "d_dest_addrs (the destination table)");
-    return FEC_ERR_NULL;
-  }
-  return table_encode_locked("scatter encode", ctx, G, k, r, P, stream, [&](const void* tables, hipStream_t s) {
-    // addrs, lens, groups, k, r, P, parity, dests, symlen_out, tables
-    const qfec::TableEncodeLaunch a{d_packet_addrs, d_packet_lens, G, k, r, P, nullptr, d_dest_addrs, d_symbol_len_out,
-                                    tables};
-    return table_encode_done(qfec::launch_encode_scatter(a, s), "qfec::launch_encode_scatter(a, pick_stream(ctx, stream))");
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_shard_addrs || !d_dest_addrs) {
+      set_error("scatter recover: %s is NULL", !ctx             ? "the context"
+                                               : !d_shard_addrs ? "d_shard_addrs"
+                                                                : "d_dest_addrs (the destination table)");
+      return FEC_ERR_NULL;
+    }
+    // behind the record offsets the symbol lengths the kernel cuts its stores at, when there is a
+    // length table and the caller asks for none
+    const bool own_symlen = d_shard_lens != nullptr && d_symbol_len_out == nullptr;
+    return table_recover_locked("scatter recover", ctx, d_shard_addrs, G, k, r, P, d_status, d_masks_out, stream,
+                                own_symlen ? 2 : 1,
+                                "stream_workspace(ctx, s, (own_symlen ? 2 : 1) * G * sizeof(uint32_t), &ws)",
+                                [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
+                                  a.lens = d_shard_lens;
+                                  a.dests = d_dest_addrs;
+                                  a.symlen = own_symlen ? a.rec_off + G : d_symbol_len_out;
+                                  QFEC_HIP(qfec::launch_recover_scatter(a, s));
+                                  return FEC_OK;
+                                });
   });
 }
 
+// ---- the encode with a table of destinations (fec_scatter_encode.hip) ----
 QFEC_EXPORT int fec_encode_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
                                           const uint32_t* d_packet_lens, const uint64_t* d_dest_addrs, uint64_t G,
                                           uint32_t k, uint32_t r, uint32_t P, uint32_t* d_symbol_len_out,
                                           void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_encode_scatter_rs_dev_impl(ctx, d_packet_addrs, d_packet_lens, d_dest_addrs, G, k, r, P,
-                                                              d_symbol_len_out, stream));
-}
-
-static int fec_decode_prepare_impl(FECEncoderCtx* ctx, uint32_t k, uint32_t r, uint64_t* bytes_out) {
-  if (!ctx) return FEC_ERR_NULL;
-  int rc = check_shape(1, k, r, 1, true);
-  if (rc != FEC_OK) return rc;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  DecodePlan* plan = nullptr;
-  rc = get_decode_plan(ctx, k, r, &plan);
-  if (rc != FEC_OK) return rc;
-  if (bytes_out) *bytes_out = plan->dense ? plan->layout.total_bytes : 0;  // 0: sparse per-call plans
-  return FEC_OK;
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_packet_addrs || !d_dest_addrs) {
+      set_error("scatter encode: %s is NULL", !ctx              ? "the context"
+                                              : !d_packet_addrs ? "d_packet_addrs"
+                                                                : "d_dest_addrs (the destination table)");
+      return FEC_ERR_NULL;
+    }
+    return table_encode_locked("scatter encode", ctx, G, k, r, P, stream, [&](const void* tables, hipStream_t s) {
+      // addrs, lens, groups, k, r, P, parity, dests, symlen_out, tables
+      const qfec::TableEncodeLaunch a{d_packet_addrs, d_packet_lens, G, k, r, P, nullptr, d_dest_addrs, d_symbol_len_out,
+                                      tables};
+      return table_encode_done(qfec::launch_encode_scatter(a, s), "qfec::launch_encode_scatter(a, pick_stream(ctx, stream))");
+    });
+  });
 }
 
 QFEC_EXPORT int fec_decode_prepare(FECEncoderCtx* ctx, uint32_t k, uint32_t r, uint64_t* bytes_out) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_decode_prepare_impl(ctx, k, r, bytes_out));
-}
-
-static int fec_fill_random_dev_impl(FECEncoderCtx* ctx, uint8_t* d_dst, uint64_t nbytes, uint64_t seed,
-                                    uint64_t byte_offset, void* stream) {
-  if (!ctx || !d_dst) return FEC_ERR_NULL;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  QFEC_HIP(qfec::launch_fill_splitmix(d_dst, nbytes, seed, byte_offset, pick_stream(ctx, stream)));
-  return FEC_OK;
+  return api_call(ctx, [&]() -> int {
+    if (!ctx) return FEC_ERR_NULL;
+    int rc = check_shape(1, k, r, 1, true);
+    if (rc != FEC_OK) return rc;
+    CtxBound bound(ctx);
+    if (bound.rc != FEC_OK) return bound.rc;
+    DecodePlan* plan = nullptr;
+    rc = get_decode_plan(ctx, k, r, &plan);
+    if (rc != FEC_OK) return rc;
+    if (bytes_out) *bytes_out = plan->dense ? plan->layout.total_bytes : 0;  // 0: sparse per-call plans
+    return FEC_OK;
+  });
 }
 
 QFEC_EXPORT int fec_fill_random_dev(FECEncoderCtx* ctx, uint8_t* d_dst, uint64_t nbytes, uint64_t seed,
                                     uint64_t byte_offset, void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_fill_random_dev_impl(ctx, d_dst, nbytes, seed, byte_offset, stream));
-}
-
-static int fec_copy_dev_impl(FECEncoderCtx* ctx, const uint8_t* d_src, uint8_t* d_dst, uint64_t nbytes,
-                             void* stream) {
-  if (!ctx || !d_src || !d_dst) return FEC_ERR_NULL;
-  if (nbytes % 16 || reinterpret_cast<uintptr_t>(d_src) % 16 || reinterpret_cast<uintptr_t>(d_dst) % 16)
-  {
-    set_error("fec_copy_dev: size and addresses must be multiples of 16");
-    return FEC_ERR_RANGE;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  DeviceGuard dg(ctx->device);
-  if (!dg.ok) return FEC_ERR_NODEV;
-  QFEC_HIP(qfec::launch_copy_words(d_src, d_dst, nbytes, pick_stream(ctx, stream)));
-  return FEC_OK;
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_dst) return FEC_ERR_NULL;
+    CtxBound bound(ctx);
+    if (bound.rc != FEC_OK) return bound.rc;
+    QFEC_HIP(qfec::launch_fill_splitmix(d_dst, nbytes, seed, byte_offset, pick_stream(ctx, stream)));
+    return FEC_OK;
+  });
 }
 
 QFEC_EXPORT int fec_copy_dev(FECEncoderCtx* ctx, const uint8_t* d_src, uint8_t* d_dst, uint64_t nbytes,
                              void* stream) {
-  g_last_error.clear();
-  return record_ctx_error(ctx, fec_copy_dev_impl(ctx, d_src, d_dst, nbytes, stream));
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_src || !d_dst) return FEC_ERR_NULL;
+    if (nbytes % 16 || reinterpret_cast<uintptr_t>(d_src) % 16 || reinterpret_cast<uintptr_t>(d_dst) % 16)
+    {
+      set_error("fec_copy_dev: size and addresses must be multiples of 16");
+      return FEC_ERR_RANGE;
+    }
+    CtxBound bound(ctx);
+    if (bound.rc != FEC_OK) return bound.rc;
+    QFEC_HIP(qfec::launch_copy_words(d_src, d_dst, nbytes, pick_stream(ctx, stream)));
+    return FEC_OK;
+  });
 }
 
 QFEC_EXPORT int fec_decode_loss_hint(FECEncoderCtx* ctx, double share) {

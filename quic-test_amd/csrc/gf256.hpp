@@ -19,6 +19,8 @@
 #include <utility>
 #include <vector>
 
+#include "fec_routes.hpp"
+
 namespace qfec {
 
 struct GF256 {
@@ -300,20 +302,17 @@ inline bool build_sparse_plan(uint32_t k, uint32_t r, const std::vector<uint8_t>
   book.clear();
   rec_off.assign(G, rec_none);
   status.assign(G, 0);
-  const uint64_t kmask = k >= 64 ? ~0ull : ((1ull << k) - 1);
-  const uint64_t rmask = r >= 64 ? ~0ull : ((1ull << r) - 1);
   std::map<std::pair<uint64_t, uint64_t>, uint32_t> seen;
   for (uint64_t g = 0; g < G; ++g) {
-    const uint64_t dm = masks[g] & kmask;
-    if (!dm) continue;
-    const uint64_t pm = k >= 64 ? 0 : (masks[g] >> k) & rmask;
-    const uint32_t e = static_cast<uint32_t>(__builtin_popcountll(dm));
-    if (e > r - static_cast<uint32_t>(__builtin_popcountll(pm))) {
+    const auto [e, unrecoverable] = mask_losses(masks[g], k, r);
+    if (e == 0) continue;
+    if (unrecoverable) {
       rec_off[g] = rec_bad;
       status[g] = 1;
       continue;
     }
-    uint64_t rsel = 0, alive = ~pm & rmask;
+    const uint64_t dm = lost_data(masks[g], k);
+    uint64_t rsel = 0, alive = ~lost_parity(masks[g], k, r) & low_bits(r);
     for (uint32_t t = 0; t < e; ++t) {
       rsel |= alive & (~alive + 1);  // lowest surviving parity row
       alive &= alive - 1;

@@ -491,8 +491,9 @@ def test_any_packet_size_gather_offsets_odd(gpu_ctx, oracle_mod, P):
 
 # ---------------- small host-resident calls: zero-copy vs DMA ----------------
 #
-# Calls of at most QUICFEC_SMALL_CALL_BYTES (default 1 MiB) run the kernels directly on
-# page-locked host memory (the caller's, or the context's staging); 0 forces the DMA paths.
+# Calls of at most QUICFEC_SMALL_CALL_BYTES (default: unlimited for page-locked buffers, 2 MiB for
+# staged ones) run the kernels directly on page-locked host memory (the caller's, or the context's
+# staging); 0 forces the DMA paths.
 
 @pytest.mark.parametrize("small", ["0", None])
 @pytest.mark.parametrize("pinned", [True, False])
