@@ -118,7 +118,10 @@ int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const ui
  * returned in *bytes_out (nullable).  When it would exceed the 2 GiB cap (e.g. k=16 r=16)
  * decode instead builds records for the patterns present in each call ("sparse plan":
  * masks are read back to the host and the call completes synchronously); *bytes_out is
- * then 0.  FEC_ERR_RANGE if k + r > 64. */
+ * then 0.  FEC_ERR_RANGE if k + r > 64.  With the context in FEC_PLAN_DEVICE
+ * (fec_decode_plan_mode) such a shape still reports 0 bytes; the call then uploads the parity
+ * matrix the device builds records from, so that the first decode allocates nothing but its
+ * workspace. */
 int fec_decode_prepare(FECEncoderCtx* ctx, uint32_t k, uint32_t r, uint64_t* bytes_out);
 
 /* The same recovery with the rebuilt packets of all groups back to back ("packed"), the
@@ -152,7 +155,9 @@ int fec_recover_batch_rs_dev_packed(FECEncoderCtx* ctx, const uint8_t* d_data, c
  * FEC_ERR_NULL for a NULL context or required pointer; FEC_ERR_RANGE for k + r > 64, for
  * packet_size < 16 (QUIC packets are never that short), for num_groups == 0 or >= 2^32, and, for
  * the recover, for a shape whose decode codebook exceeds the 2 GiB cap (fec_decode_prepare: the
- * sparse plan reads masks back on the host, which this call does not do). */
+ * sparse plan reads masks back on the host, which this call does not do) unless the context is
+ * in FEC_PLAN_DEVICE (fec_decode_plan_mode): the records are then built on the device and the
+ * recover serves the shape like any other. */
 
 /* Recover from shards wherever they are.  d_shard_addrs: num_groups*(k+r) absolute device
  * addresses (u64), group g's shard s at [g*(k+r) + s], data shards 0..k-1 then parity rows
@@ -282,6 +287,28 @@ int fec_encode_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs
  * nothing to do; results are identical either way.  share < 0 or > 1: unknown (default,
  * treated as dense loss).  The host-pointer calls measure the share from the masks. */
 int fec_decode_loss_hint(FECEncoderCtx* ctx, double share);
+
+/* Where the device-resident calls of this context take their recovery records from, for a shape
+ * whose codebook of every erasure pattern exceeds the 2 GiB cap (k=20 r=7, 24+6, 12+12, 16+16,
+ * 32+8, 60+4, 32+32, ...; fec_decode_prepare reports 0 bytes for them).
+ *   FEC_PLAN_CODEBOOK (default): fec_decode_batch_rs_dev and fec_recover_batch_rs_dev read the
+ *     masks back to the host, build a record per distinct pattern there and complete
+ *     synchronously; the three address-table recovers refuse the shape.
+ *   FEC_PLAN_DEVICE: each group's record is built on the device, in the caller stream's
+ *     workspace (at most 64 MiB of records per stream at a time; larger calls are walked in
+ *     chunks), right before the kernel that reads it.  The two contiguous calls are then
+ *     asynchronous on `stream` like every other shape, with no host synchronise and every status
+ *     byte written on the device, and fec_recover_gather_rs_dev, fec_recover_gather_var_rs_dev
+ *     and fec_recover_scatter_rs_dev serve the shape, outputs exactly as documented for the
+ *     others.  The records are byte for byte the host's, so results are identical in both modes.
+ * Shapes whose codebook fits keep it in either mode.  The host-pointer calls (fec_decode_batch_rs,
+ * fec_group_*) and the batchers keep the host-built records (their masks are on the host
+ * already), and fec_recover_batch_rs_dev_packed stays refused for these shapes.  Per context, like
+ * fec_decode_loss_hint; applies to the calls made after it returns.  FEC_ERR_NULL for a NULL
+ * context, FEC_ERR_RANGE for an unknown mode (the mode is then unchanged). */
+#define FEC_PLAN_CODEBOOK 0
+#define FEC_PLAN_DEVICE 1
+int fec_decode_plan_mode(FECEncoderCtx* ctx, int mode);
 
 /* ---- utilities for benchmarks and tests ---- */
 /* Fill d_dst with the counter-based splitmix64 stream (byte i of the stream at

@@ -46,6 +46,17 @@ constexpr int kDecodeWaveNoBranch = 6;   //   same, no branch on coefficient 0 /
 constexpr int kDecodeFused = 7;          // one wave per group, 16-B and 4-B pieces fused
 constexpr int kDecodeFusedDirect = 8;    //   same, survivor addresses from the erasure mask
 
+// Records built on the device, per call, for a shape whose codebook of every pattern is past its
+// cap (FEC_PLAN_DEVICE; fec_plan.hip build_records): part of a decode's or a table recover's
+// launch description.  arena == nullptr: the records come from the codebook.  The sizes are
+// plan_arena()'s, below.
+struct PlanLaunch {
+  uint8_t* arena = nullptr;         // per_chunk slots of `stride` bytes, in the caller stream's workspace
+  uint64_t stride = 0;              // bytes per slot, a multiple of 32
+  uint64_t per_chunk = 0;           // groups whose records the arena holds at a time
+  const uint8_t* matrix = nullptr;  // the r x k parity matrix, device
+};
+
 struct DecodeLaunch {
   int variant = kDecodeAuto;
   // Where rebuilt shards are stored, same layout as `data`; nullptr = in place in `data`.
@@ -79,6 +90,9 @@ struct DecodeLaunch {
   // compact_out with rec_off = the packed rows' row_start (fec_recover_batch_rs_dev_packed):
   // rows are placed by global row index, so chunked launches must not offset `out`.
   bool packed_rows = false;
+  // Records built on the device (plan.arena set; needs rec_ready, masks and rec_off): classify,
+  // then chunk after chunk build_records and the form's passes, `codebook` being the arena.
+  PlanLaunch plan;
 };
 
 constexpr uint32_t kDecodeScanGroups = 8;
@@ -431,6 +445,10 @@ struct TableRecoverLaunch {
   const uint8_t* codebook;   // dense CoefEntry codebook (the one `classify` addresses), device
   const uint64_t* binom;     // device, 65 x 65
   LevelMeta meta;
+  bool rec_ready = false;    // rec_off already holds the records of `codebook` (a chunk of a device
+                             // plan): no classify, as DecodeLaunch::rec_ready
+  PlanLaunch plan;           // records built on the device (plan.arena set; needs masks_out): classify,
+                             // then chunk after chunk build_records and the call's passes
 };
 
 // An encode (fec_encode_gather_var_rs_dev, fec_encode_scatter_rs_dev).  Exactly one of `parity`
@@ -487,6 +505,99 @@ inline TableRecoverForm table_recover_form(uint32_t k, uint32_t r, uint32_t P, b
     f.K = 0, f.MAXE = 8, f.POL = kGatherPol | kNoCoefBranch;
   }
   return f;
+}
+
+// ---- records built on the device (FEC_PLAN_DEVICE; fec_plan.hip, fec_plan_build.hpp) ----
+// A shape whose codebook of every pattern is past its cap has no record to look up.  With the
+// context in FEC_PLAN_DEVICE each group's record is built on the device into an arena of slots in
+// the caller stream's workspace, right before the kernels that read it; those are the runtime-k
+// record-addressed forms (decode_wave<0, 8>, the table recovers' <0, 8>, decode_bytes), which read
+// a record at codebook + rec_off[g] * 32 wherever it came from.
+//
+// A slot holds the largest record of the shape, record_bytes(k, min(k, r)) (gf256.hpp: a 128-B
+// header, then 32 B per row and survivor), a multiple of 32.
+constexpr uint64_t plan_slot_stride(uint32_t k, uint32_t r) { return 128u + uint64_t{k < r ? k : r} * k * 32u; }
+// The arena's budget per caller stream: the size of a host-pipeline chunk (kPipeChunkBytes).  A
+// cap on memory, not a tuned number: at most 16 stream workspaces exist (fec_shim.cpp), so 1 GiB
+// in all.  The test library's TestKnob::kPlanArenaBytes lowers it.
+constexpr uint64_t kPlanArenaBytes = 64ull << 20;
+inline uint64_t plan_arena_budget() {
+  const long n = test_knob(TestKnob::kPlanArenaBytes, 0);
+  return n > 0 && static_cast<uint64_t>(n) < kPlanArenaBytes ? static_cast<uint64_t>(n) : kPlanArenaBytes;
+}
+// rec_off values a record may have: below the markers kRecBad, kRecNone (fec_kernels.hpp).
+constexpr uint32_t kPlanRecLimit = 0xFFFFFFFEu;
+// The arena of a call of G groups under `budget`: max(1, budget / stride) slots, at most G.  The
+// call walks its groups in chunks of per_chunk: group i of a chunk has its record in slot i,
+// rec_off = i * stride / 32 -- no atomics, no compaction -- and the arena is reused chunk after
+// chunk in stream order.  Groups with nothing to rebuild leave their slot unwritten and unread.
+struct PlanArena {
+  uint64_t stride, per_chunk, bytes;  // bytes = per_chunk * stride
+};
+inline PlanArena plan_arena(uint32_t k, uint32_t r, uint64_t G, uint64_t budget) {
+  const uint64_t stride = plan_slot_stride(k, r);
+  uint64_t per = budget / stride;
+  if (per == 0) per = 1;
+  if (per > G) per = G;
+  return {stride, per, per * stride};
+}
+inline uint32_t plan_slot_rec(const PlanArena& a, uint64_t slot) { return static_cast<uint32_t>(slot * (a.stride / 32u)); }
+// The chunks of the walk, in order: f(first group, groups) for [0, G) in pieces of per_chunk, until
+// f returns false (fec_launch.hpp for_plan_chunks launches through it).
+template <typename F>
+inline bool plan_chunks(uint64_t G, uint64_t per_chunk, F f) {
+  for (uint64_t g0 = 0; g0 < G; g0 += per_chunk)
+    if (!f(g0, G - g0 < per_chunk ? G - g0 : per_chunk)) return false;
+  return true;
+}
+// The workspace of a device-plan call, byte offsets from its start: G record offsets; G masks (a
+// table recover whose caller gives no d_masks_out: build_records reads the masks the classify
+// derived); G symbol lengths (the scatter recover with a length table whose caller asks for none,
+// as in codebook mode); the arena, 256-B aligned.  A region not needed is empty.
+struct PlanWorkspace {
+  uint64_t rec_off, masks, symlen, arena, bytes;
+};
+inline PlanWorkspace plan_workspace(uint64_t G, bool own_masks, bool own_symlen, const PlanArena& a) {
+  PlanWorkspace w{};
+  w.rec_off = 0;
+  w.masks = (G * sizeof(uint32_t) + 7u) & ~uint64_t{7};
+  w.symlen = w.masks + (own_masks ? G * sizeof(uint64_t) : 0);
+  w.arena = (w.symlen + (own_symlen ? G * sizeof(uint32_t) : 0) + 255u) & ~uint64_t{255};
+  w.bytes = w.arena + a.bytes;
+  return w;
+}
+// Groups [g0, g0 + gn) of call `a` as a launch of their own, their records ready in the arena.
+inline DecodeLaunch plan_chunk(const DecodeLaunch& a, uint64_t g0, uint64_t gn) {
+  DecodeLaunch c = a;
+  const uint64_t P = a.P;
+  c.data = a.data + g0 * a.k * P;
+  c.parity = a.parity + g0 * a.r * P;
+  c.masks = a.masks + g0;
+  c.rec_off = a.rec_off + g0;
+  if (a.status) c.status = a.status + g0;
+  if (a.out) c.out = a.out + g0 * (a.compact_out ? a.r : a.k) * P;
+  c.groups = gn;
+  c.rec_ready = true;
+  c.codebook = a.plan.arena;
+  c.plan = PlanLaunch{};
+  return c;
+}
+inline TableRecoverLaunch plan_chunk(const TableRecoverLaunch& a, uint64_t g0, uint64_t gn) {
+  TableRecoverLaunch c = a;
+  const uint64_t n = a.k + a.r;
+  c.addrs = a.addrs + g0 * n;
+  if (a.lens) c.lens = a.lens + g0 * n;
+  if (a.dests) c.dests = a.dests + g0 * a.k;
+  if (a.out) c.out = a.out + g0 * a.r * static_cast<uint64_t>(a.P);
+  if (a.status) c.status = a.status + g0;
+  if (a.masks_out) c.masks_out = a.masks_out + g0;
+  if (a.symlen) c.symlen = a.symlen + g0;
+  c.rec_off = a.rec_off + g0;
+  c.groups = gn;
+  c.rec_ready = true;
+  c.codebook = a.plan.arena;
+  c.plan = PlanLaunch{};
+  return c;
 }
 
 // The passes of a runtime-k encode: at most kEncodePassRows parity rows per launch, pass p the rows

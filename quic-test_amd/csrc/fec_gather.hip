@@ -100,8 +100,10 @@ hipError_t launch_recover_gather(const TableRecoverLaunch& a, hipStream_t s) {
   QFEC_TABLE_RECOVER_FORMS(QFEC_GATHER, ~)
 #undef QFEC_GATHER
   if (run == nullptr) return hipErrorNotSupported;
-  const hipError_t e = run_classify_table<Lens::kNone>(a, static_cast<int64_t>(GatherLaunchForm::kClassifyGather), s);
-  return e != hipSuccess ? e : run(a, s);
+  const auto classify = [s](const TableRecoverLaunch& c) {
+    return run_classify_table<Lens::kNone>(c, static_cast<int64_t>(GatherLaunchForm::kClassifyGather), s);
+  };
+  return run_table_recover(a, classify, run, s);
 }
 
 }  // namespace qfec

@@ -207,9 +207,10 @@ hipError_t launch_recover_gather_var(const TableRecoverLaunch& a, hipStream_t s)
   QFEC_TABLE_RECOVER_FORMS(QFEC_GATHER_VAR, ~)
 #undef QFEC_GATHER_VAR
   if (run == nullptr) return hipErrorNotSupported;
-  const hipError_t e =
-      run_classify_table<Lens::kGiven>(a, static_cast<int64_t>(GatherVarLaunchForm::kClassifyGatherVar), s);
-  return e != hipSuccess ? e : run(a, s);
+  const auto classify = [s](const TableRecoverLaunch& c) {
+    return run_classify_table<Lens::kGiven>(c, static_cast<int64_t>(GatherVarLaunchForm::kClassifyGatherVar), s);
+  };
+  return run_table_recover(a, classify, run, s);
 }
 
 // The passes of table_encode_form (fec_forms.hpp); the first owns the XOR row.

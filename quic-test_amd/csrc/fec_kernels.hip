@@ -2357,6 +2357,25 @@ hipError_t launch_recover_runs(const RunsLaunch& a, hipStream_t s) {
 hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s) {
   const DecodeForm f = decode_form(a);
   if (f.kernel == DecodeKernel::kNone) return hipSuccess;
+  if (a.plan.arena != nullptr) {
+    // Records built on the device: the classify on an all-zero level table (0 where a record is
+    // needed, else kRecNone / kRecBad, and every status byte), then per chunk of the arena the
+    // records and this form's launches on them (plan_chunk: rec_ready, the arena as codebook).
+    if (!a.rec_ready || !f.rec_off || a.rec_off == nullptr || a.masks == nullptr || a.packed_rows || a.plan.per_chunk == 0)
+      return hipErrorInvalidValue;
+    return for_plan_chunks(
+        a.groups, a.plan.per_chunk,
+        [&] {
+          DecodeLaunch c = a;
+          c.meta = LevelMeta{};
+          return run_classify(c, s);
+        },
+        [&](uint64_t g0, uint64_t gn) {
+          return launch_build_records(a.plan, a.masks + g0, a.rec_off + g0, a.status ? a.status + g0 : nullptr, g0, gn, a.k,
+                                      a.r, s);
+        },
+        [&](uint64_t g0, uint64_t gn) { return launch_decode(plan_chunk(a, g0, gn), s); });
+  }
   // the codebook's format must be the one the chosen form reads
   if (a.compact_tables != f.compact_tables) return hipErrorInvalidValue;
   if (f.rec_off && a.rec_off == nullptr) return hipErrorInvalidValue;

@@ -53,6 +53,13 @@ hipError_t launch_recover_scatter(const TableRecoverLaunch& a, hipStream_t s);
 // Encode from an address table (with a nullable length table) into a table of destinations
 // (fec_scatter_encode.hip): table_encode_form's passes of encode_scatter.
 hipError_t launch_encode_scatter(const TableEncodeLaunch& a, hipStream_t s);
+// The records of one plan chunk built on the device (fec_plan.hip build_records): for each of the
+// `groups` groups from masks / rec_off / status (the chunk's first entries) whose rec_off the
+// classify left below kRecBad, the record of its mask into slot i of p.arena and rec_off[i] = its
+// place there; a group whose build meets a zero pivot gets kRecBad and status 1.  first_group: the
+// chunk's place in the call, for the launch trace.
+hipError_t launch_build_records(const PlanLaunch& p, const uint64_t* masks, uint32_t* rec_off, uint8_t* status,
+                                uint64_t first_group, uint64_t groups, uint32_t k, uint32_t r, hipStream_t s);
 // Packed recover rows: row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.

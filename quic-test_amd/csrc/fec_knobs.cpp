@@ -24,7 +24,7 @@ const char* const kNames[] = {
     "QUICFEC_RESIDENT_TEST_NOLAUNCH", "QUICFEC_RESIDENT_TEST_EPOCH", "QUICFEC_RESIDENT_TEST_TEAR",
     "QUICFEC_RESIDENT_TEST_FAIL_AT", "QUICFEC_RESIDENT_SPREAD",    "QUICFEC_RESIDENT_STAMPS",
     "QUICFEC_RESIDENT_SLOW_US",    "QUICFEC_COALESCE_STAMPS",      "QUICFEC_COALESCE_SPIN_PAUSE",
-    "QUICFEC_COALESCE_SPIN_YIELD",
+    "QUICFEC_COALESCE_SPIN_YIELD",   "QUICFEC_PLAN_ARENA_BYTES",
 };
 static_assert(sizeof(kNames) / sizeof(kNames[0]) == static_cast<size_t>(TestKnob::kCount), "one name per switch");
 }  // namespace

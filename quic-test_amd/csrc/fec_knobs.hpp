@@ -41,6 +41,7 @@ enum class TestKnob : int {
   kCoalesceStamps,    // coalescer: creation and first batches' phase times, to stderr
   kCoalesceSpinPause, // coalescer: a waiting caller's pause rounds before it yields
   kCoalesceSpinYield, // coalescer: ... and its yield rounds before it sleeps
+  kPlanArenaBytes,    // record arena of a device-plan call, bytes (forces several plan chunks)
   kCount
 };
 
@@ -100,6 +101,13 @@ enum class ScatterLaunchForm : int64_t {
 enum class ScatterEncodeLaunchForm : int64_t {
   kEncodeScatter = 25,  // LaunchRecord::first: this pass owns the XOR row; LaunchRecord::direct: 1
                         // with a length table (VAR), 0 without
+};
+
+// The record builder of the device plans (fec_plan.hip), numbered on in a list of its own; named by
+// quicfec.PLAN_LAUNCH_FORMS.
+enum class PlanLaunchForm : int64_t {
+  kBuildRecords = 26,  // first_item / items: the plan chunk's first group and its groups; aux: the
+                       // arena slot of the launch's first group
 };
 
 // One launch: 16 words, -1 where a field does not apply to the form.

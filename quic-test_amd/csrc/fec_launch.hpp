@@ -80,6 +80,23 @@ hipError_t for_wave_passes(uint64_t groups, uint32_t r, uint32_t maxe, F launch)
   return hipSuccess;
 }
 
+// The walk of a call whose records are built on the device (fec_forms.hpp PlanLaunch): every group
+// classified once, then chunk after chunk of the arena's per_chunk groups: build(first group,
+// groups) launches build_records for the chunk, consume(first group, groups) every row pass of the
+// call's kernel on it -- in stream order, so the arena is free again when the next chunk's records
+// are written.  Each returns its error; stops at the first.
+template <typename C, typename B, typename F>
+hipError_t for_plan_chunks(uint64_t groups, uint64_t per_chunk, C classify, B build, F consume) {
+  hipError_t e = classify();
+  if (e != hipSuccess) return e;
+  plan_chunks(groups, per_chunk, [&](uint64_t g0, uint64_t gn) {
+    e = build(g0, gn);
+    if (e == hipSuccess) e = consume(g0, gn);
+    return e == hipSuccess;
+  });
+  return e;
+}
+
 // The passes of a runtime-k encode over its r parity rows (fec_forms.hpp encode_pass_rows), in row
 // order: launch(row0, rows, first) launches pass [row0, row0 + rows), every chunk of it, and
 // returns its error; `first`: the pass that owns the XOR row.  Stops at the first error.

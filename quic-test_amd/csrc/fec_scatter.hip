@@ -196,9 +196,10 @@ hipError_t launch_recover_scatter(const TableRecoverLaunch& a, hipStream_t s) {
   QFEC_TABLE_RECOVER_FORMS(QFEC_SCATTER, true)
 #undef QFEC_SCATTER
   if (run == nullptr) return hipErrorNotSupported;
-  const hipError_t e =
-      run_classify_table<Lens::kNullable>(a, static_cast<int64_t>(ScatterLaunchForm::kClassifyScatter), s);
-  return e != hipSuccess ? e : run(a, s);
+  const auto classify = [s](const TableRecoverLaunch& c) {
+    return run_classify_table<Lens::kNullable>(c, static_cast<int64_t>(ScatterLaunchForm::kClassifyScatter), s);
+  };
+  return run_table_recover(a, classify, run, s);
 }
 
 }  // namespace qfec

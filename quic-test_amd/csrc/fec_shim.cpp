@@ -125,6 +125,7 @@ struct DecodePlan {
   DevBuf cbook;
   std::vector<uint8_t> M;      // parity matrix, for sparse per-call records
   DevBuf sparse_book;          // the last sparse call's records
+  DevBuf d_matrix;             // M on the device, for records built there (FEC_PLAN_DEVICE); on first use
 };
 
 constexpr uint64_t kCodebookCap = 2ull << 30;  // 2 GiB of recovery tables per (k, r)
@@ -319,6 +320,9 @@ struct FECEncoderCtx {
   // fec_decode_loss_hint: expected share of groups with lost data in device-resident decode
   // calls (< 0: unknown, treated as dense).
   double decode_need_share = -1.0;
+  // fec_decode_plan_mode: where the device-resident calls take the records of a shape without a
+  // dense codebook from
+  int plan_mode = FEC_PLAN_CODEBOOK;
   // per-stream record-offset workspaces of the device-resident decodes (stream_workspace)
   std::vector<std::unique_ptr<StreamWorkspace>> stream_ws;
   uint64_t ws_clock = 0;
@@ -653,7 +657,36 @@ struct DecodeCall {
   bool compact_out = false;        // rebuilt rows one run per group, `data` only read (DecodeLaunch)
   uint32_t* row_start = nullptr;   // set: packed rows (fec_recover_batch_rs_dev_packed), written
   uint64_t* row_total = nullptr;   //   with them, nullable: all rows
+  bool device_masks = false;       // a device-resident call (the masks are the caller's device memory): in
+                                   // FEC_PLAN_DEVICE a shape without a dense codebook has its records built there
 };
+
+// The parity matrix of a plan on the device, for build_records (uploaded once per plan).
+int plan_matrix(DecodePlan* plan, const uint8_t** out) {
+  if (!plan->d_matrix.ptr) {
+    QFEC_HIP(plan->d_matrix.ensure(plan->M.size()));
+    QFEC_HIP(hipMemcpy(plan->d_matrix.ptr, plan->M.data(), plan->M.size(), hipMemcpyHostToDevice));
+  }
+  *out = plan->d_matrix.as<uint8_t>();
+  return FEC_OK;
+}
+
+// The workspace of a device-plan call of G groups on caller stream s (fec_forms.hpp plan_arena,
+// plan_workspace) and its launch description.
+int plan_workspace_locked(FECEncoderCtx* ctx, DecodePlan* plan, hipStream_t s, uint64_t G, uint32_t k, uint32_t r,
+                          bool own_masks, bool own_symlen, qfec::PlanWorkspace* w, uint8_t** ws, qfec::PlanLaunch* p) {
+  const qfec::PlanArena arena = qfec::plan_arena(k, r, G, qfec::plan_arena_budget());
+  *w = qfec::plan_workspace(G, own_masks, own_symlen, arena);
+  int rc = plan_matrix(plan, &p->matrix);
+  if (rc != FEC_OK) return rc;
+  void* base = nullptr;
+  QFEC_HIP(stream_workspace(ctx, s, w->bytes, &base));
+  *ws = static_cast<uint8_t*>(base);
+  p->arena = *ws + w->arena;
+  p->stride = arena.stride;
+  p->per_chunk = arena.per_chunk;
+  return FEC_OK;
+}
 
 // Caller holds ctx->mu and the device.
 int decode_dev_locked(FECEncoderCtx* ctx, const DecodeCall& c) {
@@ -742,6 +775,18 @@ int decode_dev_locked(FECEncoderCtx* ctx, const DecodeCall& c) {
     void* ws = nullptr;
     QFEC_HIP(stream_workspace(ctx, s, qfec::rows_prefix_workspace_bytes(G), &ws));
     QFEC_HIP(qfec::launch_rows_prefix(d_masks, G, k, r, row_start, static_cast<uint32_t*>(ws), row_total, s));
+  }
+  if (!plan->dense && c.device_masks && ctx->plan_mode == FEC_PLAN_DEVICE) {
+    // Records built on the device, in the caller stream's workspace, chunk after chunk ahead of
+    // the form's kernels: nothing comes to the host and the call is asynchronous on s.
+    qfec::PlanWorkspace w;
+    uint8_t* ws = nullptr;
+    rc = plan_workspace_locked(ctx, plan, s, G, k, r, false, false, &w, &ws, &a.plan);
+    if (rc != FEC_OK) return rc;
+    a.rec_off = reinterpret_cast<uint32_t*>(ws + w.rec_off);
+    a.codebook = a.plan.arena;
+    QFEC_HIP(qfec::launch_decode(a, s));
+    return FEC_OK;
   }
   // Workspace: the caller's slot buffer (pipeline slots: private stream, calls serialised
   // by the context lock), else one private to this call.
@@ -1592,6 +1637,7 @@ QFEC_EXPORT int fec_decode_batch_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, con
     DecodeCall c;
     c.data = d_data, c.parity = d_parity, c.masks = d_masks;
     c.shape = {G, k, r, P}, c.status = d_status, c.stream = pick_stream(ctx, stream);
+    c.device_masks = true;
     return decode_dev_locked(ctx, c);
   });
 }
@@ -1640,6 +1686,7 @@ QFEC_EXPORT int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_da
     c.data = const_cast<uint8_t*>(d_data);  // the kernels only read `data` when the output is compact
     c.parity = d_parity, c.masks = d_masks, c.out = d_rebuilt, c.compact_out = true;
     c.shape = {G, k, r, P}, c.status = d_status, c.stream = pick_stream(ctx, stream);
+    c.device_masks = true;
     return decode_dev_locked(ctx, c);
   });
 }
@@ -1676,14 +1723,17 @@ int check_gather_shape(const char* what, uint64_t G, uint32_t k, uint32_t r, uin
 constexpr const char* kRecOffWorkspaceCall = "stream_workspace(ctx, s, G * sizeof(uint32_t), &ws)";
 
 // What the three table recovers do between their own NULL checks and their launch.  Refused
-// before any lock or device call: the shape, then a codebook past the cap (the sparse plan reads
-// masks back on the host; judged before a plan and its codebook are built).  Then, under the
-// context's lock and on its device: the decode plan, the stream, the launch fields every table
-// recover sets, and `ws_words` uint32_t per group of the caller stream's workspace (shared in
-// stream order with the other decodes), the first G of them the record offsets; `ws_call` is
-// the text a failure of that step reports (each call's message as it was: QFEC_HIP reports the
-// failing expression, and the calls wrote this one differently).  launch(a, s) adds the call's
-// own fields and launches, the lock still held.
+// before any lock or device call: the shape.  Refused under the context's lock, before a plan and
+// its codebook are built: a codebook past the cap while the context is in FEC_PLAN_CODEBOOK (the
+// sparse plan reads masks back on the host).  Then, on the context's device: the decode plan, the
+// stream, the launch fields every table recover sets, and `ws_words` uint32_t per group of the
+// caller stream's workspace (shared in stream order with the other decodes), the first G of them
+// the record offsets, the second G (ws_words = 2: the scatter's own symbol lengths) a.symlen;
+// `ws_call` is the text a failure of that step reports (each call's message as it was: QFEC_HIP
+// reports the failing expression, and the calls wrote this one differently).  In FEC_PLAN_DEVICE a
+// shape past the cap takes plan_workspace's layout instead -- record offsets, the masks when the
+// caller gives no d_masks_out, the symbol lengths, the record arena -- and a.plan describes the
+// arena.  launch(a, s) adds the call's own fields and launches, the lock still held.
 template <typename F>
 int table_recover_locked(const char* what, FECEncoderCtx* ctx, const uint64_t* d_shard_addrs, uint64_t G, uint32_t k,
                          uint32_t r, uint32_t P, uint8_t* d_status, uint64_t* d_masks_out, void* stream,
@@ -1691,12 +1741,14 @@ int table_recover_locked(const char* what, FECEncoderCtx* ctx, const uint64_t* d
   int rc = check_gather_shape(what, G, k, r, P);
   if (rc != FEC_OK) return rc;
   qfec::CodebookLayout layout;
-  if (!qfec::codebook_layout(k, r, kCodebookCap, layout)) {
+  const bool dense = qfec::codebook_layout(k, r, kCodebookCap, layout);
+  CtxBound bound(ctx);
+  if (!dense && ctx->plan_mode != FEC_PLAN_DEVICE) {
     set_error("%s: the codebook of k=%u r=%u exceeds the %llu-byte cap (sparse-plan shape: use "
-              "fec_recover_batch_rs_dev)", what, k, r, static_cast<unsigned long long>(kCodebookCap));
+              "fec_recover_batch_rs_dev, or fec_decode_plan_mode(ctx, FEC_PLAN_DEVICE))", what, k, r,
+              static_cast<unsigned long long>(kCodebookCap));
     return FEC_ERR_RANGE;
   }
-  CtxBound bound(ctx);
   if (bound.rc != FEC_OK) return bound.rc;
   DecodePlan* plan = nullptr;
   rc = get_decode_plan(ctx, k, r, &plan);
@@ -1713,10 +1765,22 @@ int table_recover_locked(const char* what, FECEncoderCtx* ctx, const uint64_t* d
   a.codebook = plan->codebook.as<uint8_t>();
   a.binom = ctx->d_binom.as<uint64_t>();
   a.meta = level_meta(plan->layout, r);
+  if (!plan->dense) {
+    qfec::PlanWorkspace w;
+    uint8_t* pws = nullptr;
+    rc = plan_workspace_locked(ctx, plan, s, G, k, r, d_masks_out == nullptr, ws_words == 2, &w, &pws, &a.plan);
+    if (rc != FEC_OK) return rc;
+    a.rec_off = reinterpret_cast<uint32_t*>(pws + w.rec_off);
+    if (d_masks_out == nullptr) a.masks_out = reinterpret_cast<uint64_t*>(pws + w.masks);
+    if (ws_words == 2) a.symlen = reinterpret_cast<uint32_t*>(pws + w.symlen);
+    a.codebook = a.plan.arena;
+    return launch(a, s);
+  }
   void* ws = nullptr;
   const hipError_t we = stream_workspace(ctx, s, ws_words * G * sizeof(uint32_t), &ws);
   if (we != hipSuccess) return hip_fail(we, ws_call);
   a.rec_off = static_cast<uint32_t*>(ws);
+  if (ws_words == 2) a.symlen = a.rec_off + G;
   return launch(a, s);
 }
 
@@ -1841,7 +1905,7 @@ QFEC_EXPORT int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d
                                 [&](qfec::TableRecoverLaunch& a, hipStream_t s) {
                                   a.lens = d_shard_lens;
                                   a.dests = d_dest_addrs;
-                                  a.symlen = own_symlen ? a.rec_off + G : d_symbol_len_out;
+                                  if (!own_symlen) a.symlen = d_symbol_len_out;  // else the workspace's
                                   QFEC_HIP(qfec::launch_recover_scatter(a, s));
                                   return FEC_OK;
                                 });
@@ -1880,6 +1944,10 @@ QFEC_EXPORT int fec_decode_prepare(FECEncoderCtx* ctx, uint32_t k, uint32_t r, u
     rc = get_decode_plan(ctx, k, r, &plan);
     if (rc != FEC_OK) return rc;
     if (bytes_out) *bytes_out = plan->dense ? plan->layout.total_bytes : 0;  // 0: sparse per-call plans
+    if (!plan->dense && ctx->plan_mode == FEC_PLAN_DEVICE) {
+      const uint8_t* matrix = nullptr;
+      return plan_matrix(plan, &matrix);  // all a device plan keeps between calls
+    }
     return FEC_OK;
   });
 }
@@ -1916,6 +1984,19 @@ QFEC_EXPORT int fec_decode_loss_hint(FECEncoderCtx* ctx, double share) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   ctx->decode_need_share = share >= 0.0 && share <= 1.0 ? share : -1.0;
   return FEC_OK;
+}
+
+QFEC_EXPORT int fec_decode_plan_mode(FECEncoderCtx* ctx, int mode) {
+  return api_call(ctx, [&]() -> int {
+    if (!ctx) return FEC_ERR_NULL;
+    if (mode != FEC_PLAN_CODEBOOK && mode != FEC_PLAN_DEVICE) {
+      set_error("fec_decode_plan_mode: unknown mode %d", mode);
+      return FEC_ERR_RANGE;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->plan_mode = mode;
+    return FEC_OK;
+  });
 }
 
 QFEC_EXPORT int fec_synchronize(FECEncoderCtx* ctx) {

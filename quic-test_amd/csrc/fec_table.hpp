@@ -171,5 +171,33 @@ hipError_t run_classify_table(const TableRecoverLaunch& a, int64_t form, hipStre
   });
 }
 
+// The launches of a table recover once its form is chosen: classify(a) -- the call's
+// run_classify_table -- then run(a, s), every pass of its kernel.  With records built on the device
+// (a.plan.arena set, fec_forms.hpp PlanLaunch): the classify on an all-zero level table (0 where a
+// record is needed, else kRecNone / kRecBad; status, masks and symbol lengths as ever), then per
+// chunk of the arena build_records from the masks the classify wrote and run() on the chunk
+// (plan_chunk: rec_ready, the arena as codebook).
+template <typename C>
+hipError_t run_table_recover(const TableRecoverLaunch& a, C classify,
+                             hipError_t (*run)(const TableRecoverLaunch&, hipStream_t), hipStream_t s) {
+  if (a.plan.arena == nullptr) {
+    const hipError_t e = a.rec_ready ? hipSuccess : classify(a);
+    return e != hipSuccess ? e : run(a, s);
+  }
+  if (a.masks_out == nullptr || a.plan.per_chunk == 0) return hipErrorInvalidValue;
+  return for_plan_chunks(
+      a.groups, a.plan.per_chunk,
+      [&] {
+        TableRecoverLaunch c = a;
+        c.meta = LevelMeta{};
+        return classify(c);
+      },
+      [&](uint64_t g0, uint64_t gn) {
+        return launch_build_records(a.plan, a.masks_out + g0, a.rec_off + g0, a.status ? a.status + g0 : nullptr, g0, gn,
+                                    a.k, a.r, s);
+      },
+      [&](uint64_t g0, uint64_t gn) { return run(plan_chunk(a, g0, gn), s); });
+}
+
 }  // namespace
 }  // namespace qfec

@@ -34,6 +34,9 @@ FEC_ERR_NODEV = -4
 FEC_ERR_NOMEM = -5
 FEC_ERR_AGAIN = -6
 FEC_ERR_UNRECOVERABLE = -7
+# fec_decode_plan_mode (Context.decode_plan_mode)
+FEC_PLAN_CODEBOOK = 0
+FEC_PLAN_DEVICE = 1
 
 # Every function the headers declare (tests check the library exports all of them).
 REFERENCE_SYMBOLS = (
@@ -56,7 +59,7 @@ HIP_SYMBOLS = (
     "fec_recover_batch_rs_dev_packed", "fec_coalesce_stats", "fec_coalesce_stats_sized",
     "fec_recover_gather_rs_dev", "fec_encode_gather_rs_dev",
     "fec_recover_gather_var_rs_dev", "fec_encode_gather_var_rs_dev",
-    "fec_recover_scatter_rs_dev", "fec_encode_scatter_rs_dev",
+    "fec_recover_scatter_rs_dev", "fec_encode_scatter_rs_dev", "fec_decode_plan_mode",
 )
 
 
@@ -125,6 +128,7 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
         "fec_copy_dev": (_int, [_vp, _vp, _vp, _u64, _vp]),
         "fec_synchronize": (_int, [_vp]),
         "fec_decode_loss_hint": (_int, [_vp, _dbl]),
+        "fec_decode_plan_mode": (_int, [_vp, _int]),
         "fec_group_new": (_vp, [ctypes.POINTER(_int), _int]),
         "fec_group_free": (None, [_vp]),
         "fec_group_size": (_int, [_vp]),
@@ -395,6 +399,12 @@ class Context:
         """Expected share of groups with lost data in device-resident decodes (< 0: unknown)."""
         _check(self.lib.fec_decode_loss_hint(self.handle, share), "fec_decode_loss_hint", self.lib)
 
+    def decode_plan_mode(self, mode: int) -> None:
+        """Where the device-resident calls take the records of a shape past the codebook cap from:
+        PLAN_CODEBOOK (default: host-built per call, synchronous; the table recovers refuse the
+        shape) or PLAN_DEVICE (built on the device per call: asynchronous, the table recovers serve it)."""
+        _check(self.lib.fec_decode_plan_mode(self.handle, mode), "fec_decode_plan_mode", self.lib)
+
     def synchronize(self) -> None:
         _check(self.lib.fec_synchronize(self.handle), "fec_synchronize", self.lib)
 
@@ -622,6 +632,9 @@ SCATTER_LAUNCH_FORMS = {23: "classify_scatter", 24: "recover_scatter"}
 # the scatter encode's kernel (csrc/fec_scatter_encode.hip; ScatterEncodeLaunchForm), again its own;
 # `first` = the pass owns the XOR row, `direct` = the length-table form
 SCATTER_ENCODE_LAUNCH_FORMS = {25: "encode_scatter"}
+# the record builder of the device plans (csrc/fec_plan.hip; PlanLaunchForm), again its own:
+# first_item / items = the plan chunk's first group and its groups, aux = the launch's first arena slot
+PLAN_LAUNCH_FORMS = {26: "build_records"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -650,7 +663,7 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
         rec = dict(zip(LAUNCH_FIELDS, (int(x) for x in row)))
         form = rec["form"]
         for names in (LAUNCH_FORMS, GATHER_LAUNCH_FORMS, GATHER_VAR_LAUNCH_FORMS, SCATTER_LAUNCH_FORMS,
-                      SCATTER_ENCODE_LAUNCH_FORMS):
+                      SCATTER_ENCODE_LAUNCH_FORMS, PLAN_LAUNCH_FORMS):
             if form in names:
                 rec["form"] = names[form]
         out.append(rec)
