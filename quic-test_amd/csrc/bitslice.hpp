@@ -91,11 +91,11 @@ struct PlanOf {
 
 // ---- compile-time loops ----
 template <class F, int... I>
-QFEC_HD inline void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+QFEC_HD void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
   (f(std::integral_constant<int, I>{}), ...);
 }
 template <int N, class F>
-QFEC_HD inline void static_for(F&& f) {
+QFEC_HD void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
@@ -105,14 +105,14 @@ QFEC_HD inline void static_for(F&& f) {
 // off-diagonal S x S blocks: row d's columns with bit S set <-> row d+S's columns with it
 // clear; each pair costs two shifts and two bit selects (v_bfi_b32 / v_bitop3_b32).
 template <int S>
-QFEC_HD inline void swap_bits(uint32_t& a, uint32_t& b, uint32_t lo) {
+QFEC_HD void swap_bits(uint32_t& a, uint32_t& b, uint32_t lo) {
   const uint32_t na = (a & lo) | ((b << S) & ~lo);
   const uint32_t nb = ((a >> S) & lo) | (b & ~lo);
   a = na;
   b = nb;
 }
 
-QFEC_HD inline void transpose8(uint32_t (&x)[8]) {
+QFEC_HD void transpose8(uint32_t (&x)[8]) {
   swap_bits<4>(x[0], x[4], 0x0F0F0F0Fu);
   swap_bits<4>(x[1], x[5], 0x0F0F0F0Fu);
   swap_bits<4>(x[2], x[6], 0x0F0F0F0Fu);
@@ -128,7 +128,7 @@ QFEC_HD inline void transpose8(uint32_t (&x)[8]) {
 }
 
 // a ^ b ^ c in one VALU operation (v_bitop3_b32 / v_xor3_b32 on the device)
-QFEC_HD inline uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+QFEC_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 #else
@@ -139,7 +139,7 @@ QFEC_HD inline uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 // Hides v's expression from the optimiser.  Without it the compiler re-associates every
 // row's XOR chain down to single planes (the chains share nothing any more, 2-3x the XORs)
 // and keeps every packet's planes live to the end.
-QFEC_HD inline uint32_t opaque(uint32_t v) {
+QFEC_HD uint32_t opaque(uint32_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
   __asm__("" : "+v"(v));
 #else
@@ -171,7 +171,7 @@ struct Combos {
 // with every packet held: 211 VGPRs, 2 waves per SIMD, and all of a CU's waves load and
 // compute in lockstep; MI355X measured 43% VALU issue and slower than the tables).
 template <int K, int R, int W, class Load>
-QFEC_HD inline void encode_stream(Load&& load, uint32_t (&out)[R][8]) {
+QFEC_HD void encode_stream(Load&& load, uint32_t (&out)[R][8]) {
   static_assert(W >= 1 && W <= K, "window");
   uint32_t buf[W][8];
   static_for<W>([&](auto jj) { load(decltype(jj)::value, buf[decltype(jj)::value]); });
@@ -219,7 +219,7 @@ QFEC_HD inline void encode_stream(Load&& load, uint32_t (&out)[R][8]) {
 
 // The same with every packet already in registers (x is left transposed).
 template <int K, int R>
-QFEC_HD inline void encode_chunk(uint32_t (&x)[K][8], uint32_t (&out)[R][8]) {
+QFEC_HD void encode_chunk(uint32_t (&x)[K][8], uint32_t (&out)[R][8]) {
   encode_stream<K, R, K>(
       [&](int j, uint32_t(&dst)[8]) {
         for (int d = 0; d < 8; ++d) dst[d] = x[j][d];

@@ -11,9 +11,9 @@
 #include <cstdint>
 
 #if defined(__HIPCC__)
-#define QFEC_HD __host__ __device__
+#define QFEC_HD __host__ __device__ __forceinline__
 #else
-#define QFEC_HD
+#define QFEC_HD inline
 #endif
 
 namespace qfec {
@@ -24,7 +24,7 @@ struct TabWords {
   uint32_t t2;          // c * (v << 6) for v = 0..3  (bits 6..7)
 };
 
-QFEC_HD inline TabWords tab_words(uint32_t c) {
+QFEC_HD TabWords tab_words(uint32_t c) {
   uint32_t p[8];
   p[0] = c & 0xFFu;
   for (int b = 1; b < 8; ++b) p[b] = ((p[b - 1] << 1) ^ ((p[b - 1] & 0x80u) ? 0x1Du : 0u)) & 0xFFu;

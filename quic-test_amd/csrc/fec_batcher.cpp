@@ -63,6 +63,7 @@
 #include <vector>
 
 #include "fec_hip.h"
+#include "fec_mask.hpp"  // mask_losses
 
 #define QFEC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -727,7 +728,7 @@ int take(FECBatcher* b, int64_t ticket, uint8_t* out, uint32_t out_stride, int* 
   const int rc = e.rc.load(std::memory_order_relaxed);
   const uint32_t n = e.len.load(std::memory_order_relaxed);
   const uint64_t m = e.mask.load(std::memory_order_relaxed);
-  const uint32_t nrows = b->decoder ? static_cast<uint32_t>(__builtin_popcountll(m & ((1ull << b->k) - 1))) : b->r;
+  const uint32_t nrows = b->decoder ? qfec::mask_losses(m, b->k, b->r).lost : b->r;
   bool stale = false;
   if (rc == FEC_OK && out) {
     if (out_stride < n) {

@@ -2,9 +2,11 @@
 // fec_gather.hip, fec_gather_var.hip, fec_scatter.hip; what only the three address-table units
 // share is fec_table.hpp's).  First the small pieces: the coefficient table entry,
 // byte-aligned packet loads and stores under a memory policy, the GF(2^8) product of a dword, the
-// selector split of a dword (SelN / sel_split), record bytes and the workgroup order.  Then the
+// selector split of a dword (SelN / sel_split), record bytes and the workgroup order; piece_load, a
+// lane's load of its 4 * NM + NT dwords in the fused walk (decode_fused, recover_runs).  Then the
 // record-addressed decode, stated once:
-//  * classify_mask: erasure mask -> codebook record and status (the classify rule);
+//  * classify_mask: erasure mask -> codebook record and status (the rule is fec_mask.hpp's; the
+//    mask-addressed kernels of fec_kernels.hip spell their own);
 //  * RecHead / rec_head: a record's header (row count, XOR flag, coefficient tables);
 //  * decode_piece: the rebuild of one lane's piece of every lost row.  The survivors' bases come
 //    from the record and the group's contiguous data / parity (RecordBases, the default), or
@@ -23,6 +25,7 @@
 
 #include "fec_forms.hpp"    // the POL bits (kNtLoad .. kStageRows), LevelMeta
 #include "fec_kernels.hpp"  // kRecNone, kRecBad
+#include "fec_mask.hpp"     // the rule of an erasure mask: losses, the pick, ranks and the record
 
 namespace qfec {
 namespace {
@@ -106,6 +109,27 @@ __device__ __forceinline__ void stw(uint8_t* p, const uint32_t (&v)[NW]) {
   }
 }
 
+// One lane's piece of a packet in the fused walk (decode_fused, recover_runs): NM 16-byte pieces at
+// i * 1024 + lane * 16, then NT 4-byte tail pieces at toff[t] (the kernel's: NM * 1024 + t * 256 +
+// lane * 4, shifted back to end at P), 4 * NM + NT dwords in all.
+template <int NM, int NT, int POL>
+__device__ __forceinline__ void piece_load(const uint8_t* base, uint32_t lane, const uint32_t (&toff)[NT > 0 ? NT : 1],
+                                           uint32_t (&v)[4 * NM + NT]) {
+#pragma unroll
+  for (int i = 0; i < NM; ++i) {
+    const u32x4 t = ld16<POL>(base + i * 1024u + lane * 16u);
+    v[4 * i] = t.x;
+    v[4 * i + 1] = t.y;
+    v[4 * i + 2] = t.z;
+    v[4 * i + 3] = t.w;
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    if constexpr ((POL & kNtLoad) != 0) v[4 * NM + t] = __builtin_nontemporal_load(reinterpret_cast<const u32u*>(base + toff[t]));
+    else v[4 * NM + t] = *reinterpret_cast<const u32u*>(base + toff[t]);
+  }
+}
+
 // Selector bytes for the three pieces of every byte of NW dwords.
 template <int NW>
 struct SelN {
@@ -122,10 +146,9 @@ __device__ __forceinline__ void sel_split(const uint32_t (&v)[NW], SelN<NW>& s) 
   }
 }
 
-// The classify rule: erasure mask (bit s set where shard s of the k data + r parity shards is
-// lost) -> codebook record (in 32-B units) and status.  Nothing lost: kRecNone.  More data
-// shards lost than parity rows alive: kRecBad, status 1.  Else the record of the colex ranks of
-// the erased data set and of the e lowest surviving parity rows (`binom`: rows of 65).
+// The classify rule (fec_mask.hpp) as the record-addressed kernels read it: erasure mask ->
+// codebook record (in 32-B units) and status.  Nothing lost: kRecNone.  Unrecoverable: kRecBad,
+// status 1.  Else the pick's record (`binom`: the C(n, t) table, rows of 65).
 struct Classified {
   uint32_t rec;
   uint8_t status;
@@ -133,36 +156,10 @@ struct Classified {
 
 __device__ __forceinline__ Classified classify_mask(uint64_t m, uint32_t k, uint32_t r,
                                                     const uint64_t* __restrict__ binom, const LevelMeta& meta) {
-  const uint64_t kmask = k >= 64 ? ~0ull : ((1ull << k) - 1);
-  const uint64_t rmask = r >= 64 ? ~0ull : ((1ull << r) - 1);
-  uint64_t dm = m & kmask;
-  const uint64_t pm = (k >= 64) ? 0 : ((m >> k) & rmask);
-  const uint32_t e = __popcll(dm);
-  uint32_t rec = kRecNone;
-  uint8_t st = 0;
-  if (e > 0) {
-    const uint32_t alive = r - __popcll(pm);
-    if (e > alive) {
-      rec = kRecBad;
-      st = 1;
-    } else {
-      uint64_t rank_e = 0, rank_r = 0;
-      for (uint32_t t = 0; dm; ++t) {
-        const uint32_t j = __ffsll(static_cast<unsigned long long>(dm)) - 1;
-        rank_e += binom[j * 65 + t + 1];
-        dm &= dm - 1;
-      }
-      uint64_t sp = ~pm & rmask;
-      for (uint32_t t = 0; t < e; ++t) {
-        const uint32_t i = __ffsll(static_cast<unsigned long long>(sp)) - 1;
-        rank_r += binom[i * 65 + t + 1];
-        sp &= sp - 1;
-      }
-      const uint64_t idx = rank_e * meta.count_r[e] + rank_r;
-      rec = static_cast<uint32_t>((meta.base[e] + idx * meta.stride[e]) >> 5);
-    }
-  }
-  return {rec, st};
+  const MaskLosses l = mask_losses(m, k, r);
+  if (l.lost == 0) return {kRecNone, 0};
+  if (l.unrecoverable) return {kRecBad, 1};
+  return {static_cast<uint32_t>(mask_record(m, k, r, l.lost, meta, ChooseTable{binom}) >> 5), 0};
 }
 
 // A record's header (gf256.hpp build_record): survivor ids from byte 0, erased ids from byte 64,

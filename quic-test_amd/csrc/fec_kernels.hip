@@ -10,7 +10,13 @@
 //    into rows 1..R-1 with v_perm_b32 table lookups (3 per dword per coefficient, tables
 //    in SGPRs via scalar loads), then stores R dwordx4.
 //  * classify: one lane per group, erasure mask -> codebook record and status byte
-//    (classify_mask, fec_device.hpp).
+//    (classify_mask, fec_device.hpp).  What a mask means -- losses, rows per group, the pick of
+//    survivors and rows, the ranks and the record -- is fec_mask.hpp's for the cold kernels here
+//    (classify, the rows_* prefix kernels), which call it.  The mask-addressed hot kernels
+//    (decode_fused's DIRECT / INLINE forms, recover_runs) do NOT: each keeps its own hand-written
+//    statement of the same rule, because every call into the header that was tried changed their
+//    instructions (profiles/mask_rule/VERDICT.md).  They share ChooseSmall, low_bits(K) and
+//    piece_load only, and only the GPU every-mask tests check their copies.
 //  * decode_wave<K,MAXE>: one wave per group, record-addressed; the piece rebuild
 //    (decode_piece) and the record header (RecHead) are fec_device.hpp's, shared with the
 //    address-table recover of fec_gather.hip.
@@ -32,7 +38,8 @@
 
 #include "bitslice.hpp"
 #include "coef_tables.hpp"
-#include "fec_device.hpp"  // Tab, ld16 / st16, gmul, ldw / stw, decode_block; classify_mask, RecHead, decode_piece
+#include "fec_device.hpp"  // Tab, ld16 / st16, gmul, ldw / stw, piece_load, decode_block; classify_mask, RecHead,
+                           // decode_piece; fec_mask.hpp: low_bits, ChooseSmall, mask_rows
 #include "fec_kernels.hpp"
 #include "fec_knobs.hpp"
 #include "fec_launch.hpp"  // launch limits, for_chunks, launch_record
@@ -358,13 +365,6 @@ __global__ __launch_bounds__(256) void classify(const uint64_t* __restrict__ mas
   if (status) status[g] = c.status;
 }
 
-// C(n, t) for t = 1..3 without the table (the mask-addressed decode ranks inline; its
-// shapes have r <= 3, so e <= 3).  n < t gives 0 like the table.
-__device__ __forceinline__ uint64_t choose_small(uint32_t n, uint32_t t) {
-  const uint64_t a = n, b = n - 1u, c = n - 2u;
-  return t == 1u ? a : t == 2u ? (a * b) >> 1 : (a * b * c) / 6u;
-}
-
 // Per-wave LDS slice of N coefficient entries (decode_fused with kLdsTabs; 4 waves per
 // workgroup).  Only instantiated by the kernels that use it.
 template <int N>
@@ -424,7 +424,10 @@ __device__ __forceinline__ void fused_group(uint64_t gw, uint64_t m, uint32_t la
                                             uint32_t m0, uint8_t* __restrict__ out, const RankMeta& rm,
                                             uint8_t* __restrict__ status) {
   constexpr int NW = 4 * NM + NT;  // dwords per lane and survivor
-  constexpr uint64_t kmask = (1ull << K) - 1;
+  // (the classify, the ranks and the pick below restate fec_mask.hpp's mask_losses, mask_record and
+  // mask_pick by hand: calling them, colex_rank alone, or low_bits(r) for the rows' mask, moves all
+  // 90 mask-addressed decode_fused instantiations.  Not checked on the CPU.)
+  constexpr uint64_t kmask = low_bits(K);
   uint64_t rec_byte_off;
   if constexpr (INLINE) {
     uint64_t dm = m & kmask;
@@ -436,12 +439,12 @@ __device__ __forceinline__ void fused_group(uint64_t gw, uint64_t m, uint32_t la
     if (ne == 0 || bad) return;
     uint64_t rank_e = 0, rank_r = 0;
     for (uint32_t t = 0; dm; ++t) {
-      rank_e += choose_small(static_cast<uint32_t>(__builtin_ctzll(dm)), t + 1u);
+      rank_e += ChooseSmall{}(static_cast<uint32_t>(__builtin_ctzll(dm)), t + 1u);
       dm &= dm - 1;
     }
     uint64_t sp = ~pm & rmask;
     for (uint32_t t = 0; t < ne; ++t) {
-      rank_r += choose_small(static_cast<uint32_t>(__builtin_ctzll(sp)), t + 1u);
+      rank_r += ChooseSmall{}(static_cast<uint32_t>(__builtin_ctzll(sp)), t + 1u);
       sp &= sp - 1;
     }
     rec_byte_off = rm.base[ne] + (rank_e * rm.count_r[ne] + rank_r) * rm.stride[ne];
@@ -460,7 +463,7 @@ __device__ __forceinline__ void fused_group(uint64_t gw, uint64_t m, uint32_t la
   if constexpr (DIRECT) {
     lost = m & kmask;
     e = static_cast<uint32_t>(__popcll(lost));
-    uint64_t alive = ~(m >> K) & ((r >= 64 ? 0ull : (1ull << r)) - 1);
+    uint64_t alive = ~(m >> K) & ((r >= 64 ? 0ull : (1ull << r)) - 1);  // low_bits(r)
     xor_only = e == 1 && (alive & 1u);
     uint64_t rsel = 0;
     for (uint32_t t = 0; t < e; ++t) {
@@ -477,28 +480,16 @@ __device__ __forceinline__ void fused_group(uint64_t gw, uint64_t m, uint32_t la
   const uint8_t* dg = data + gw * K * static_cast<uint64_t>(P);
   const uint8_t* pg = parity + gw * r * static_cast<uint64_t>(P);
   uint8_t* og = out + gw * K * static_cast<uint64_t>(P);
-  const uint32_t main_end = NM * 1024u;
   uint32_t toff[NT > 0 ? NT : 1];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    toff[t] = main_end + t * 256u + lane * 4u;
+    toff[t] = NM * 1024u + t * 256u + lane * 4u;
     if (toff[t] + 4u > P) toff[t] = P - 4u;
   }
-  auto load = [&](const uint8_t* base, uint32_t (&v)[NW]) {
-#pragma unroll
-    for (int i = 0; i < NM; ++i) {
-      const u32x4 t = ld16<POL>(base + i * 1024u + lane * 16u);
-      v[4 * i] = t.x;
-      v[4 * i + 1] = t.y;
-      v[4 * i + 2] = t.z;
-      v[4 * i + 3] = t.w;
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      if constexpr ((POL & kNtLoad) != 0) v[4 * NM + t] = __builtin_nontemporal_load(reinterpret_cast<const u32u*>(base + toff[t]));
-      else v[4 * NM + t] = *reinterpret_cast<const u32u*>(base + toff[t]);
-    }
-  };
+  // (the load is fec_device.hpp's piece_load, shared with runs_load; the same for the tail offsets
+  // or the store moves decode_fused<20,5,2115,0,2>, and for recover_runs' row stores 14 or 15 of its 36
+  // instantiations: those stay spelled out)
+  auto load = [&](const uint8_t* base, uint32_t (&v)[NW]) { piece_load<NM, NT, POL>(base, lane, toff, v); };
   auto store = [&](uint8_t* base, const uint32_t (&v)[NW]) {
 #pragma unroll
     for (int i = 0; i < NM; ++i) st16<POL>(base + i * 1024u + lane * 16u, u32x4{v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]});
@@ -711,69 +702,13 @@ __global__ __launch_bounds__(256) void decode_fused(const uint8_t* __restrict__ 
                                                     const uint64_t* __restrict__ masks, RankMeta rm,
                                                     uint8_t* __restrict__ status) {
   static_assert(!INLINE || (DIRECT && MAXE <= 3), "inline classify: mask-addressed forms with r <= 3");
-  static_assert(SCAN == 0 || (DIRECT && INLINE && (SCAN <= 64 || SCAN % 256 == 0)),
-                "scan: mask-addressed inline forms, <= 64 groups per wave or whole 256-group rows per block");
+  static_assert(SCAN == 0 || (DIRECT && INLINE && SCAN <= 64), "scan: mask-addressed inline forms, <= 64 groups per wave");
   extern __shared__ __attribute__((aligned(16))) uint8_t occupancy_lds[];  // see encode_v16
   if (never) occupancy_lds[threadIdx.x] = 0;
   const uint64_t wv = static_cast<uint64_t>(decode_block(swz)) * 4u +
                       static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
   const uint32_t lane = threadIdx.x & 63u;
-  if constexpr (SCAN > 64) {
-    // Segment form: the block's 4 waves check SCAN groups (one mask per thread and row of
-    // 256), write every status byte, compact the groups to rebuild into LDS in group order
-    // and share them out round robin, so every wave of the block gets the same number of
-    // groups (+-1) whatever the loss pattern; a block's groups sit within SCAN * (k + r)
-    // packets of each other.
-    constexpr int J = SCAN / 256;
-    __shared__ uint64_t seg_mask[SCAN];
-    __shared__ uint16_t seg_idx[SCAN];
-    __shared__ uint32_t seg_cnt[J * 4];
-    const uint64_t g0 = static_cast<uint64_t>(decode_block(swz)) * SCAN;
-    if (g0 >= groups) return;
-    const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
-    constexpr uint64_t kmask = (1ull << K) - 1;
-    uint64_t mv[J], bal[J];
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const uint64_t g = g0 + j * 256u + threadIdx.x;
-      bool need = false;
-      mv[j] = 0;
-      if (g < groups) {
-        mv[j] = masks[g];
-        const uint32_t ne = static_cast<uint32_t>(__popcll(mv[j] & kmask));
-        const bool bad = ne > r - static_cast<uint32_t>(__popcll((mv[j] >> K) & ((1ull << r) - 1)));
-        if (status != nullptr) status[g] = bad ? 1 : 0;
-        need = ne > 0 && !bad;
-      }
-      bal[j] = __ballot(need);
-      if (lane == 0) seg_cnt[j * 4 + wave] = static_cast<uint32_t>(__popcll(bal[j]));
-    }
-    __syncthreads();
-    uint32_t total = 0, off[J];
-#pragma unroll
-    for (int c = 0; c < J * 4; ++c) {
-      if (static_cast<uint32_t>(c % 4) == wave) off[c / 4] = total;
-      total += seg_cnt[c];
-    }
-    const uint64_t below = (1ull << lane) - 1;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      if ((bal[j] >> lane) & 1u) {
-        const uint32_t pos = off[j] + static_cast<uint32_t>(__popcll(bal[j] & below));
-        seg_mask[pos] = mv[j];
-        seg_idx[pos] = static_cast<uint16_t>(j * 256u + threadIdx.x);
-      }
-    }
-    __syncthreads();
-    for (uint32_t i = wave; i < total; i += 4u) {
-      const uint64_t mi = seg_mask[i];
-      const uint64_t m = (static_cast<uint64_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(mi >> 32))) << 32) |
-                         __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(mi));
-      const uint32_t gl = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(seg_idx[i]));
-      fused_group<K, MAXE, POL, NM, NT, DIRECT, INLINE>(g0 + gl, m, lane, data, parity, rec_off, codebook, P, r, m0,
-                                                        out, rm, nullptr);
-    }
-  } else if constexpr (SCAN == 0) {
+  if constexpr (SCAN == 0) {
     if (wv >= groups) return;
     const uint64_t m = DIRECT ? masks[wv] : 0;
     fused_group<K, MAXE, POL, NM, NT, DIRECT, INLINE>(wv, m, lane, data, parity, rec_off, codebook, P, r, m0, out, rm,
@@ -789,7 +724,8 @@ __global__ __launch_bounds__(256) void decode_fused(const uint8_t* __restrict__ 
     bool need = false;
     if (lane < static_cast<uint32_t>(SCAN) && g0 + lane < groups) {
       mv = masks[g0 + lane];
-      constexpr uint64_t kmask = (1ull << K) - 1;
+      // fec_mask.hpp's mask_losses / mask_rows, restated by hand as in fused_group
+      constexpr uint64_t kmask = low_bits(K);
       const uint32_t ne = static_cast<uint32_t>(__popcll(mv & kmask));
       const bool bad = ne > r - static_cast<uint32_t>(__popcll((mv >> K) & ((1ull << r) - 1)));
       if (status != nullptr) status[g0 + lane] = bad ? 1 : 0;
@@ -805,7 +741,6 @@ __global__ __launch_bounds__(256) void decode_fused(const uint8_t* __restrict__ 
                                                         out, rm, nullptr);
     }
   }
-
 }
 
 // ---------------------------------------------------------------------------------
@@ -836,11 +771,11 @@ constexpr uint64_t kRunAgg = 1ull << 32;
 constexpr uint64_t kRunIncl = 2ull << 32;
 constexpr uint32_t kRunEpochShift = 34;
 
-// One group's rebuild in two stages, so a wave can have the next group's survivor loads in flight
-// while it computes and stores this one (kRunPipe): runs_load issues the survivor loads and finds
-// the record, runs_compute forms the rows.  Same survivor choice, record and arithmetic as
-// fused_group's DIRECT + INLINE path (survivors: the surviving data shards ascending, then the e
-// lowest surviving parity rows; record from the colex ranks).
+// One group's rebuild of recover_runs, in two stages: runs_load issues the survivor loads and
+// finds the record, runs_compute forms the rows.  Same survivor choice, record and arithmetic as
+// fused_group's DIRECT + INLINE path (the rule of fec_mask.hpp).
+// (one function for both stages moves all 36 recover_runs instantiations, and so does colex_rank
+// or for_each_chosen in place of the loops below: two stages, the rule restated by hand)
 struct RunMeta {
   const Tab* tabs;
   uint32_t e;
@@ -852,8 +787,8 @@ __device__ __forceinline__ RunMeta runs_load(uint64_t g, uint64_t m, uint32_t la
                                              const uint8_t* __restrict__ parity, const uint8_t* __restrict__ codebook,
                                              const RankMeta& rm, uint32_t P, const uint32_t (&toff)[NT > 0 ? NT : 1],
                                              uint32_t (&x)[K][4 * NM + NT]) {
-  constexpr uint64_t kmask = (1ull << K) - 1;
-  constexpr uint64_t rmask = (1ull << R) - 1;
+  constexpr uint64_t kmask = low_bits(K);
+  constexpr uint64_t rmask = low_bits(R);
   const uint64_t lost = m & kmask;
   const uint32_t e = static_cast<uint32_t>(__popcll(lost));
   const uint64_t pm = (m >> K) & rmask;
@@ -861,13 +796,13 @@ __device__ __forceinline__ RunMeta runs_load(uint64_t g, uint64_t m, uint32_t la
   {
     uint64_t dm = lost;
     for (uint32_t t = 0; dm; ++t) {
-      rank_e += choose_small(static_cast<uint32_t>(__builtin_ctzll(dm)), t + 1u);
+      rank_e += ChooseSmall{}(static_cast<uint32_t>(__builtin_ctzll(dm)), t + 1u);
       dm &= dm - 1;
     }
     uint64_t sp = ~pm & rmask;
     for (uint32_t t = 0; t < e; ++t) {
       const uint32_t bit = static_cast<uint32_t>(__builtin_ctzll(sp));
-      rank_r += choose_small(bit, t + 1u);
+      rank_r += ChooseSmall{}(bit, t + 1u);
       rsel |= 1ull << bit;
       sp &= sp - 1;
     }
@@ -884,19 +819,7 @@ __device__ __forceinline__ RunMeta runs_load(uint64_t g, uint64_t m, uint32_t la
     const uint32_t sid = static_cast<uint32_t>(__builtin_ctzll(surv));
     surv &= surv - 1;
     const uint8_t* src = sid < K ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - K) * static_cast<uint64_t>(P);
-#pragma unroll
-    for (int i = 0; i < NM; ++i) {
-      const u32x4 t = ld16<POL>(src + i * 1024u + lane * 16u);
-      x[s][4 * i] = t.x;
-      x[s][4 * i + 1] = t.y;
-      x[s][4 * i + 2] = t.z;
-      x[s][4 * i + 3] = t.w;
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      if constexpr ((POL & kNtLoad) != 0) x[s][4 * NM + t] = __builtin_nontemporal_load(reinterpret_cast<const u32u*>(src + toff[t]));
-      else x[s][4 * NM + t] = *reinterpret_cast<const u32u*>(src + toff[t]);
-    }
+    piece_load<NM, NT, POL>(src, lane, toff, x[s]);
   }
   return mt;
 }
@@ -939,9 +862,6 @@ __device__ __forceinline__ void runs_compute(const RunMeta& mt, uint32_t (&x)[K]
   }
 }
 
-// recover_runs: the wave's groups one after another (default), or with the next group's survivor
-// loads issued before this group's arithmetic and stores (probe form).
-constexpr int kRunPipe = 16384;
 // recover_runs (probe form): the run image leaves by plain stores while rows past the image keep
 // the POL's store policy.
 constexpr int kRunImgPlain = 32768;
@@ -969,8 +889,8 @@ __global__ __launch_bounds__(64 * WAVES) void recover_runs(const uint8_t* __rest
   constexpr uint32_t kTile = TG;
   constexpr uint32_t kScanWaves = TG >= 64 ? TG / 64 : 1;
   constexpr int NW = 4 * NM + NT;
-  constexpr uint64_t kmask = (1ull << K) - 1;
-  constexpr uint64_t rmask = (1ull << R) - 1;
+  constexpr uint64_t kmask = low_bits(K);
+  constexpr uint64_t rmask = low_bits(R);
   extern __shared__ __attribute__((aligned(16))) uint8_t run_image[];
   __shared__ uint64_t s_mask[kTile];
   __shared__ uint32_t s_item[kTile];  // (local group << 16) | first row in the run
@@ -992,6 +912,7 @@ __global__ __launch_bounds__(64 * WAVES) void recover_runs(const uint8_t* __rest
   uint32_t rows = 0;
   if (tid < kTile && g < groups) {
     m = masks[g];
+    // fec_mask.hpp's mask_losses / mask_rows, restated by hand (called, they move every recover_runs)
     const uint32_t ne = static_cast<uint32_t>(__popcll(m & kmask));
     const bool bad = ne > R - static_cast<uint32_t>(__popcll((m >> K) & rmask));
     if (status != nullptr) status[g] = bad ? 1 : 0;
@@ -1091,44 +1012,14 @@ __global__ __launch_bounds__(64 * WAVES) void recover_runs(const uint8_t* __rest
     gi = static_cast<uint64_t>(tile) * kTile + (item >> 16);
     r0 = item & 0xFFFFu;
   };
-  constexpr bool kPipe = (POL & kRunPipe) != 0;
-  uint32_t xn[kPipe ? K : 1][kPipe ? NW : 1];  // kRunPipe: the next group's survivors, loads in flight
-  RunMeta mn{};
-  if constexpr (kPipe) {
-    if (wave < nwork) {
-      uint64_t gi, mw;
-      uint32_t r0;
-      item_of(wave, gi, mw, r0);
-      mn = runs_load<K, R, NM, NT, POL>(gi, mw, lane, data, parity, codebook, rm, P, toff, xn);
-    }
-  }
   for (uint32_t i = wave; i < nwork; i += WAVES) {
     uint64_t gi, mw;
     uint32_t r0;
     item_of(i, gi, mw, r0);
-    uint32_t acc[R][NW];
-    uint32_t e;
-    if constexpr (kPipe) {
-      uint32_t x[K][NW];
-#pragma unroll
-      for (int s2 = 0; s2 < K; ++s2)
-#pragma unroll
-        for (int q = 0; q < NW; ++q) x[s2][q] = xn[s2][q];
-      const RunMeta mt = mn;
-      if (i + WAVES < nwork) {
-        uint64_t gn, mwn;
-        uint32_t rn;
-        item_of(i + WAVES, gn, mwn, rn);
-        mn = runs_load<K, R, NM, NT, POL>(gn, mwn, lane, data, parity, codebook, rm, P, toff, xn);
-      }
-      runs_compute<K, R, NM, NT>(mt, x, acc);
-      e = mt.e;
-    } else {
-      uint32_t x[K][NW];
-      const RunMeta mt = runs_load<K, R, NM, NT, POL>(gi, mw, lane, data, parity, codebook, rm, P, toff, x);
-      runs_compute<K, R, NM, NT>(mt, x, acc);
-      e = mt.xor_only ? 1u : mt.e;
-    }
+    uint32_t acc[R][NW], x[K][NW];
+    const RunMeta mt = runs_load<K, R, NM, NT, POL>(gi, mw, lane, data, parity, codebook, rm, P, toff, x);
+    runs_compute<K, R, NM, NT>(mt, x, acc);
+    const uint32_t e = mt.xor_only ? 1u : mt.e;
     if (flags & 1u) continue;  // probe: reads and arithmetic only
 #pragma unroll
     for (int mm = 0; mm < R; ++mm) {
@@ -1186,13 +1077,6 @@ static_assert(kRowsPerThread == 4, "thread_rows and the rows_* kernels are writt
 constexpr uint32_t kRowsPerBlock = 256 * kRowsPerThread;
 constexpr uint32_t kRowsDirectBlocks = 4096;
 
-__device__ __forceinline__ uint32_t rebuilt_rows(uint64_t m, uint32_t k, uint32_t r) {
-  const uint64_t kmask = k >= 64 ? ~0ull : (1ull << k) - 1;
-  const uint32_t ne = static_cast<uint32_t>(__popcll(m & kmask));
-  const uint32_t pl = static_cast<uint32_t>(__popcll((m >> k) & ((1ull << r) - 1)));
-  return ne > 0 && ne + pl <= r ? ne : 0u;
-}
-
 // Inclusive scan of one value per thread over a 256-thread block (LDS, 8 steps).
 __device__ __forceinline__ uint32_t block_inclusive_scan(uint32_t v, uint32_t* lds) {
   const uint32_t t = threadIdx.x;
@@ -1224,12 +1108,12 @@ __device__ __forceinline__ void thread_rows(const uint64_t* __restrict__ masks, 
   if (g0 + kRowsPerThread <= groups) {
     typedef uint64_t u64x4 __attribute__((ext_vector_type(4), aligned(8)));  // masks may be 8-B aligned
     const u64x4 m = *reinterpret_cast<const u64x4*>(masks + g0);
-    rows[0] = rebuilt_rows(m.x, k, r);
-    rows[1] = rebuilt_rows(m.y, k, r);
-    rows[2] = rebuilt_rows(m.z, k, r);
-    rows[3] = rebuilt_rows(m.w, k, r);
+    rows[0] = mask_rows(m.x, k, r);
+    rows[1] = mask_rows(m.y, k, r);
+    rows[2] = mask_rows(m.z, k, r);
+    rows[3] = mask_rows(m.w, k, r);
   } else {
-    for (uint32_t i = 0; i < kRowsPerThread; ++i) rows[i] = g0 + i < groups ? rebuilt_rows(masks[g0 + i], k, r) : 0u;
+    for (uint32_t i = 0; i < kRowsPerThread; ++i) rows[i] = g0 + i < groups ? mask_rows(masks[g0 + i], k, r) : 0u;
   }
 }
 
@@ -2190,7 +2074,7 @@ hipError_t run_decode_wave(const DecodeLaunch& a, hipStream_t s) {
 
 template <int K, int MAXE, int POL, int NM, int NT, bool DIRECT = false, bool INLINE = DIRECT, int SCAN = 0>
 hipError_t run_decode_fused(const DecodeLaunch& a, hipStream_t s) {
-  constexpr uint64_t kGroupsPerBlock = SCAN > 64 ? SCAN : 4u * (SCAN > 0 ? SCAN : 1);
+  constexpr uint64_t kGroupsPerBlock = 4u * (SCAN > 0 ? SCAN : 1);
   const uint32_t passes = (a.r + MAXE - 1) / MAXE;
   const uint32_t smem = occupancy_cap_lds(a.waves_per_cu ? a.waves_per_cu : knob(TestKnob::kDecodeWaves, kDecodeWavesPerCU), 4);
   const RankMeta rm = rank_meta(a.meta);

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void build_records(const uint64_t* __restrict_
   const uint64_t m = static_cast<uint64_t>(mask_hi) << 32 | mask_lo;
   // the classify's verdict again, from the mask the record is built from: 1 <= e <= min(k, r) is
   // what keeps the build inside its scratch and its slot
-  const PlanLosses losses = plan_losses(m, k, r);
+  const MaskLosses losses = mask_losses(m, k, r);
   bool ok = losses.lost != 0 && !losses.unrecoverable;
   const uint64_t slot = slot0 + g;
   if (ok) {

@@ -1,6 +1,6 @@
 // fec_plan_build.hpp — one group's recovery record, built from its erasure mask and the r x k parity
 // matrix: the bytes gf256.hpp's build_record writes for the pattern (E, R), E = the lost data
-// shards, R = the e lowest surviving parity rows (the rule of classify_mask and build_sparse_plan).
+// shards, R = the e lowest surviving parity rows (the rule of fec_mask.hpp).
 // For the shapes whose codebook of every pattern is past its cap, where a record cannot be looked
 // up and is built per group instead (fec_plan.hip build_records, FEC_PLAN_DEVICE).
 //
@@ -22,7 +22,7 @@
 
 #include <cstdint>
 
-#include "fec_varlen.hpp"  // QFEC_HD
+#include "fec_mask.hpp"  // QFEC_HD; lost_data, alive_rows, low_bits, bit_count
 
 namespace qfec {
 
@@ -44,26 +44,6 @@ struct PlanScratch {
   uint8_t inv[kPlanMaxE * kPlanMaxE];  // its inverse
   uint8_t coef[kPlanMaxE * kPlanMaxE];  // the record's e x k coefficients: e * k <= 1024 as e <= min(k, 64 - k)
 };
-
-// The classify rule on a mask (fec_routes.hpp mask_losses, fec_device.hpp classify_mask): e lost
-// data shards need e surviving parity rows; bits above k + r are ignored.
-struct PlanLosses {
-  uint32_t lost;       // e
-  bool unrecoverable;  // e > 0 and fewer than e parity rows survive
-};
-QFEC_HD uint64_t plan_low_bits(uint32_t n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }
-QFEC_HD uint32_t plan_popcount(uint64_t x) {
-  x = x - ((x >> 1) & 0x5555555555555555ull);
-  x = (x & 0x3333333333333333ull) + ((x >> 2) & 0x3333333333333333ull);
-  x = (x + (x >> 4)) & 0x0F0F0F0F0F0F0F0Full;
-  return static_cast<uint32_t>((x * 0x0101010101010101ull) >> 56);
-}
-QFEC_HD PlanLosses plan_losses(uint64_t mask, uint32_t k, uint32_t r) {
-  const uint64_t dm = mask & plan_low_bits(k);
-  const uint64_t pm = k >= 64 ? 0 : (mask >> k) & plan_low_bits(r);
-  const uint32_t e = plan_popcount(dm), alive = r - plan_popcount(pm);
-  return {e, e > 0 && e > alive};
-}
 
 QFEC_HD uint32_t plan_gf_mul(uint32_t a, uint32_t b) {
   uint32_t p = 0;
@@ -107,24 +87,27 @@ QFEC_HD PlanHalf plan_entry_half(uint32_t c, uint32_t half) {
 }
 
 // Builds the record of `mask` at rec: plan_record_bytes(k, e) bytes, 16-B aligned, every one of
-// them written.  Needs plan_losses(mask, k, r) = {e >= 1, recoverable} and k + r <= 64; M is the
+// them written.  Needs mask_losses(mask, k, r) = {e >= 1, recoverable} and k + r <= 64; M is the
 // r x k parity matrix, row-major.  Returns false on a zero pivot (the record is then not valid).
 // Every lane gets the same answer.
 template <typename EACH>
 QFEC_HD bool plan_build_record(uint32_t k, uint32_t r, const uint8_t* M, uint64_t mask, PlanScratch& sc, uint8_t* rec,
                                EACH each) {
-  const uint64_t dm = mask & plan_low_bits(k);
-  const uint64_t alive = ~(k >= 64 ? 0 : mask >> k) & plan_low_bits(r);
-  const uint32_t e = plan_popcount(dm);
+  // the pick of fec_mask.hpp, one cell per shard: the erased set and the alive rows are its sets;
+  // row i is chosen when it is alive and fewer than e alive rows lie below it (mask_pick's rows,
+  // without its walk over them)
+  const uint64_t dm = lost_data(mask, k);
+  const uint64_t alive = alive_rows(mask, k, r);
+  const uint32_t e = bit_count(dm);
   // survivors: the data shards not lost, ascending, then k + R_t; E and R
   each([&](uint32_t lane, uint32_t lanes) {
     for (uint32_t j = lane; j < k; j += lanes) {
-      const uint32_t before = plan_popcount(dm & plan_low_bits(j));
+      const uint32_t before = bit_count(dm & low_bits(j));
       if ((dm >> j) & 1u) sc.erased[before] = static_cast<uint8_t>(j);
       else sc.surv[j - before] = static_cast<uint8_t>(j);
     }
     for (uint32_t i = lane; i < r; i += lanes) {
-      const uint32_t rank = plan_popcount(alive & plan_low_bits(i));
+      const uint32_t rank = bit_count(alive & low_bits(i));
       if (((alive >> i) & 1u) && rank < e) {
         sc.rows[rank] = static_cast<uint8_t>(i);
         sc.surv[k - e + rank] = static_cast<uint8_t>(k + i);

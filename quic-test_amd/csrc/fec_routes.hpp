@@ -1,6 +1,6 @@
 // fec_routes.hpp — which way a host-memory call (fec_encode_batch_rs, fec_decode_batch_rs, the
-// legacy fec_encode_batch) goes, and the host-side rules those ways share: the classify rule of an
-// erasure mask, the chunk size of the DMA pipeline, the window of a call's packet offsets.
+// legacy fec_encode_batch) goes, and the host-side rules those ways share: the chunk size of the
+// DMA pipeline, the window of a call's packet offsets (the rule of an erasure mask: fec_mask.hpp).
 // Host-only (no HIP include, no device code, no environment), so a plain C++ program can ask for
 // every combination (tests/csrc/routes_dump.cpp).  fec_shim.cpp classifies the pointers, reads the
 // limits' overrides, asks here and switches on the answer.
@@ -8,33 +8,13 @@
 
 #include <cstdint>
 
+#include "fec_mask.hpp"  // the rule of an erasure mask: mask_losses, lost_data / lost_parity, for_each_lost
+
 namespace qfec {
 
 // Where a caller's pointer lives: pageable host memory, page-locked host memory (kernels can
 // address it over PCIe), device memory.
 enum class Mem { kHost, kPinned, kDevice };
-
-// ---- the erasure mask of a group: bit j < k = data shard j lost, bit k + i = parity row i lost ----
-constexpr uint64_t low_bits(uint32_t n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }
-constexpr uint64_t lost_data(uint64_t m, uint32_t k) { return m & low_bits(k); }
-constexpr uint64_t lost_parity(uint64_t m, uint32_t k, uint32_t r) { return k >= 64 ? 0 : (m >> k) & low_bits(r); }
-
-// The classify rule as the host states it (the kernels': fec_device.hpp classify_mask): e lost data
-// shards need e surviving parity rows; bits above k + r are ignored.
-struct MaskLosses {
-  uint32_t lost;       // e: data shards to rebuild
-  bool unrecoverable;  // e > 0 and fewer than e parity rows survive (status 1, data untouched)
-};
-inline MaskLosses mask_losses(uint64_t m, uint32_t k, uint32_t r) {
-  const uint32_t e = static_cast<uint32_t>(__builtin_popcountll(lost_data(m, k)));
-  const uint32_t alive = r - static_cast<uint32_t>(__builtin_popcountll(lost_parity(m, k, r)));
-  return {e, e > 0 && e > alive};
-}
-// f(j) for every lost data shard j of mask m, ascending.
-template <class F>
-inline void for_each_lost(uint64_t m, uint32_t k, F&& f) {
-  for (uint64_t lost = lost_data(m, k); lost; lost &= lost - 1) f(static_cast<uint32_t>(__builtin_ctzll(lost)));
-}
 
 // ---- the limits ----
 // Host-resident calls up to a small-call limit (data + parity bytes) run zero-copy: the kernels

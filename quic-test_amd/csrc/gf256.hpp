@@ -19,7 +19,7 @@
 #include <utility>
 #include <vector>
 
-#include "fec_routes.hpp"
+#include "fec_mask.hpp"  // the rule of an erasure mask; colex_rank
 
 namespace qfec {
 
@@ -148,17 +148,19 @@ inline const Binom& binom() {
   return b;
 }
 
-// Colex rank of a sorted subset {c_0 < c_1 < ...}: sum_t C(c_t, t+1).
-inline uint64_t colex_rank(const uint32_t* c, uint32_t n) {
-  uint64_t r = 0;
-  for (uint32_t t = 0; t < n; ++t) r += binom().c[c[t]][t + 1];
-  return r;
+// C(n, t) for fec_mask.hpp's colex_rank and record_offset, from the table above.
+inline ChooseTable choose_binom() { return {&binom().c[0][0]}; }
+// The bit set of a sorted subset.
+inline uint64_t subset_bits(const uint32_t* c, uint32_t n) {
+  uint64_t set = 0;
+  for (uint32_t t = 0; t < n; ++t) set |= 1ull << c[t];
+  return set;
 }
 
 // ---------------------------------------------------------------------------------
 // Decode codebook.  One record per recoverable pattern (E, R): E = erased data shards
 // (|E| = e, 1 <= e <= r), R = the e lowest surviving parity rows used to rebuild them.
-// Pattern index inside level e = rank(E) * C(r, e) + rank(R).
+// Pattern index inside level e = rank(E) * C(r, e) + rank(R), colex ranks (fec_mask.hpp).
 //
 // Record (all offsets in bytes, records 32-byte aligned):
 //   [0, 64)    survivor shard ids, k bytes: surviving data shards ascending, then k+R_t
@@ -283,9 +285,9 @@ inline bool build_codebook(const CodebookLayout& L, const std::vector<uint8_t>& 
   for (uint32_t e = 1; e <= r && e <= k; ++e) {
     const uint64_t cr = binom().c[r][e];
     for_each_subset(k, e, [&](const uint32_t* E) {
-      const uint64_t rankE = colex_rank(E, e);
+      const uint64_t rankE = colex_rank(subset_bits(E, e), choose_binom());
       for_each_subset(r, e, [&](const uint32_t* R) {
-        const uint64_t idx = rankE * cr + colex_rank(R, e);
+        const uint64_t idx = rankE * cr + colex_rank(subset_bits(R, e), choose_binom());
         ok &= build_record(k, M, E, R, e, out.data() + L.level_base[e] + idx * L.level_stride[e], L.compact);
       });
     });
@@ -311,12 +313,8 @@ inline bool build_sparse_plan(uint32_t k, uint32_t r, const std::vector<uint8_t>
       status[g] = 1;
       continue;
     }
-    const uint64_t dm = lost_data(masks[g], k);
-    uint64_t rsel = 0, alive = ~lost_parity(masks[g], k, r) & low_bits(r);
-    for (uint32_t t = 0; t < e; ++t) {
-      rsel |= alive & (~alive + 1);  // lowest surviving parity row
-      alive &= alive - 1;
-    }
+    const MaskPick pick = mask_pick(masks[g], k, r);
+    const uint64_t dm = pick.erased, rsel = pick.rows;
     auto key = std::make_pair(dm, rsel);
     auto it = seen.find(key);
     if (it == seen.end()) {

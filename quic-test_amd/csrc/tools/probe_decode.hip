@@ -45,15 +45,9 @@ __global__ __launch_bounds__(256) void wr_layout(const uint8_t* __restrict__ dat
   const uint32_t lane = threadIdx.x & 63u;
   if (g >= groups) return;
   const uint64_t m = masks[g];
-  const uint64_t lost = m & 0x3FFu;
-  const uint32_t e = uint32_t(__popcll(lost));
-  if (e == 0 || e > R - uint32_t(__popcll((m >> K) & 7u))) return;
-  uint64_t alive = ~(m >> K) & 7u, rsel = 0;
-  for (uint32_t t = 0; t < e; ++t) {
-    rsel |= alive & (~alive + 1);
-    alive &= alive - 1;
-  }
-  uint64_t surv = (~lost & 0x3FFu) | (rsel << K);
+  const uint32_t e = mask_rows(m, K, R);
+  if (e == 0) return;
+  uint64_t surv = mask_pick(m, K, R).survivors;
   const uint8_t* dg = data + g * K * P;
   const uint8_t* pg = parity + g * R * P;
   uint32_t toff = 1024u + lane * 4u;
@@ -120,14 +114,13 @@ int main(int argc, char** argv) {
         m = 0;
         for (uint32_t j = 0; j < k + r; ++j)
           if (double(rng() >> 11) * 0x1.0p-53 < loss) m |= 1ull << j;
-      } while (uint32_t(__builtin_popcountll(m & ((1ull << k) - 1))) > r - uint32_t(__builtin_popcountll((m >> k) & ((1ull << r) - 1))));
+      } while (mask_losses(m, k, r).unrecoverable);
     } else {
-      while (uint32_t(__builtin_popcountll(m)) < ners) m |= 1ull << (rng() % (k + r));
+      while (bit_count(m) < ners) m |= 1ull << (rng() % (k + r));
     }
     hm[g] = m;
-    const uint32_t e = __builtin_popcountll(m & ((1ull << k) - 1));
-    const uint32_t alive = r - __builtin_popcountll((m >> k) & ((1ull << r) - 1));
-    if (e && e <= alive) alg += uint64_t(k + e) * P;
+    const uint32_t e = mask_rows(m, k, r);
+    if (e) alg += uint64_t(k + e) * P;
   }
   CK(hipMemcpy(masks, hm.data(), G * 8, hipMemcpyHostToDevice));
   CodebookLayout L;
@@ -273,7 +266,7 @@ int main(int argc, char** argv) {
     uint32_t acc = 0;
     for (uint64_t g = 0; g < G; ++g) {
       hpre[g] = acc;
-      acc += uint32_t(__builtin_popcountll(hm[g] & 0x3FFu));
+      acc += mask_losses(hm[g], k, r).lost;
     }
     uint32_t* dpre = nullptr;
     CK(hipMalloc(&dpre, G * 4));
@@ -297,7 +290,6 @@ int main(int argc, char** argv) {
                   }});
   if (k == 10 && r == 3 && P == 1200) {
     PSCAN(2) PSCAN(4) PSCAN(8) PSCAN(16) PSCAN(32) PSCAN(64)
-    PSCAN(256) PSCAN(512) PSCAN(1024)
     vars.push_back({"scan8 compact-out", kDecodeFused, -1, 1, {}, [cout](const DecodeLaunch& a) {
                       DecodeLaunch b = a;
                       b.out = cout;

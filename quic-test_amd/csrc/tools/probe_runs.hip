@@ -89,12 +89,11 @@ int main(int argc, char** argv) {
       for (uint32_t j = 0; j < k + r; ++j)
         if (double(rng() >> 11) * 0x1.0p-53 < loss) m |= 1ull << j;
     } else {
-      while (__builtin_popcountll(m) < 2) m |= 1ull << (rng() % (k + r));
+      while (bit_count(m) < 2) m |= 1ull << (rng() % (k + r));
     }
     hm[g] = m;
-    const uint32_t e = __builtin_popcountll(m & ((1ull << k) - 1));
-    const uint32_t alive = r - __builtin_popcountll((m >> k) & ((1ull << r) - 1));
-    if (e && e <= alive) {
+    const uint32_t e = mask_rows(m, k, r);
+    if (e) {
       alg += uint64_t(k + e) * P;
       rows_total += e;
     }
@@ -240,23 +239,19 @@ int main(int argc, char** argv) {
       RF("runs w8 tg16 nl+ns st58K" + at, NL | NS, 8, 16, 57600, 0, chk, outs[i])
       RF("runs w4 tg8 nl+ns st29K" + at, NL | NS, 4, 8, 28800, 0, chk, outs[i])
       RF("runs w8 tg8 nostore" + at, NL, 8, 8, 28800, 1, false, outs[i])
-      // several groups per wave, the next group's loads in flight during this one's rows (kRunPipe)
+      // several groups per wave
       RF("runs w4 tg16 nl+ns st58K" + at, NL | NS, 4, 16, 59392, 0, chk, outs[i])
-      RF("runs w4 tg16 pipe nl+ns st58K" + at, NL | NS | kRunPipe, 4, 16, 59392, 0, chk, outs[i])
-      RF("runs w8 tg32 pipe nl+ns st60K" + at, NL | NS | kRunPipe, 8, 32, 61440, 0, chk, outs[i])
     }
     if (loss > 0) {
       RF("runs w8 nl+ns st32K" + at, NL | NS, 8, 512, 32768, 0, chk, outs[i])
       RF("runs w4 nl+ns st24K" + at, NL | NS, 4, 256, 24576, 0, chk, outs[i])
       RF("runs w4 nl st24K" + at, NL, 4, 256, 24576, 0, chk, outs[i])
       RF("runs w8 nostore" + at, NL, 8, 512, 0, 1, false, outs[i])
-      RF("runs w8 pipe nl+ns st48K" + at, NL | NS | kRunPipe, 8, 512, 49152, 0, chk, outs[i])
       // the store policy by path: the run image's copy-out plain, rows past it nt; a larger image
       RF("runs w8 nl+ns img-plain st48K" + at, NL | NS | kRunImgPlain, 8, 512, 49152, 0, chk, outs[i])
       RF("runs w8 nl+ns st64K" + at, NL | NS, 8, 512, 65536, 0, chk, outs[i])
       RF("runs w8 nl st64K" + at, NL, 8, 512, 65536, 0, chk, outs[i])
       RF("runs w8 nl+ns img-plain st64K" + at, NL | NS | kRunImgPlain, 8, 512, 65536, 0, chk, outs[i])
-      RF("runs w4 tg256 pipe nl+ns st24K" + at, NL | NS | kRunPipe, 4, 256, 24576, 0, chk, outs[i])
     }
   }
   // reference output: the two-step packed recover

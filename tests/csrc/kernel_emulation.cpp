@@ -146,14 +146,11 @@ int main() {
       if (gmul(w, e) != uint32_t(qfec::gf().mul(uint8_t(c), uint8_t(x))) * 0x01010101u) return fail("gmul", c, x, 0);
     }
   }
-  // decode_fused<..., INLINE>: choose_small (fec_kernels.hip, the inline classify's C(n, t)
-  // for t <= 3, same unsigned wrap-around for n < t) against the binomial table classify reads
+  // ChooseSmall (fec_mask.hpp: the C(n, t) of the mask-addressed kernels' inline ranks, t <= 3,
+  // unsigned wrap-around for n < t) against the binomial table classify reads
   for (uint32_t n = 0; n < 64; ++n)
-    for (uint32_t t = 1; t <= 3; ++t) {
-      const uint64_t a = n, b = n - 1u, c = n - 2u;
-      const uint64_t v = t == 1u ? a : t == 2u ? (a * b) >> 1 : (a * b * c) / 6u;
-      if (v != qfec::binom().c[n][t]) return fail("choose_small", int(n), int(t), 0);
-    }
+    for (uint32_t t = 1; t <= 3; ++t)
+      if (qfec::ChooseSmall{}(n, t) != qfec::binom().c[n][t]) return fail("choose_small", int(n), int(t), 0);
   // encode_bits (bitslice.hpp): the compiled-in matrix is gf256.hpp's, the transpose is an
   // involution, and 32-byte chunks of the bit-sliced encode equal the oracle's parity.
   if (bitslice_check<20, 5>(rng) || bitslice_check<10, 3>(rng) || bitslice_check<10, 2>(rng) ||

@@ -1,7 +1,8 @@
 // plan_build_test.cpp — the device-plan record builder (csrc/fec_plan_build.hpp) against the host's
 // build_record (csrc/gf256.hpp), with no GPU.
 //
-// For every mask tried, plan_losses is compared with mask_losses (fec_routes.hpp); for a
+// For every mask tried, the shared mask_losses (fec_mask.hpp: what build_records asks before it
+// builds) is compared with a count of the mask's bits, one by one; for a
 // recoverable mask with e >= 1 lost data shards, plan_build_record runs with all 64 lanes (each
 // step lane after lane) into a heap block of exactly record_bytes(k, e) bytes, filled 0xEE before,
 // and the block is compared by memcmp with the record build_record writes for E = the lost data
@@ -54,10 +55,14 @@ uint64_t random_bits(uint32_t n, uint32_t width) {
 }
 
 bool check(uint32_t k, uint32_t r, const std::vector<uint8_t>& M, uint64_t mask) {
-  const MaskLosses want = mask_losses(mask, k, r);
-  const PlanLosses got = plan_losses(mask, k, r);
+  MaskLosses want{0, false};  // bit by bit
+  uint32_t rows_alive = 0;
+  for (uint32_t j = 0; j < k; ++j) want.lost += static_cast<uint32_t>((mask >> j) & 1u);
+  for (uint32_t i = 0; i < r; ++i) rows_alive += static_cast<uint32_t>(~(mask >> (k + i)) & 1u);
+  want.unrecoverable = want.lost > rows_alive;
+  const MaskLosses got = mask_losses(mask, k, r);
   if (got.lost != want.lost || got.unrecoverable != want.unrecoverable) {
-    std::fprintf(stderr, "k=%u r=%u mask=%llx: plan_losses {%u, %d}, mask_losses {%u, %d}\n", k, r,
+    std::fprintf(stderr, "k=%u r=%u mask=%llx: mask_losses {%u, %d}, bit by bit {%u, %d}\n", k, r,
                  static_cast<unsigned long long>(mask), got.lost, got.unrecoverable, want.lost, want.unrecoverable);
     return false;
   }

@@ -32,7 +32,7 @@ def work_dir(tmp_path_factory):
 # ------------------------------------------------------------------------------------------
 def test_records_equal_build_record_plain_and_under_sanitizers(work_dir):
     """Every pattern of (4,2), (5,5), (10,3) and 2,000 drawn masks of each of eight large shapes:
-    plan_losses equals mask_losses, and the record the 64 lanes write into a heap block of exactly
+    mask_losses equals a bit-by-bit count, and the record the 64 lanes write into a heap block of exactly
     record_bytes(k, e) bytes equals build_record's.  Once plain, once with AddressSanitizer and
     UBSan linked in statically: no report and the same counts -- no byte outside a record is
     touched.  Every kind of mask the builder has a case for was met."""
