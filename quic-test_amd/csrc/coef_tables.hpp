@@ -1,6 +1,6 @@
 // coef_tables.hpp — the v_perm_b32 lookup tables of one GF(2^8) coefficient, computed from
 // the coefficient alone.  Used by the kernels that receive bare coefficient bytes
-// (fec_kernels.hip, kCoefBytes) and checked on the CPU against gf256.hpp's make_entry
+// (fec_decode_fused.hip, kCoefBytes) and checked on the CPU against gf256.hpp's make_entry
 // (tests/csrc/kernel_emulation.cpp).
 //
 // x -> c*x is linear over GF(2), so c*v for a 3-bit (or 2-bit) piece v of x is the XOR of

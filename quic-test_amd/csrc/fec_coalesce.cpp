@@ -32,7 +32,7 @@
 // 16).  A launch per batch costs the leader ~6-9 us of HIP API time and ~12 us until it sees
 // the completion (profiles/r03_legacy_v3_tuning.jsonl), so batching alone only matches the
 // per-context path.  Instead workgroups stay resident on each device and serve a ring of
-// submission slots in page-locked coherent host memory (fec_kernels.hpp ServerSlot,
+// submission slots in page-locked coherent host memory (fec_server.hpp ServerSlot,
 // legacy_server): a caller takes a sequence number, writes its packets' device addresses and
 // its repair rows' address into slot seq % kServerSlots, every word tagged with the slot's lap,
 // and polls the slot's done word; a workgroup takes every complete slot of its class in order
@@ -528,7 +528,7 @@ class Resident {
     // Test switches (libfec_hip_test.so only; fec_knobs.hpp):
     // an instance that never serves (relaunch records a launch without launching);
     r->no_launch = test_knob(TestKnob::kResidentNoLaunch, 0) != 0;
-    // a short tag epoch (fec_kernels.hpp server_tag), so the scrubs at its boundaries run within
+    // a short tag epoch (fec_server.hpp server_tag), so the scrubs at its boundaries run within
     // a few thousand calls;
     const long ep = std::min<long>(kServerEpoch, std::max(1L, test_knob(TestKnob::kResidentEpoch, kServerEpoch)));
     r->epoch = 1u;
@@ -548,7 +548,7 @@ class Resident {
     // no word of a slot that was never written carries a tag (tags are 1 .. epoch; alloc_coherent zeroed it)
     std::memset(r->ring.host, 0, sizeof(ServerSlot) * kServerSlots);
     if (env_long("QUICFEC_RESIDENT_VRAM", 1) != 0) r->setup_vram();
-    // Serving classes (fec_kernels.hpp kServerMaxClasses): QUICFEC_RESIDENT_SERVERS workgroups
+    // Serving classes (fec_server.hpp kServerMaxClasses): QUICFEC_RESIDENT_SERVERS workgroups
     // (default 8 with the VRAM ring; 1 with the page-locked ring, whose every poll is a PCIe round
     // trip), a power of two up to 8 (rounded down); more than one share a few words of uncached
     // device memory, and without them the instance is one workgroup.  Same box,
@@ -652,7 +652,7 @@ class Resident {
                                           : outs.dev + size_t(si) * kResidentOutBytes;
     // The first lap of a tag epoch: no chunk the server wrote into this slot's output staging in
     // the previous epoch may carry a tag of this one (the server zeroed the slot's own words and
-    // data area after serving its last lap; fec_kernels.hpp server_tag).  The previous occupant's
+    // data area after serving its last lap; fec_server.hpp server_tag).  The previous occupant's
     // rows were all collected, so the device writes nothing here until this slot is published.
     if (vinl && seq >= kServerSlots && server_tag(seq, epoch) == 1u) {
       std::memset(iouts.host + size_t(si) * kInlineOutBytes, 0, kInlineOutBytes);
@@ -911,7 +911,7 @@ class Resident {
   }
 
   // One 8-B half of an inline chunk: payload bytes [off, off + 6) of a packet of P bytes (zero
-  // past P) and the tag in the top two bytes (fec_kernels.hpp kServerInline).
+  // past P) and the tag in the top two bytes (fec_server.hpp kServerInline).
   static uint64_t chunk_half(const uint8_t* src, uint32_t P, uint32_t off, uint32_t tag16) {
     uint64_t w = 0;
     if (off + 8 <= P) {
@@ -925,7 +925,7 @@ class Resident {
 
   static void store_half(uint8_t* p, uint64_t w) { *reinterpret_cast<volatile uint64_t*>(p) = w; }
 
-  // An inline slot's packets into its data area through the BAR (fec_kernels.hpp kServerInline):
+  // An inline slot's packets into its data area through the BAR (fec_server.hpp kServerInline):
   // packet p = g * 10 + j as nch 16-B chunks, each two 8-B halves of 6 payload bytes and the tag;
   // each chunk one 16-B store (write-combined).  torn (test switch kResidentTear): that
   // chunk gets only its high half here; the caller stores the low half after the header.

@@ -1,12 +1,15 @@
-// fec_device.hpp — the device code shared by the kernel translation units (fec_kernels.hip,
-// fec_gather.hip, fec_gather_var.hip, fec_scatter.hip; what only the three address-table units
-// share is fec_table.hpp's).  First the small pieces: the coefficient table entry,
+// fec_device.hpp — the device code shared by the kernel translation units (fec_encode.hip,
+// fec_decode.hip, fec_decode_fused.hip, fec_runs.hip, fec_gather.hip, fec_gather_var.hip,
+// fec_scatter.hip; what only the address-table units share is fec_table.hpp's).  First the small
+// pieces: the coefficient table entry,
 // byte-aligned packet loads and stores under a memory policy, the GF(2^8) product of a dword, the
 // selector split of a dword (SelN / sel_split), record bytes and the workgroup order; piece_load, a
-// lane's load of its 4 * NM + NT dwords in the fused walk (decode_fused, recover_runs).  Then the
+// lane's load of its 4 * NM + NT dwords in the fused walk (decode_fused, recover_runs); the
+// 16-byte-column pieces of the encodes and the column decodes (Sel, prep, mac, xor_into, gmul_byte,
+// col_off16); RankMeta, the codebook levels the mask-addressed kernels rank in.  Then the
 // record-addressed decode, stated once:
 //  * classify_mask: erasure mask -> codebook record and status (the rule is fec_mask.hpp's; the
-//    mask-addressed kernels of fec_kernels.hip spell their own);
+//    mask-addressed kernels of fec_decode_fused.hip and fec_runs.hip spell their own);
 //  * RecHead / rec_head: a record's header (row count, XOR flag, coefficient tables);
 //  * decode_piece: the rebuild of one lane's piece of every lost row.  The survivors' bases come
 //    from the record and the group's contiguous data / parity (RecordBases, the default), or
@@ -145,6 +148,41 @@ __device__ __forceinline__ void sel_split(const uint32_t (&v)[NW], SelN<NW>& s) 
     s.s2[q] = (v[q] >> 6) & 0x03030303u;
   }
 }
+
+// Selector bytes of a 16-byte column: the encodes (fec_encode.hip) and the column decodes
+// (fec_decode.hip decode_v16, decode_tiled).
+using Sel = SelN<4>;
+
+__device__ __forceinline__ void prep(const u32x4& x, Sel& s) {
+  const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+  sel_split(w, s);
+}
+
+__device__ __forceinline__ void mac(u32x4& acc, const Sel& s, const Tab& t) {
+  acc.x ^= gmul(s.s0[0], s.s1[0], s.s2[0], t);
+  acc.y ^= gmul(s.s0[1], s.s1[1], s.s2[1], t);
+  acc.z ^= gmul(s.s0[2], s.s1[2], s.s2[2], t);
+  acc.w ^= gmul(s.s0[3], s.s1[3], s.s2[3], t);
+}
+
+__device__ __forceinline__ void xor_into(u32x4& acc, const u32x4& x) { acc ^= x; }
+
+__device__ __forceinline__ uint8_t gmul_byte(uint32_t x, const Tab& t) {
+  return static_cast<uint8_t>(gmul(x & 7u, (x >> 3) & 7u, (x >> 6) & 3u, t));
+}
+
+// Byte offset of 16-byte column `col` inside a packet of P >= 16 bytes: the last column
+// is shifted back to end at P (fec_encode.hip header).
+__device__ __forceinline__ uint32_t col_off16(uint32_t col, uint32_t P) {
+  const uint32_t o = col * 16u;
+  return o + 16u <= P ? o : P - 16u;
+}
+
+// Codebook levels e = 1..3 for the inline classify of the mask-addressed kernels (decode_fused,
+// recover_runs take it by value; fec_launch.hpp rank_meta fills it).
+struct RankMeta {
+  uint64_t base[4], stride[4], count_r[4];
+};
 
 // The classify rule (fec_mask.hpp) as the record-addressed kernels read it: erasure mask ->
 // codebook record (in 32-B units) and status.  Nothing lost: kRecNone.  Unrecoverable: kRecBad,

@@ -1,8 +1,9 @@
 // fec_forms.hpp — which kernel form a call runs: the launch descriptions, the lists of compiled
 // shapes and the rules that choose among them.  Host-only (no HIP include, no device code), so a
 // plain C++ program can ask for every packet size (tests/csrc/forms_dump.cpp; for the address-table
-// calls tests/csrc/table_forms_dump.cpp).  The launchers of fec_kernels.hip and of the
-// address-table units dispatch on what is decided here and expand the same lists.
+// calls tests/csrc/table_forms_dump.cpp).  The launchers of the kernel translation units
+// (fec_encode.hip, fec_decode.hip, fec_decode_fused.hip, fec_runs.hip; the address-table units)
+// dispatch on what is decided here and expand the same lists.
 #pragma once
 
 #include <cstdint>
@@ -17,7 +18,7 @@ namespace qfec {
 enum class OffsetKind : int { kNone = 0, kU32 = 1, kU64 = 2, kAddr = 3 };
 
 // Packets of any size P >= 16 at any byte address run on the 16-byte-column kernels
-// (fec_kernels.hip header); shorter ones on the byte kernels.
+// (fec_encode.hip header); shorter ones on the byte kernels.
 struct EncodeLaunch {
   const uint8_t* data;       // base of the data shards (device address)
   const void* offsets;       // device u32/u64 offsets (k per group) or nullptr
@@ -99,7 +100,7 @@ constexpr uint32_t kDecodeScanGroups = 8;
 // Share of groups needing a rebuild below which the host paths use the scan form.
 constexpr double kDecodeScanMaxShare = 0.25;
 
-// Packed recover in one launch (recover_runs, fec_kernels.hip): every workgroup owns 512
+// Packed recover in one launch (recover_runs, fec_runs.hip): every workgroup owns 512
 // consecutive groups, finds its run's first row by decoupled look-back (no prefix launches)
 // and writes its rebuilt rows as one contiguous run, staged through an LDS image of up to
 // stage bytes.  Mask-addressed shapes only (runs_supported).
@@ -128,7 +129,7 @@ struct RunsLaunch {
 // `last` (0: none since the workspace was zeroed): first .. first + n - 1, each non-zero and
 // below `limit`, none handed out twice while the workspace's words live.  When they would reach
 // the limit the workspace must be zeroed first (`rezero`) and the count starts again at 1.
-// Needs n < limit.  The epoch is the 30 bits above bit 34 of a look-back word (fec_kernels.hip
+// Needs n < limit.  The epoch is the 30 bits above bit 34 of a look-back word (fec_runs.hip
 // kRunEpochShift), so the limit is 2^30 (the test library's TestKnob::kRunsEpochLimit lowers it).
 constexpr uint32_t kRunsEpochLimit = 1u << 30;
 struct RunsEpochs {
@@ -262,17 +263,22 @@ static_assert(has_layout(16) && has_layout(2047) && !has_layout(15) && !has_layo
 #define QFEC_SCAN_LAYOUTS(X, K, R) QFEC_LAYOUTS(QFEC_FORM_SCAN, X, K, R)
 #define QFEC_LDS_LAYOUTS(X, K, R) QFEC_LAYOUTS(QFEC_FORM_LDS, X, K, R)
 #define QFEC_RUNS_LAYOUTS(X, K, R) QFEC_LAYOUTS(QFEC_FORM_RUNS, X, K, R)
-#define QFEC_DECODE_FORMS(X)                                                                      \
+// Two lists, one per translation unit: decode_fused's forms (fec_decode_fused.hip) and the others
+// (fec_decode.hip); each unit expands its own, QFEC_DECODE_FORMS is both.
+#define QFEC_DECODE_FUSED_FORMS(X)                                                                \
   QFEC_MASK_SHAPES(QFEC_MASK_LAYOUTS, X) QFEC_SCAN_SHAPES(QFEC_SCAN_LAYOUTS, X)                   \
-  QFEC_LDS_SHAPES(QFEC_LDS_LAYOUTS, X) QFEC_RECORD_FORMS(QFEC_FORM_RECORD, X)                     \
+  QFEC_LDS_SHAPES(QFEC_LDS_LAYOUTS, X) QFEC_RECORD_FORMS(QFEC_FORM_RECORD, X)
+#define QFEC_DECODE_OTHER_FORMS(X)                                                                \
   QFEC_TILED_SHAPES(QFEC_FORM_TILED, X) QFEC_WAVE_SHAPES(QFEC_FORM_WAVE, X)                       \
   X(kWave, 0, 8, 0, 0, kNtStore | kNoCoefBranch, false, 0)                                        \
   X(kWave, 0, 8, 0, 0, kNtStore | kNoCoefBranch | kCompactOut, false, 0)                          \
   X(kBytes, 0, 0, 0, 0, 0, false, 0) X(kBytes, 0, 0, 0, 0, kCompactOut, false, 0)
+#define QFEC_DECODE_FORMS(X) QFEC_DECODE_FUSED_FORMS(X) QFEC_DECODE_OTHER_FORMS(X)
 #define QFEC_RUNS_FORMS(X) QFEC_MASK_SHAPES(QFEC_RUNS_LAYOUTS, X)
 #define QFEC_FORM_TILED_PLAIN(X, K, R) X(kTiled, K, R, 0, 0, 0, false, 0)
 #define QFEC_FORM_WAVE_PLAIN(X, K, R) X(kWave, K, R, 0, 0, 0, false, 0) X(kV16, K, R, 0, 0, 0, false, 0)
 #define QFEC_FORM_WAVE_NB(X, K, R) X(kWave, K, R, 0, 0, kNtStore | kNoCoefBranch, false, 0)
+// (no decode_fused form among them: the probes launch theirs by hand, so the list is fec_decode.hip's)
 #define QFEC_PROBE_DECODE_FORMS(X)                                                                \
   QFEC_TILED_SHAPES(QFEC_FORM_TILED_PLAIN, X) QFEC_WAVE_SHAPES(QFEC_FORM_WAVE_PLAIN, X)           \
   QFEC_WAVE_NB_SHAPES(QFEC_FORM_WAVE_NB, X) X(kWave, 0, 8, 0, 0, 0, false, 0) X(kV16, 0, 8, 0, 0, 0, false, 0)

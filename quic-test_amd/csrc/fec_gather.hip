@@ -5,7 +5,7 @@
 //
 //  * classify_table<Lens::kNone> (fec_table.hpp; the launch trace's classify_gather): forms each
 //    group's erasure mask from its table entries (bit s set where entry s is 0); the status byte
-//    and the codebook record come from classify_mask, the rule `classify` (fec_kernels.hip)
+//    and the codebook record come from classify_mask, the rule `classify` (fec_decode.hip)
 //    applies to a given mask.
 //  * recover_gather<K, MAXE, POL>: one wave per group, record-addressed like decode_wave.  The
 //    base address of the record's survivor s is the group's table entry of that shard id, fetched
@@ -16,7 +16,7 @@
 // scan and the table-entry pointer fec_table.hpp's; this file holds only what the address table
 // adds to the recover.
 //
-// Shards may have any byte alignment (unaligned 16-B / 4-B global access, as in fec_kernels.hip)
+// Shards may have any byte alignment (unaligned 16-B / 4-B global access, as in fec_encode.hip and fec_decode.hip)
 // and P >= 16.  A lost shard's entry and a parity row the decode rule does not use are never
 // dereferenced: the record lists only the k survivors it rebuilds from.
 #include <hip/hip_runtime.h>

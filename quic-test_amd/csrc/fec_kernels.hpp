@@ -1,13 +1,16 @@
 // fec_kernels.hpp — launch interface between the C-ABI shim (fec_shim.cpp) and the
-// gfx950 kernels (fec_kernels.hip; the address-table units fec_gather.hip, fec_gather_var.hip,
-// fec_scatter.hip, fec_scatter_encode.hip with their shared fec_table.hpp).  Internal to libfec_hip.so.
+// gfx950 kernels, one translation unit per kernel family: fec_encode.hip, fec_decode.hip,
+// fec_decode_fused.hip, fec_runs.hip, fec_server.hip, fec_util.hip; the address-table units
+// fec_gather.hip, fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip with their shared
+// fec_table.hpp; fec_plan.hip.  Internal to libfec_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "fec_forms.hpp"  // launch descriptions and the choice of kernel form
+#include "fec_forms.hpp"   // launch descriptions and the choice of kernel form
+#include "fec_server.hpp"  // the resident encoder's ring protocol
 
 namespace qfec {
 
@@ -33,11 +36,17 @@ inline uint32_t occupancy_cap_lds(int waves_per_cu, uint32_t waves_per_block) {
   return 160u * 1024u / (blocks + 1) + 16u;
 }
 
-constexpr int kDecodeFusedXcdSwizzle = 1;  // tuned per kernel (fec_kernels.hip decode_swizzle)
+constexpr int kDecodeFusedXcdSwizzle = 1;  // tuned per kernel (fec_launch.hpp decode_swizzle)
 constexpr int kDecodeWaveXcdSwizzle = 1;
 
+// The contiguous encodes (fec_encode.hip).
 hipError_t launch_encode(const EncodeLaunch& a, hipStream_t s);
+// The record- and mask-addressed decodes (fec_decode.hip): the plan-chunk walk, the checks, the
+// classify launch and the dispatch of decode_form's choice.  Its decode_fused forms are a unit of
+// their own (fec_decode_fused.hip), entered through launch_decode_fused with the form launch_decode
+// chose (f.kernel == DecodeKernel::kFused); nothing else calls it.
 hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s);
+hipError_t launch_decode_fused(const DecodeLaunch& a, const DecodeForm& f, hipStream_t s);
 // Recover from an address table (fec_gather.hip): the classify scan (fec_table.hpp classify_table,
 // one kernel template for the three table recovers, traced under each call's own classify form),
 // then table_recover_form's recover_gather.
@@ -60,7 +69,7 @@ hipError_t launch_encode_scatter(const TableEncodeLaunch& a, hipStream_t s);
 // chunk's place in the call, for the launch trace.
 hipError_t launch_build_records(const PlanLaunch& p, const uint64_t* masks, uint32_t* rec_off, uint8_t* status,
                                 uint64_t first_group, uint64_t groups, uint32_t k, uint32_t r, hipStream_t s);
-// Packed recover rows: row_start[g] = exclusive prefix sum of the rows each group rebuilds
+// Packed recover rows (fec_runs.hip): row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.
 uint64_t rows_prefix_workspace_bytes(uint64_t groups);
@@ -74,102 +83,8 @@ uint32_t runs_launches(uint64_t groups);
 uint64_t runs_workspace_bytes(uint64_t groups);
 uint32_t runs_stage_bytes(const RunsLaunch& a);
 hipError_t launch_recover_runs(const RunsLaunch& a, hipStream_t s);
-// ---- resident legacy encoder (fec_coalesce.cpp "resident server") ----
-// A ring of submission slots (page-locked coherent host memory, or VRAM written through the BAR).
-// The host fills slot seq % kServerSlots with a legacy call's groups: every 8-B word of a slot
-// carries the slot's tag, server_tag(seq), in its top 16 bits, so the device recognises a
-// complete slot by the tags alone, whatever order its reads of the host's stores land in.  An
-// aligned 8-B store is the unit the host's stores are assumed to arrive in (x86 quadword
-// atomicity); nothing larger is assumed to arrive in one piece, so every 8-B word is
-// self-validating.  Resident workgroups serve the slots in seq order (one per serving class,
-// below) and store done[seq % kServerSlots] = seq + 1.  Calls are served without a kernel launch
-// each.
-//
-// Tags and the epoch.  A slot's tag is (lap & (epoch - 1)) + 1 with lap = seq / kServerSlots and
-// epoch a power of two (no division on the server's critical path), so the tags of one slot
-// repeat every `epoch` laps (32768; shorter in the test library, fec_knobs.hpp kResidentEpoch).  A word left from the previous epoch could carry the current tag (a word written
-// exactly `epoch` laps ago and not since, e.g. a later group's address word under inline-only
-// calls), so the slot is scrubbed at every epoch boundary: the server zeroes the slot's words
-// and its inline data area after serving the last lap of an epoch, before that slot's done word
-// (its next occupant writes only after it has seen the done word, so the zeroes are in place
-// first), and the host zeroes the slot's inline output staging before publishing the first lap
-// of an epoch.  Within an epoch every tag of a slot is used once, so no stale word matches;
-// tag 0 (the zeroed state) never matches.
-constexpr uint32_t kServerSlots = 1024;
-constexpr uint32_t kServerMaxGroups = 8;  // groups per slot (legacy calls of 1..8 groups)
-constexpr uint32_t kServerPackets = 10;   // the legacy call's packets per group
-constexpr uint64_t kServerTagShift = 48;  // addresses below 2^48 (x86-64 user virtual addresses)
-constexpr uint64_t kServerAddrMask = (1ull << kServerTagShift) - 1;
-constexpr uint32_t kServerEpoch = 32768;  // laps per tag epoch, a power of two (tags 1 .. epoch fit 16 bits)
-__host__ __device__ inline uint32_t server_tag(uint64_t seq, uint32_t epoch) {
-  return (static_cast<uint32_t>(seq / kServerSlots) & (epoch - 1u)) + 1u;
-}
-// Whether the server scrubs the slot of seq after serving it (the last lap of an epoch).
-__host__ __device__ inline bool server_scrub_after(uint64_t seq, uint32_t epoch) {
-  return (static_cast<uint32_t>(seq / kServerSlots) & (epoch - 1u)) == epoch - 1u;
-}
-struct alignas(64) ServerSlot {
-  uint64_t out;             // tag | device address of the repair rows, row g at out + g * P
-  uint64_t shape;           // tag | P (bits 0..15) | groups (bits 16..23; 0 = nothing to do) | kServerInline
-  uint64_t addr[kServerMaxGroups * kServerPackets];  // tag | device address of packet (g, j) at [g * 10 + j]
-};
-// VRAM ring (large-BAR devices, fec_coalesce.cpp Resident): the slots and the packets of small
-// calls live in uncached device memory that the host writes through the BAR, so the server's
-// poll and packet loads stay on the device.  An inline slot (shape bit kServerInline) carries
-// no addresses: its packets are copied by the host into the slot's data area, packet (g, j) as
-// 16-B chunks at chunk (g * 10 + j) * nch + c, nch = ceil(P / 12).  A chunk is two 8-B halves,
-// each 6 payload bytes and the slot's 16-bit tag in its top two bytes:
-//   bytes 0..5 = payload [12c, 12c + 6), bytes 6..7 = tag, bytes 8..13 = payload [12c + 6,
-//   12c + 12), bytes 14..15 = tag (payload zero past P),
-// so each half validates itself (a 16-B write-combined store may reach the device as two 8-B
-// pieces) and no ordering of the host's stores through the BAR is assumed.  The rows come back
-// the same way: an inline slot's `out` is its output staging in page-locked host memory, repair
-// chunk (g, c) in the same two-half form at out + (g * nch + c) * 16, and the host takes the rows
-// once both halves of every chunk carry the tag (the done word then only says "consumed").
-constexpr uint64_t kServerInline = 1ull << 24;
-constexpr uint32_t kInlineMaxGroups = 4;
-constexpr uint32_t kInlineMaxP = 1536;
-constexpr uint32_t kInlinePayload = 12;  // payload bytes of a 16-B chunk (6 per 8-B half)
-constexpr uint32_t kInlineSlotBytes = kInlineMaxGroups * kServerPackets * (kInlineMaxP / kInlinePayload) * 16;
-// Serving classes.  An instance is `classes` workgroups (a power of two, 1 .. kServerMaxClasses,
-// so it divides kServerSlots): workgroup c serves the seqs with seq % classes == c, in order, so
-// concurrent callers are served by independent poll -> serve -> done cycles.
-constexpr uint32_t kServerMaxClasses = 8;
-constexpr uint32_t kServerPoll = 16;  // slots of its class a workgroup reads per poll (the longest run it serves)
-struct alignas(64) ServerControl {
-  uint64_t stop;            // host -> device: leave at the next poll
-  uint64_t pad0[7];
-  uint64_t exited;          // device -> host: generation of the last instance that left (its last workgroup)
-  uint64_t pad1[7];
-  uint64_t progress[kServerMaxClasses];   // device -> host: every seq of class c below progress[c] was served
-  uint64_t bad_slots[kServerMaxClasses];  // device -> host: polls that found a slot with a word not yet landed (diagnostic)
-  uint64_t scrubs[kServerMaxClasses];     // device -> host: slots scrubbed at an epoch boundary (diagnostic)
-};
-// Device memory the workgroups of one instance share (uncached: they run on different XCDs, each
-// with its own L2).  Words are tagged with the instance's generation, so nothing is reset
-// between instances.
-struct alignas(64) ServerCoord {
-  uint64_t leave;                      // gen: every workgroup of instance gen leaves at its next poll
-  uint64_t exits;                      // (gen << 8) | workgroups of instance gen that have left
-  uint64_t pad[6];
-  uint64_t idle[kServerMaxClasses];    // gen while class c's workgroup has been idle for idle_ticks, else 0
-};
-// The coordination rules, shared by legacy_server and the CPU model (tests/csrc/ring_protocol_test.cpp).
-// Whether every class of instance gen is idle: this one (idle, now) and the others by the flags
-// it last read (idle_seen[c] == gen; a flag of an earlier instance never counts).
-__host__ __device__ inline bool server_all_idle(bool idle, const uint64_t* idle_seen, uint32_t classes, uint32_t cls,
-                                                uint64_t gen) {
-  bool all = idle;
-  for (uint32_t c = 0; c < classes; ++c) all = all && (c == cls || idle_seen[c] == gen);
-  return all;
-}
-// The exit count: a workgroup leaving instance gen turns the word v into this (the word still
-// holds the previous instance's count until the first of this one's); the workgroup whose new
-// word counts all `classes` is the last out and stores ctl->exited = gen.
-__host__ __device__ inline uint64_t server_exits_next(uint64_t v, uint64_t gen) {
-  return (v >> 8) == gen ? v + 1 : (gen << 8) | 1u;
-}
-__host__ __device__ inline bool server_exits_last(uint64_t nv, uint32_t classes) { return (nv & 0xFFu) == classes; }
+// ---- resident legacy encoder (fec_server.hip; the ring's protocol -- slots, control and
+// coordination words, tags and the epoch, serving classes -- is fec_server.hpp's) ----
 // One resident instance serving the ring, each class from its progress mark, until every class
 // has found nothing to do for idle_ticks, or it lived life_ticks (wall-clock ticks,
 // hipDeviceAttributeWallClockRate), or the host sets ctl->stop; on leaving a workgroup stores its
@@ -186,10 +101,32 @@ hipError_t launch_legacy_server(ServerSlot* ring, uint8_t* inl, uint64_t* done, 
                                 uint64_t slow_ticks, uint64_t life_ticks, uint64_t* stamps, uint32_t epoch,
                                 hipStream_t s);
 
+// Synthetic data and the box calibration copy (fec_util.hip).
 hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t nbytes, uint64_t seed, uint64_t byte_offset,
                                 hipStream_t s);
 // dst <- src, nbytes a multiple of 16, both 16-B aligned (box calibration).
 hipError_t launch_copy_words(const uint8_t* src, uint8_t* dst, uint64_t nbytes, hipStream_t s);
+
+// Each kernel translation unit is a code object of its own, and the HIP runtime loads a code object
+// onto the current device at the first use of one of its functions.  load_*_unit asks for the
+// attributes of one kernel of its unit -- no launch -- which is such a use; load_kernel_units loads
+// the six units of the contiguous calls, so that no first call pays for it (fec_shim.cpp
+// warm_device_once).  The address-table and plan units load at their first call.
+hipError_t load_encode_unit();
+hipError_t load_decode_unit();
+hipError_t load_decode_fused_unit();
+hipError_t load_runs_unit();
+hipError_t load_server_unit();
+hipError_t load_util_unit();
+inline hipError_t load_kernel_units() {
+  hipError_t (*const units[])() = {load_encode_unit, load_decode_unit, load_decode_fused_unit,
+                                   load_runs_unit,   load_server_unit, load_util_unit};
+  for (auto load : units) {
+    const hipError_t e = load();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 // Records marking "nothing to do" / "unrecoverable" in rec_off.
 constexpr uint32_t kRecNone = 0xFFFFFFFFu;

@@ -52,7 +52,7 @@ long test_knob(TestKnob k, long def);
 bool test_knobs_enabled();
 
 // ---- launch trace ----
-// Every host launcher of fec_kernels.hip reports each kernel launch here, so that a test can
+// Every host launcher of the kernel translation units reports each kernel launch here, so that a test can
 // see which kernel form produced the bytes it checks.  Like test_knob() this is compiled twice:
 // in libfec_hip.so trace_launch() is an empty function and nothing is stored; in
 // libfec_hip_test.so it appends the record to a bounded buffer (under a mutex: the batcher's

@@ -1,17 +1,39 @@
-// fec_launch.hpp — what the host launchers of the kernel translation units (fec_kernels.hip,
-// fec_gather.hip, fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip) share: the per-launch limits with their
-// test switches, the chunk walk, the pass-and-chunk walk of the wave-per-group kernels, the row
-// passes of the runtime-k encodes and the launch trace's record.  Host code only.
+// fec_launch.hpp — what the host launchers of the kernel translation units (fec_encode.hip,
+// fec_decode.hip, fec_decode_fused.hip, fec_runs.hip, fec_server.hip, fec_util.hip, fec_gather.hip,
+// fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip, fec_plan.hip) share: the per-launch
+// limits with their test switches, the chunk walk, the pass-and-chunk walk of the wave-per-group
+// kernels, the row passes of the runtime-k encodes, the launch trace's record, and the small
+// launch arguments more than one unit computes (knob, decode_swizzle, rank_meta).  Host code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "fec_device.hpp"  // RankMeta
 #include "fec_forms.hpp"
 #include "fec_knobs.hpp"
 
 namespace qfec {
+
+// A test-library switch (fec_knobs.hpp) as an int; `def` in the product library.
+inline int knob(TestKnob k, int def) { return static_cast<int>(test_knob(k, def)); }
+
+// XCD-aware group order for a decode kernel: at k=10 r=3 measured +10% for decode_fused and
+// -1%..+5% for decode_wave over two boxes (tools/probe_decode.hip; tunable per kernel).
+inline uint32_t decode_swizzle(const DecodeLaunch& a, int tuned) {
+  return static_cast<uint32_t>(a.xcd_swizzle >= 0 ? a.xcd_swizzle : tuned);
+}
+
+namespace {
+// Levels 1..3 of the codebook, all the mask-addressed kernels rank (RankMeta is internal to its
+// translation unit, as all of fec_device.hpp).
+inline RankMeta rank_meta(const LevelMeta& m) {
+  RankMeta rm{};
+  for (int e = 1; e <= 3; ++e) rm.base[e] = m.base[e], rm.stride[e] = m.stride[e], rm.count_r[e] = m.count_r[e];
+  return rm;
+}
+}  // namespace
 
 constexpr uint32_t kMaxThreadsPerLaunch = 1u << 30;
 // Wave-per-group decode launches: 256-thread workgroups, so at most 2^22 of them keep the

@@ -17,8 +17,8 @@
 // (fec_plan_build.hpp, build_records) and the probes.  Plain C++ with no HIP include, so a host
 // program checks these very functions (tests/csrc/mask_rule_test.cpp); no path shifts a 64-bit
 // value by 64, whatever k and r.
-// Who does NOT: the mask-addressed hot kernels of fec_kernels.hip (decode_fused's DIRECT / INLINE
-// forms, recover_runs) keep their own hand-written statement of this rule, with compile-time K and
+// Who does NOT: the mask-addressed hot kernels (fec_decode_fused.hip decode_fused's DIRECT / INLINE
+// forms, fec_runs.hip recover_runs) keep their own hand-written statement of this rule, with compile-time K and
 // their own guards, because calling these functions changes their instructions
 // (profiles/mask_rule/VERDICT.md); they take only low_bits(K) and ChooseSmall from here.  A change
 // to the rule has to be made there too, and only the GPU every-mask tests (tests/test_gpu_forms.py)

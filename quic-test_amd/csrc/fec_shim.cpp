@@ -2,7 +2,7 @@
 //
 // Replaces the reference's native library internal/fec/fec_xor_simd.cpp behind the
 // same eleven symbols, and adds the batch GF(2^8) encode/decode API.  All arithmetic
-// runs in the gfx950 kernels of fec_kernels.hip; this file owns contexts, device
+// runs in the gfx950 kernels (fec_kernels.hpp names their units); this file owns contexts, device
 // buffers, host<->device staging, per-(k,r) plans and error reporting.
 //
 // Threading (SURVEY.md §8(b) "Threading"): one context per caller stream of work; every
@@ -395,17 +395,21 @@ struct CtxBound {
   }
 };
 
-// The first kernel launched on a device loads the library's code object there (all kernels of
-// fec_kernels.hip at once), and the resident encoder's first call allocates its page-locked
-// ring: together ~26 ms that otherwise land on the first fec_encode_batch of the process — the
-// first repair packet of the first QUIC stream (batcher_latency legacy_raw: max delay 25.8-27.5
-// ms without, 11.5-12.2 ms with the code object loaded here).  Done once per device, at the
-// first context; failures are left to the calls that follow (they report them).
+// The first use of a kernel on a device loads its translation unit's code object there, and the
+// resident encoder's first call allocates its page-locked ring: together ~26 ms that otherwise
+// land on the first fec_encode_batch of the process — the first repair packet of the first QUIC
+// stream (batcher_latency legacy_raw: max delay 25.8-27.5 ms without, 11.5-12.2 ms with the code
+// objects loaded here).  Loaded here: the six units of the contiguous calls (fec_kernels.hpp
+// load_kernel_units: the encodes, the decodes, decode_fused, the packed rows, the resident server,
+// the utilities), so none of their first calls loads one; then one launch of the fill kernel, the
+// device's first.  The address-table and plan units load at their first call.  Done once per
+// device, at the first context; failures are left to the calls that follow (they report them).
 void warm_device_once(int device, hipStream_t s) {
   constexpr int kMaxWarm = 64;
   static std::once_flag once[kMaxWarm];
   if (device < 0 || device >= kMaxWarm || std::getenv("QUICFEC_NO_WARMUP") != nullptr) return;
   std::call_once(once[device], [&] {
+    (void)qfec::load_kernel_units();
     uint8_t* p = nullptr;
     if (hipMalloc(&p, 256) == hipSuccess) {
       if (qfec::launch_fill_splitmix(p, 256, 0, 0, s) == hipSuccess) (void)hipStreamSynchronize(s);

@@ -6,7 +6,8 @@
 // costs; if not, the k=20 r=5 read/write mix itself is the ceiling.  Not part of the library.
 //
 //   probe_c4 [groups] [rounds]
-#include "../fec_kernels.hip"
+#include "../fec_encode.hip"
+#include "../fec_util.hip"
 
 #include <algorithm>
 #include <cstdio>

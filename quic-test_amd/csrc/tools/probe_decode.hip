@@ -1,6 +1,9 @@
 // probe_decode.hip — development probe: decode kernel variants A/B in one process, each
 // verified to rebuild the poisoned shards exactly.  Not part of the library.
-#include "../fec_kernels.hip"
+#include "../fec_decode.hip"
+#include "../fec_decode_fused.hip"
+#include "../fec_encode.hip"
+#include "../fec_util.hip"
 
 #include <algorithm>
 #include <cstdio>

@@ -1,7 +1,8 @@
 // probe_encode.hip — development probe: HBM ceilings and encode-kernel variants,
 // interleaved in one process (cdna_hip_programming.md §5.4 rule 24).  Not part of the
 // library.  Build: make -C quic-test_amd/csrc probe ; run: quic-test_amd/lib/probe_encode
-#include "../fec_kernels.hip"
+#include "../fec_encode.hip"
+#include "../fec_util.hip"
 
 #include <algorithm>
 #include <cstdio>

@@ -6,7 +6,11 @@
 //
 //   probe_runs [groups] [rounds] [loss]      loss > 0: iid per shard (C5: 0.01); 0: 2 erasures
 //                                             per group uniform over the 13 shards (C3)
-#include "../fec_kernels.hip"
+#include "../fec_decode.hip"
+#include "../fec_decode_fused.hip"
+#include "../fec_encode.hip"
+#include "../fec_runs.hip"
+#include "../fec_util.hip"
 
 #include <algorithm>
 #include <cstdio>

@@ -638,7 +638,7 @@ PLAN_LAUNCH_FORMS = {26: "build_records"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
-# the `pol` bits (csrc/fec_kernels.hip)
+# the `pol` bits (csrc/fec_forms.hpp)
 POL_NT_LOAD, POL_NT_STORE, POL_NO_COEF_BRANCH, POL_LDS_TABS = 1, 2, 4, 64
 POL_COMPACT_OUT, POL_COEF_BYTES, POL_PAIR_MAC, POL_STAGE_ROWS = 1024, 2048, 4096, 8192
 

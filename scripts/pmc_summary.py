@@ -38,7 +38,7 @@ def collect(d: Path, counter: str):
     return vals
 
 
-K_COMPACT_OUT = 1024  # fec_kernels.hip kCompactOut: the recover (rebuilt packets back to back) forms
+K_COMPACT_OUT = 1024  # fec_forms.hpp kCompactOut: the recover (rebuilt packets back to back) forms
 
 
 def short(name: str) -> str:

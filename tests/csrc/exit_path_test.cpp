@@ -16,7 +16,7 @@
 // buffers; the *hostring modes keep the resident ring in page-locked host memory
 // (QUICFEC_RESIDENT_VRAM=0: the ring kind is fixed per process).
 //
-// The ring's tag checks (fec_kernels.hpp server_tag):
+// The ring's tag checks (fec_server.hpp server_tag):
 //  * tear: QUICFEC_RESIDENT_TEST_TEAR -- every inline call stores one chunk's tagged high half
 //    first and its low half ~100 us after the slot's header (a write-combined 16-B store evicted
 //    in two pieces), and every addressed call of several groups stores its later groups' address

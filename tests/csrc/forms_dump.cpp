@@ -1,7 +1,7 @@
 // forms_dump.cpp — prints which kernel form csrc/fec_forms.hpp decides for every packet size,
 // with no GPU: one line per query, "<query> | <launch> ; <launch> ..." or "<query> | refused",
-// each launch in the field names of quicfec.launch_trace as the launchers of fec_kernels.hip
-// record it.  tests/test_gpu_forms.py compares every line with its table.
+// each launch in the field names of quicfec.launch_trace as the launchers of the kernel units
+// (fec_encode.hip, fec_decode.hip, fec_decode_fused.hip, fec_runs.hip) record it.  tests/test_gpu_forms.py compares every line with its table.
 //
 //   forms_dump             decode (in place, slots, packed) and encode queries
 //   forms_dump --packed    the packed decode queries only (run with QUICFEC_PACKED_RUNS set,

@@ -1,6 +1,7 @@
 // kernel_emulation.cpp — CPU check of the GPU library's table arithmetic (tests only).
 //
-// Re-executes, on the CPU, exactly the per-dword arithmetic of fec_kernels.hip
+// Re-executes, on the CPU, exactly the per-dword arithmetic of the kernels (fec_device.hpp gmul,
+// as fec_encode.hip and the decode units use it)
 // (v_perm_b32 table lookups, the classify ranking, codebook-driven rebuild) using the
 // product's own host code (quic-test_amd/csrc/gf256.hpp), and compares the bytes with the
 // oracle restatement (oracle/liboracle.so).  Lets the CPU suite catch table / ranking /
@@ -212,7 +213,7 @@ int main() {
       if (!dense && !qfec::build_sparse_plan(k, r, M, masks.data(), G, 0xFFFFFFFFu, 0xFFFFFFFEu, book, sro, sst))
         return fail("sparse", k, r, P);
       for (uint64_t g = 0; g < G; ++g) {
-        // classify (fec_kernels.hip)
+        // classify (fec_decode.hip)
         const uint64_t kmask = (1ull << k) - 1, rmask = (r >= 64) ? ~0ull : ((1ull << r) - 1);
         uint64_t dm = masks[g] & kmask;
         const uint64_t pm = (masks[g] >> k) & rmask;

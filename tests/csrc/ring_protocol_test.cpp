@@ -1,6 +1,6 @@
 // ring_protocol_test.cpp — CPU model check of the resident encoder's ring protocol (tests only).
 //
-// Uses the product's own definitions (fec_kernels.hpp: ServerSlot / ServerControl / ServerCoord
+// Uses the product's own definitions (fec_server.hpp, plain C++: ServerSlot / ServerControl / ServerCoord
 // layout, server_tag, server_scrub_after, the inline chunk constants) and checks the properties
 // the server's and the host's acceptance rules rest on (DESIGN_HISTORY.md §8c round 5):
 //  1. tags: 1 .. epoch, never 0 (the zeroed state); a slot's tags over `epoch` consecutive laps are
@@ -31,7 +31,7 @@
 #include <set>
 #include <vector>
 
-#include "fec_kernels.hpp"
+#include "fec_server.hpp"
 
 using namespace qfec;
 

@@ -242,7 +242,7 @@ def test_kernel_arithmetic_emulation(tmp_path, oracle_mod):
 
 def test_resident_ring_protocol_model(tmp_path):
     """The resident ring's acceptance rules checked on the CPU against the product's own
-    definitions (fec_kernels.hpp server_tag / server_scrub_after, the slot, control and
+    definitions (fec_server.hpp, which needs no HIP: server_tag / server_scrub_after, the slot, control and
     coordination layouts): tags unique within an epoch and never 0, no stale 8-B word accepted
     over 40 epochs of torn, partly rewritten laps with the epoch scrub (and a stale acceptance
     without it, the control), serving classes' seqs confined to their own slots with the
@@ -251,7 +251,7 @@ def test_resident_ring_protocol_model(tmp_path):
     together, none on an earlier instance's words, exactly one stores exited (ADVICE r05;
     controls without the generation checks must fail) (tests/csrc/ring_protocol_test.cpp)."""
     exe = tmp_path / "ring_protocol_test"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+    subprocess.run(["g++", "-O2", "-std=c++17",
                     "-I", str(REPO / "quic-test_amd" / "csrc"), str(REPO / "tests" / "csrc" / "ring_protocol_test.cpp"),
                     "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)

@@ -173,8 +173,12 @@ def test_null_context_is_refused_without_a_gpu(quicfec_mod, which):
 def test_new_kernel_is_built_and_hashed():
     """fec_plan.hip is an object of both libraries and among the hashed sources."""
     mk = (CSRC / "Makefile").read_text()
-    assert "fec_plan.hip" in re.search(r"^SRCS := (.*)$", mk, re.M).group(1)
-    assert "$(OUT_DIR)/fec_plan.o" in re.search(r"^COMMON := (.*\\\n.*)$", mk, re.M).group(1)
+    assert "fec_plan.hip" in re.search(r"^SRCS := (.*)$", mk, re.M).group(1).split()
+    # the objects both libraries share are derived from SRCS: make's own link lines name the object
+    dry = subprocess.run(["make", "-C", str(CSRC), "-n", "-B", "../lib/libfec_hip.so", "../lib/libfec_hip_test.so"],
+                         capture_output=True, text=True, check=True).stdout
+    links = [ln for ln in dry.splitlines() if " -shared " in ln]
+    assert len(links) == 2 and all("../lib/fec_plan.o" in ln.split() for ln in links), links
     import sys
     sys.path.insert(0, str(CSRC))
     import src_hash

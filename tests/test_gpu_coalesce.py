@@ -445,7 +445,7 @@ def test_resident_ring_kinds_mixed_shapes(mode):
 
 
 def test_resident_serves_no_torn_chunk_or_late_address_word():
-    """The VRAM ring's tags are per 8-B word (fec_kernels.hpp server_tag):
+    """The VRAM ring's tags are per 8-B word (fec_server.hpp server_tag):
     with QUICFEC_RESIDENT_TEST_TEAR every inline call stores one chunk's tagged high half first
     and its low half ~100 us after the slot's header -- a 16-B write-combined store reaching the
     device as two pieces -- and every addressed call of several groups stores its later groups'
@@ -532,7 +532,7 @@ _SERVER_MODES = [("resident", 300), ("mixed", 360), ("mixed_hostring", 360), ("t
 def test_resident_serving_classes(mode, calls, servers):
     """QUICFEC_RESIDENT_SERVERS: the resident instance is `servers` workgroups (default 8 on the
     VRAM ring, which the runs above use, 1 on the page-locked ring), workgroup c serving the seqs of class c (seq % servers == c) with its own
-    poll, run, done words and progress mark (fec_kernels.hip legacy_server).  Every ring-protocol
+    poll, run, done words and progress mark (fec_server.hip legacy_server).  Every ring-protocol
     run above -- mixed shapes on both ring kinds, torn chunks and late address words, epoch scrubs,
     poisoning under 8 threads, relaunch cycles under 4 -- gives every row equal to the CPU XOR
     with one, two and four classes too, and the exit stays HIP-free."""

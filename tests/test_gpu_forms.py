@@ -116,7 +116,7 @@ def expected_decode(api, k, r, P, scan=False, runs=False):
 
 
 def pick_tile(cpp, k, P):
-    """Groups per workgroup of the tiled mapping (fec_kernels.hip pick_tile: fewest idle lanes of
+    """Groups per workgroup of the tiled mapping (fec_forms.hpp pick_tile: fewest idle lanes of
     whole waves, +0.05 when the tile's bytes are no multiple of 128, +0.02 below 256 lanes;
     0 = flat, more than 512 columns per packet)."""
     if cpp == 0 or cpp > 512:
@@ -657,7 +657,7 @@ def compiled_instantiations(forms_dump):
     """The kernel instantiations libfec_hip.so carries: the decode forms and recover_runs as
     forms_dump --compiled expands them from the lists of csrc/fec_forms.hpp that launch_decode and
     launch_recover_runs dispatch on; the encodes and the rest from the lists in fec_forms.hpp /
-    fec_kernels.hip (QFEC_ENCODE_*_FORMS, run_encode_generic)."""
+    fec_encode.hip (QFEC_ENCODE_*_FORMS, run_encode_generic)."""
     out = {sig_of(_parse_launch(line)) for line in forms_dump("--compiled")}
     for off in range(4):
         out.add(form("encode_bytes", k=0, off=off))

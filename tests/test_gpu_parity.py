@@ -417,7 +417,7 @@ def test_full_size_c4_shard_encode(gpu_ctx, oracle_mod, torch_cuda):
 # ---------------- any packet size, any packet address ----------------
 #
 # P >= 16 runs on the 16-byte-column kernels whatever P % 16 and the packet alignment are:
-# the last column of a packet is shifted back to end at P (fec_kernels.hip header).  These
+# the last column of a packet is shifted back to end at P (fec_encode.hip header).  These
 # cases cover every encode form (compile-time k, runtime-k loop, gathered offsets) and every
 # decode form the library picks (fused with NT = 1..4 tail pieces, mask-addressed or not,
 # the runtime-k wave kernel), with sizes around the 16-B, 256-B and 1 KiB boundaries.  They
