@@ -83,7 +83,7 @@ def fast_arena(c, seed, encode=False, at_length=False):
     if at_length:
         data, par = c.raw, c.praw
     else:
-        data, par = c.data.reshape(G, k, P), c.par.reshape(G, r, P)
+        data, par = c.data.reshape(G, k, P), c.par_in.reshape(G, r, P)       # junk in the rows the rule does not read
     cols = np.arange(PAD_MAX + width)
     where = np.full((G, n, 2), -1, dtype=np.int64)
     where[:, :, 1] = 0
@@ -126,7 +126,7 @@ def check_fast_arena(c, at_length):
             want = c.raw[g, s, :ln] if s < k else c.praw[g, s - k, :ln]
         else:
             ln = P
-            want = c.data.reshape(G, k, P)[g, s] if s < k else c.par.reshape(G, r, P)[g, s - k]
+            want = c.data.reshape(G, k, P)[g, s] if s < k else c.par_in.reshape(G, r, P)[g, s - k]
         assert np.array_equal(arenas[a][off:off + ln], want), (g, s)
         assert (arenas[a][off - 1] == 0xEE) and arenas[a][off + ln] == 0xEE  # a pad before it, 0xEE right after it
         used[a][off:off + ln] += 1

@@ -22,6 +22,7 @@ import test_gpu_gather as fx
 import test_gpu_gather_var as var
 import test_gpu_scatter as sc
 import test_gpu_streams as st
+import unread_shards as us
 from test_gpu_address_limits import G_MAIN, check_limit_case, limit_masks
 from test_gpu_gather import hooks_ctx, product_ctx
 from test_gpu_gather_var import dealt_lengths, edge_lengths
@@ -273,7 +274,8 @@ def test_chunked_walk_equals_the_single_chunk(quicfec_mod, oracle_mod, torch_cud
 # ------------------------------------------------------------------------------------------
 def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda):
     """test_gpu_streams.py's pipeline for k=16 r=16 P = 32 G = 131 in FEC_PLAN_DEVICE: fill -> encode
-    -> lost shards overwritten -> masks copied in -> recover into slots -> decode in place, all
+    -> every shard the rule does not read overwritten with the case's junk -> masks copied in -> recover
+    into slots -> decode in place, all
     queued on one non-blocking side stream behind 32 fills of 1 GiB, one synchronise at the end.
     When the calls are made the masks say "every shard lost" (a host read would find every group
     unrecoverable), and when they have returned the stream is still busy with the work queued ahead
@@ -281,8 +283,9 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda):
     torch = torch_cuda
     k, r, P, G = 16, 16, 32, 131
     c = st._case(oracle_mod, k, r, P, G)
-    lost = (c.masks[:, None] >> np.arange(k + r, dtype=np.uint64)[None, :]) & np.uint64(1)
-    d_lost = st._dev(torch, lost.astype(bool))
+    ro = us.roles(c.masks, k, r)
+    d_junk_d, d_junk_p = st._dev(torch, ro.lost_d), st._dev(torch, ro.unread_p)
+    d_broken, d_par_in = st._dev(torch, c.broken).view(G, k, P), st._dev(torch, c.par_in).view(G, r, P)
     d_masks_src = st._dev(torch, c.masks.view(np.int64))
     dd = torch.full((G * k * P,), 0x11, dtype=torch.uint8, device="cuda")
     par = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
@@ -304,8 +307,8 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda):
         ctx.fill_random_dev(dd, G * k * P, c.seed, 0, stream=s)
         ctx.encode_dev(dd, G, k, r, P, par, stream=s)
         with torch.cuda.stream(stream):
-            dd.view(G, k, P).masked_fill_(d_lost[:, :k, None], 0xEE)
-            par.view(G, r, P).masked_fill_(d_lost[:, k:, None], 0xEE)
+            dd.view(G, k, P).copy_(torch.where(d_junk_d[:, :, None], d_broken, dd.view(G, k, P)))
+            par.view(G, r, P).copy_(torch.where(d_junk_p[:, :, None], d_par_in, par.view(G, r, P)))
             dm.copy_(d_masks_src, non_blocking=True)
         st.launch(ctx, slots, stream)
         with torch.cuda.stream(stream):
@@ -320,6 +323,7 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda):
     st.check(slots)
     assert np.array_equal(status.cpu().numpy(), c.status)
     assert np.array_equal(dd.cpu().numpy(), c.ref)
+    assert np.array_equal(par.cpu().numpy(), c.par_in)
 
 
 def test_two_threads_on_two_streams(quicfec_mod, oracle_mod, torch_cuda):

@@ -3,8 +3,9 @@
 Every other GPU test checks the bytes a call produced; a call that quietly fell back to another
 correct form would pass them all.  These run through libfec_hip_test.so (gpu_ctx_hooks), whose
 launchers record every kernel launch (csrc/fec_knobs.hpp LaunchRecord, quicfec.launch_trace), and
-check two things per case: the bytes, statuses, row starts and totals against the oracle (0xEE in
-lost shards, 0x5A in unwritten output, 7 in unwritten status), and the launches against the table
+check two things per case: the bytes, statuses, row starts and totals against the oracle (seeded junk in
+every shard the erasure rule does not read -- tests/unread_shards.py -- 0x5A in unwritten output,
+7 in unwritten status), and the launches against the table
 below.
 
 The table (expected_decode / expected_encode) is written from the dispatch rules as documented --
@@ -25,6 +26,8 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+
+import unread_shards as us
 
 gpu = pytest.mark.gpu
 
@@ -237,17 +240,18 @@ def perm_masks(k, r, G, seed):
 class Case:
     """One batch and everything the oracle says about it, computed once and never modified."""
 
-    def __init__(self, oracle, k, r, P, masks):
+    def __init__(self, oracle, k, r, P, masks, need_unchosen_alive=True):
         G = len(masks)
         self.k, self.r, self.P, self.G, self.masks = k, r, P, G, masks
         data = oracle.splitmix_bytes(G * k * P, SEED + k * 31 + r * 7 + P)
-        self.par = oracle.rs_encode(data, G, k, r, P, nthreads=8)
-        lost = ((masks[:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-        broken = data.reshape(G, k, P).copy()
-        broken[lost] = 0xEE
-        self.broken = broken.reshape(-1)
+        self.par = oracle.rs_encode(data, G, k, r, P, nthreads=8)          # true: what an encode must give
+        lost = us.roles(masks, k, r).lost_d
+        # what a decode is given: junk in every lost data shard and every parity row the rule does
+        # not read (a lost row below the highest chosen one needs r > 1)
+        self.broken, self.par_in = us.inputs(data, self.par, masks, k, r, P, SEED + k * 31 + r * 7 + P,
+                                             need_lost_below=r > 1, need_unchosen_alive=need_unchosen_alive)
         ref = self.broken.copy()
-        _, self.status = oracle.rs_decode(ref, self.par, masks, G, k, r, P, nthreads=8)
+        _, self.status = oracle.rs_decode(ref, self.par_in, masks, G, k, r, P, nthreads=8)
         self.ref = ref                                    # in-place result
         ok = self.status == 0
         # the oracle's rebuilt packets are the original ones
@@ -259,7 +263,7 @@ class Case:
         self.slots[gi, mi] = self.rows
         per_group = (lost & ok[:, None]).sum(axis=1)
         self.row_start = np.concatenate([[0], np.cumsum(per_group)[:-1]]).astype(np.uint32)
-        for a in (self.par, self.broken, self.ref, self.status, self.rows, self.slots, self.row_start, self.masks):
+        for a in (self.par, self.par_in, self.broken, self.ref, self.status, self.rows, self.slots, self.row_start, self.masks):
             a.setflags(write=False)
 
 
@@ -272,7 +276,7 @@ def run_decode(ctx, quicfec, torch, c, api, expected):
     """One decode call of `api` on case c: bytes against the oracle, launches against `expected`
     (None: the call must be refused with FEC_ERR_RANGE and touch nothing)."""
     k, r, P, G = c.k, c.r, c.P, c.G
-    dd, dp, dm = _dev(torch, c.broken), _dev(torch, c.par), _dev(torch, c.masks.view(np.int64))
+    dd, dp, dm = _dev(torch, c.broken), _dev(torch, c.par_in), _dev(torch, c.masks.view(np.int64))
     st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
     ctx.synchronize()
     quicfec.launch_trace(ctx.lib)                          # clear
@@ -280,13 +284,13 @@ def run_decode(ctx, quicfec, torch, c, api, expected):
         ctx.decode_dev(dd, dp, dm, G, k, r, P, st)
         ctx.synchronize()
         trace = quicfec.launch_trace(ctx.lib)
-        assert np.array_equal(dd.cpu().numpy(), c.ref)
+        assert np.array_equal(dd.cpu().numpy(), c.ref), us.mismatch(c.masks, k, r, dd.cpu().numpy(), c.ref)
     elif api == "slots":
         out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
         ctx.recover_dev(dd, dp, dm, G, k, r, P, out, st)
         ctx.synchronize()
         trace = quicfec.launch_trace(ctx.lib)
-        assert np.array_equal(out.cpu().numpy().reshape(G, r, P), c.slots)
+        assert np.array_equal(out.cpu().numpy().reshape(G, r, P), c.slots), us.mismatch(c.masks, k, r, out.cpu().numpy(), c.slots)
         assert np.array_equal(dd.cpu().numpy(), c.broken)          # data untouched
     else:
         out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
@@ -300,7 +304,7 @@ def run_decode(ctx, quicfec, torch, c, api, expected):
             assert quicfec.launch_trace(ctx.lib) == []             # refused before anything ran
             assert bool((out == 0x5A).all()) and bool((rs == 0x3C3C3C3C).all()) and int(tot.item()) == -5
             assert bool((st == 7).all())
-            assert np.array_equal(dd.cpu().numpy(), c.broken)
+            assert np.array_equal(dd.cpu().numpy(), c.broken) and np.array_equal(dp.cpu().numpy(), c.par_in)
             return []
         ctx.recover_packed_dev(dd, dp, dm, G, k, r, P, out, rs, tot, st)
         ctx.synchronize()
@@ -312,7 +316,8 @@ def run_decode(ctx, quicfec, torch, c, api, expected):
         assert np.array_equal(o[:n], c.rows)
         assert (o[n:] == 0x5A).all()                               # nothing past the last row
         assert np.array_equal(dd.cpu().numpy(), c.broken)
-    assert np.array_equal(st.cpu().numpy(), c.status)
+    assert np.array_equal(st.cpu().numpy(), c.status), us.mismatch(c.masks, k, r, st.cpu().numpy(), c.status)
+    assert np.array_equal(dp.cpu().numpy(), c.par_in)              # parity only read, junk rows included
     return assert_forms(trace, G, expected)
 
 
@@ -372,6 +377,7 @@ def test_host_decode_scan_choice(gpu_ctx_hooks, quicfec_mod, oracle_mod, torch_c
     rng = np.random.default_rng(int(loss * 100))
     w = np.left_shift(np.uint64(1), np.arange(k + r, dtype=np.uint64))
     masks = ((rng.random((G, k + r)) < loss) * w).sum(axis=1, dtype=np.uint64)
+    masks[0] = 1 | 1 << k                  # planted: row 0 lost, row 1 chosen, row 2 survives unread
     c = Case(oracle_mod, k, r, P, masks)
     lost = (masks & np.uint64((1 << k) - 1)) != 0
     share = float((lost & (c.status == 0)).sum()) / G
@@ -379,8 +385,10 @@ def test_host_decode_scan_choice(gpu_ctx_hooks, quicfec_mod, oracle_mod, torch_c
     ctx = gpu_ctx_hooks
     data, st = c.broken.copy(), np.full(G, 7, dtype=np.uint8)
     quicfec_mod.launch_trace(ctx.lib)
-    bad = ctx.decode(data, c.par, masks, k, r, P, st)
+    par_in = c.par_in.copy()
+    bad = ctx.decode(data, par_in, masks, k, r, P, st)
     trace = quicfec_mod.launch_trace(ctx.lib)
+    assert np.array_equal(par_in, c.par_in)
     assert np.array_equal(data, c.ref) and np.array_equal(st, c.status) and bad == int((c.status != 0).sum())
     assert_forms(trace, G, expected_decode("in_place", k, r, P, scan=share < SCAN_MAX_SHARE))
 
@@ -595,7 +603,8 @@ def test_every_codebook_record(gpu_ctx_hooks, quicfec_mod, oracle_mod, torch_cud
     hide as an 'unrecoverable' group."""
     masks = record_masks(k, r, k * 100 + r)
     assert len(masks) == records
-    c = Case(oracle_mod, k, r, P, masks)
+    # every group rebuilds: with one parity row none survives unchosen
+    c = Case(oracle_mod, k, r, P, masks, need_unchosen_alive=r > 1)
     assert (c.status == 0).all() and len(c.rows) == int(sum(bin(int(m) & ((1 << k) - 1)).count("1") for m in masks))
     for api in ("in_place", "slots"):
         run_decode(gpu_ctx_hooks, quicfec_mod, torch_cuda, c, api, expected_decode(api, k, r, P))

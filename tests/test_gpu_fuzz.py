@@ -3,11 +3,14 @@ count, erasure patterns (up to r + 1 lost, so some groups are unrecoverable) and
 (host pageable, host page-locked, device in place, device recover) drawn from a seeded
 generator.  Each case is small, the whole sweep runs in seconds; it exists to catch the
 interaction bugs that the per-shape parity tests do not pin (form selection, workspace and
-staging reuse across calls of different shapes on one context)."""
+staging reuse across calls of different shapes on one context).  Decode inputs hold junk in every
+shard the erasure rule does not read (tests/unread_shards.py)."""
 import os
 
 import numpy as np
 import pytest
+
+import unread_shards as us
 
 pytestmark = pytest.mark.gpu
 
@@ -36,51 +39,68 @@ def _masks(rng, G, k, r):
     return m
 
 
+def _junked(data, par, masks, k, r, P, seed, seen):
+    """The helper's inputs for one drawn case.  A drawn case may be a single group or have one
+    parity row, so no single case promises a lost row below a chosen one or a surviving unread
+    row; `seen` collects which kinds the block's cases held and the test asserts both at its end."""
+    ro = us.roles(masks, k, r)
+    seen["lost_below"] |= bool(us.has_lost_row_below_chosen(ro).any())
+    seen["unchosen_alive"] |= bool(us.has_unchosen_alive_row(ro).any())
+    return us.inputs(data, par, masks, k, r, P, seed, need_lost_below=False, need_unchosen_alive=False)
+
+
 @pytest.mark.parametrize("block", range(BLOCKS))
 def test_random_shapes_all_apis(gpu_ctx, oracle_mod, torch_cuda, block):
     torch = torch_cuda
     rng = np.random.default_rng(SEED + block)
+    seen = {"lost_below": False, "unchosen_alive": False}
     for _ in range(10):   # one context, shapes and APIs interleaved
         k, r, P, G, api = _case(rng)
         data = oracle_mod.splitmix_bytes(G * k * P, int(rng.integers(0, 1 << 30)))
         par_exp = oracle_mod.rs_encode(data, G, k, r, P, nthreads=4)
         masks = _masks(rng, G, k, r)
-        lost = ((masks[:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-        broken = data.copy().reshape(G, k, P)
-        broken[lost] = 0xEE
+        lost = us.roles(masks, k, r).lost_d
+        broken, par_in = _junked(data, par_exp, masks, k, r, P, SEED + block, seen)
+        broken = broken.reshape(G, k, P)
         ref = broken.copy().reshape(-1)
-        bad_exp, st_exp = oracle_mod.rs_decode(ref, par_exp, masks, G, k, r, P, nthreads=4)
+        bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=4)
         tag = (k, r, P, G, api)
         if api in ("host", "pinned"):
             if api == "pinned":
                 d = torch.from_numpy(data).pin_memory()
                 par = torch.zeros(G * r * P, dtype=torch.uint8).pin_memory()
                 gpu_ctx.encode(d, k, r, P, par, num_groups=G)
-                par_np = par.numpy()
+                par_np = par.numpy().copy()
                 dd = torch.from_numpy(broken.reshape(-1)).pin_memory()
+                par.copy_(torch.from_numpy(par_in))                         # the same page-locked buffer, junk where unread
                 st = torch.zeros(G, dtype=torch.uint8).pin_memory()
                 bad = gpu_ctx.decode(dd, par, torch.from_numpy(masks.view(np.int64)), k, r, P, st, num_groups=G)
-                got, st_np = dd.numpy(), st.numpy()
+                got, st_np, par_after = dd.numpy(), st.numpy(), par.numpy()
             else:
                 par_np = np.zeros(G * r * P, dtype=np.uint8)
                 gpu_ctx.encode(data, k, r, P, par_np, num_groups=G)
                 got = broken.reshape(-1).copy()
                 st_np = np.zeros(G, dtype=np.uint8)
-                bad = gpu_ctx.decode(got, par_np, masks, k, r, P, st_np, num_groups=G)
+                par_after = par_in.copy()
+                bad = gpu_ctx.decode(got, par_after, masks, k, r, P, st_np, num_groups=G)
             assert np.array_equal(par_np, par_exp), tag
             assert bad == bad_exp and np.array_equal(st_np, st_exp), tag
-            assert np.array_equal(got, ref), tag
+            assert np.array_equal(got, ref), tag + (us.mismatch(masks, k, r, got, ref),)
+            assert np.array_equal(par_after, par_in), tag
             continue
         dd = torch.from_numpy(broken.reshape(-1)).cuda()
         d_src = torch.from_numpy(data).cuda()
         dp = torch.zeros(G * r * P, dtype=torch.uint8, device="cuda")
         gpu_ctx.encode_dev(d_src, G, k, r, P, dp)
+        gpu_ctx.synchronize()
+        assert np.array_equal(dp.cpu().numpy(), par_exp), tag
+        dp.copy_(torch.from_numpy(par_in))                                  # junk where the rule does not read
         dm = torch.from_numpy(masks.view(np.int64)).cuda()
         st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
         if api == "dev_inplace":
             gpu_ctx.decode_dev(dd, dp, dm, G, k, r, P, st)
             gpu_ctx.synchronize()
-            assert np.array_equal(dd.cpu().numpy(), ref), tag
+            assert np.array_equal(dd.cpu().numpy(), ref), tag + (us.mismatch(masks, k, r, dd.cpu().numpy(), ref),)
         else:
             out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
             gpu_ctx.recover_dev(dd, dp, dm, G, k, r, P, out, st)
@@ -90,8 +110,9 @@ def test_random_shapes_all_apis(gpu_ctx, oracle_mod, torch_cuda, block):
             for g in np.nonzero(st_exp == 0)[0]:
                 for m, j in enumerate(np.nonzero(lost[g])[0]):
                     assert np.array_equal(o3[g, m], ref3[g, j]), tag + (int(g), int(j))
-        assert np.array_equal(dp.cpu().numpy(), par_exp), tag
+        assert np.array_equal(dp.cpu().numpy(), par_in), tag
         assert np.array_equal(st.cpu().numpy(), st_exp), tag
+    assert seen["lost_below"] and seen["unchosen_alive"], seen
 
 
 @pytest.mark.parametrize("block", range(4))
@@ -160,6 +181,7 @@ def test_random_packed_recover(gpu_ctx_hooks, oracle_mod, torch_cuda, block):
     torch = torch_cuda
     rng = np.random.default_rng(SEED + 200 + block)
     shapes = [(10, 3), (10, 2), (10, 1), (4, 2)]
+    seen = {"lost_below": False, "unchosen_alive": False}
     saved = os.environ.get("QUICFEC_PACKED_RUNS")
     try:
         for _ in range(8):
@@ -177,17 +199,16 @@ def test_random_packed_recover(gpu_ctx_hooks, oracle_mod, torch_cuda, block):
             masks = ((rng.random((G, k + r)) < loss) * w).sum(axis=1, dtype=np.uint64)
             data = oracle_mod.splitmix_bytes(G * k * P, int(rng.integers(0, 1 << 30)))
             par = oracle_mod.rs_encode(data, G, k, r, P, nthreads=4)
-            lost = ((masks[:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-            broken = data.copy().reshape(G, k, P)
-            broken[lost] = 0xEE
-            ref = broken.copy().reshape(-1)
-            _, st_exp = oracle_mod.rs_decode(ref, par, masks, G, k, r, P, nthreads=4)
+            lost = us.roles(masks, k, r).lost_d
+            broken, par_in = _junked(data, par, masks, k, r, P, SEED + 200 + block, seen)
+            ref = broken.copy()
+            _, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=4)
             ok = st_exp == 0
             rows = np.where(ok, lost.sum(axis=1), 0)
             start = np.concatenate([[0], np.cumsum(rows)[:-1]]).astype(np.uint32)
             exp = ref.reshape(G, k, P)[lost & ok[:, None]]
-            dd = torch.from_numpy(broken.reshape(-1)).cuda()
-            dp = torch.from_numpy(par).cuda()
+            dd = torch.from_numpy(broken).cuda()
+            dp = torch.from_numpy(par_in).cuda()
             dm = torch.from_numpy(masks.view(np.int64)).cuda()
             out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
             rs = torch.zeros(G, dtype=torch.int32, device="cuda")
@@ -203,6 +224,8 @@ def test_random_packed_recover(gpu_ctx_hooks, oracle_mod, torch_cuda, block):
             o = out.cpu().numpy().reshape(G * r, P)
             assert np.array_equal(o[:n], exp), tag
             assert (o[n:] == 0x5A).all(), tag
+            assert np.array_equal(dd.cpu().numpy(), broken) and np.array_equal(dp.cpu().numpy(), par_in), tag
+        assert seen["lost_below"] and seen["unchosen_alive"], seen
     finally:
         gpu_ctx.decode_loss_hint(-1.0)
         if saved is None:

@@ -5,7 +5,9 @@ device allocations at arbitrary byte offsets, reached through a table of absolut
 The arena (build_arena): two separate allocations filled with 0xEE; the surviving shards of every
 group, data and parity mixed, placed in a seeded random order at a stride of P + pad with pad drawn
 from 1..37 per shard, so shard addresses take every residue mod 16.  A lost shard is placed nowhere
-and its table entry is 0; every other entry is a readable address.
+and its table entry is 0; every other entry is a readable address.  A surviving parity row the
+erasure rule does not read (a row past the e lowest surviving ones, every row of a group that
+rebuilds nothing: tests/unread_shards.py) is placed like any other, with seeded junk for contents.
 
 After every call: both arenas byte-identical to before; the rebuilt buffer (pre-filled 0x5A, with
 guard bytes before and after) equals the oracle's slots and still holds 0x5A everywhere else;
@@ -19,6 +21,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+import unread_shards as us
 from test_gather_forms import expected_launches      # the table written from DESIGN.md §5b
 
 pytestmark = pytest.mark.gpu
@@ -84,10 +87,12 @@ def make_case(oracle, k, r, P, masks, seed):
     par = oracle.rs_encode(data, G, k, r, P, nthreads=8)
     lost = ((masks[:, None] >> np.arange(k + r, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
     lost_d = lost[:, :k]
-    broken = data.reshape(G, k, P).copy()
-    broken[lost_d] = 0xEE
-    ref = broken.reshape(-1).copy()
-    _, status = oracle.rs_decode(ref, par, masks, G, k, r, P, nthreads=8)
+    # junk in every lost data shard and every parity row the rule does not read.  A lost row has
+    # address 0 in a table, so which groups have one below a chosen row does not matter here, and
+    # make_case also serves encode cases and edge masks: main_case asserts the mix of its own cases.
+    broken, par_in = us.inputs(data, par, masks, k, r, P, seed, need_lost_below=False, need_unchosen_alive=False)
+    ref = broken.copy()
+    _, status = oracle.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
     ok = status == 0
     # the oracle's rebuilt packets are the original ones
     assert np.array_equal(ref.reshape(G, k, P)[ok], data.reshape(G, k, P)[ok])
@@ -95,9 +100,9 @@ def make_case(oracle, k, r, P, masks, seed):
     mi = (np.cumsum(lost_d, axis=1) - 1)[gi, ji]
     slots = np.full((G, r, P), 0x5A, dtype=np.uint8)
     slots[gi, mi] = ref.reshape(G, k, P)[gi, ji]
-    c = SimpleNamespace(k=k, r=r, P=P, G=G, masks=masks, lost=lost, data=data, par=par, broken=broken.reshape(-1),
+    c = SimpleNamespace(k=k, r=r, P=P, G=G, masks=masks, lost=lost, data=data, par=par, par_in=par_in, broken=broken,
                         status=status, slots=slots, rows=len(gi))
-    for a in (c.masks, c.lost, c.data, c.par, c.broken, c.status, c.slots):
+    for a in (c.masks, c.lost, c.data, c.par, c.par_in, c.broken, c.status, c.slots):
         a.setflags(write=False)
     return c
 
@@ -118,6 +123,12 @@ def main_case(oracle, k, r, P):
     if r >= 2:
         assert ((e == 1) & row0_lost).any() and (e >= 2).any()
     assert np.array_equal(e > 0, (c.status == 0) & ((c.masks & kmask) != 0))
+    # a surviving row that a rebuilding group does not read (junk in the arena), and with r >= 2 a
+    # lost row below a chosen one
+    ro = us.roles(c.masks, k, r)
+    assert us.has_unchosen_alive_row(ro).any()
+    if r >= 2:
+        assert (us.has_unchosen_alive_row(ro) & (e > 0)).any() and us.has_lost_row_below_chosen(ro).any()
     return c
 
 
@@ -126,7 +137,8 @@ def main_case(oracle, k, r, P):
 # ------------------------------------------------------------------------------------------
 def build_arena(c, seed, encode=False):
     """Host image of the two arenas and, per table entry, (arena, offset) or (-1, 0) for a lost shard.
-    encode: only the k data packets of every group, all present (the encode call's table)."""
+    encode: only the k data packets of every group, all present (the encode call's table).  A present
+    parity row holds c.par_in: true parity where the rule reads it, junk where it does not."""
     k, r, P, G = c.k, c.r, c.P, c.G
     n = k if encode else k + r
     rng = np.random.default_rng(seed)
@@ -143,7 +155,7 @@ def build_arena(c, seed, encode=False):
         where[gi[i], si[i]] = (a, fill[a])
         fill[a] += P
     arenas = [np.full(fill[a] + 38, 0xEE, dtype=np.uint8) for a in (0, 1)]
-    shards = np.concatenate([c.data.reshape(G, k, P), c.par.reshape(G, r, P)], axis=1)
+    shards = np.concatenate([c.data.reshape(G, k, P), c.par_in.reshape(G, r, P)], axis=1)
     for g, s in zip(gi, si):
         a, off = where[g, s]
         arenas[a][off:off + P] = shards[g, s]
@@ -191,7 +203,8 @@ def check_recover(b, what=""):
     whole = b.whole.cpu().numpy()
     assert (whole[:GUARD] == 0x5A).all() and (whole[GUARD + c.slots.size:] == 0x5A).all(), what
     # the oracle's slots; 0x5A in slots m >= e and in every slot of an unrecoverable group
-    assert np.array_equal(whole[GUARD:GUARD + c.slots.size].reshape(c.G, c.r, c.P), c.slots), what
+    assert np.array_equal(whole[GUARD:GUARD + c.slots.size].reshape(c.G, c.r, c.P), c.slots), \
+        (what, us.mismatch(c.masks, c.k, c.r, whole[GUARD:GUARD + c.slots.size], c.slots))
     assert np.array_equal(b.st.cpu().numpy(), c.status), what
     assert np.array_equal(b.mo.cpu().numpy().view(np.uint64), c.masks), what
 
@@ -219,7 +232,7 @@ def test_arena_addresses_take_every_residue():
     """On the CPU: the arena of a main case puts shards at every residue mod 16 (allocations are
     at least 16-B aligned, so offsets decide), in both arenas, data and parity mixed."""
     c = SimpleNamespace(k=10, r=3, P=1200, G=G_MAIN, lost=np.zeros((G_MAIN, 13), dtype=bool),
-                        data=np.zeros(G_MAIN * 10 * 1200, dtype=np.uint8), par=np.zeros(G_MAIN * 3 * 1200, dtype=np.uint8))
+                        data=np.zeros(G_MAIN * 10 * 1200, dtype=np.uint8), par_in=np.zeros(G_MAIN * 3 * 1200, dtype=np.uint8))
     _, where = build_arena(c, 1)
     for a in (0, 1):
         for part in (where[:, :10], where[:, 10:]):
@@ -246,7 +259,7 @@ def test_identity_table_equals_contiguous_recover(quicfec_mod, oracle_mod, torch
     c = main_case(oracle_mod, k, r, P)
     G = c.G
     dd = torch.from_numpy(np.array(c.broken)).to("cuda")
-    dp = torch.from_numpy(np.array(c.par)).to("cuda")
+    dp = torch.from_numpy(np.array(c.par_in)).to("cuda")
     dm = torch.from_numpy(np.array(c.masks).view(np.int64)).to("cuda")
     s = np.arange(k + r, dtype=np.uint64)
     addr = np.where(s < k, np.uint64(dd.data_ptr()) + (np.arange(G, dtype=np.uint64)[:, None] * np.uint64(k) + s) * np.uint64(P),
@@ -269,7 +282,7 @@ def test_identity_table_equals_contiguous_recover(quicfec_mod, oracle_mod, torch
     assert np.array_equal(outs[1][0][GUARD:-GUARD].reshape(G, r, P), c.slots)
     assert np.array_equal(outs[1][1], c.status)
     assert np.array_equal(mo.cpu().numpy().view(np.uint64), c.masks)
-    assert np.array_equal(dd.cpu().numpy(), c.broken) and np.array_equal(dp.cpu().numpy(), c.par)
+    assert np.array_equal(dd.cpu().numpy(), c.broken) and np.array_equal(dp.cpu().numpy(), c.par_in)
 
 
 # ------------------------------------------------------------------------------------------
@@ -358,7 +371,7 @@ def test_queue_on_one_side_stream(quicfec_mod, oracle_mod, torch_cuda):
         gathers.append(make_recover(torch, c, SEED + 200 + i))
         # a contiguous slot recover of a record-addressed form (its classify writes the workspace too)
         d = SimpleNamespace(c=c, dd=torch.from_numpy(np.array(c.broken)).to("cuda"),
-                            dp=torch.from_numpy(np.array(c.par)).to("cuda"),
+                            dp=torch.from_numpy(np.array(c.par_in)).to("cuda"),
                             dm=torch.from_numpy(np.array(c.masks).view(np.int64)).to("cuda"),
                             st=torch.full((G,), 7, dtype=torch.uint8, device="cuda"))
         d.whole, d.out = guarded(torch, G * r * P, 0x5A)

@@ -9,6 +9,9 @@ seeded random order, each followed by a pad of 1..37 bytes of 0xEE and then the 
 addresses take every residue mod 16; each arena ends with P + 38 bytes of 0xEE.  A read past a
 shard's length therefore changes the output and never leaves the allocation.  A present shard of
 length 0 points at pad bytes.  A lost / absent entry is address 0 and its length entry is garbage.
+A present parity row the erasure rule does not read (a row past the e lowest surviving ones, every
+row of a group that rebuilds nothing: tests/unread_shards.py) keeps its address and its length
+entry -- the group's symbol length is taken over every present entry -- and holds seeded junk.
 
 After every call: both arenas byte-identical to before; the output (pre-filled 0x5A, with guard
 bytes before and after) equals the oracle's and still holds 0x5A everywhere else; status
@@ -21,6 +24,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+import unread_shards as us
 from test_gather_var_forms import expected_encode_launches, expected_recover_launches   # the table of DESIGN.md §5b
 from test_gpu_gather import GUARD, _planted, guarded, hooks_ctx, iid_masks, perm_masks, product_ctx
 
@@ -86,10 +90,19 @@ def make_case(oracle, k, r, P, masks, dlens, plens_min, seed, present=None):
     assert np.array_equal(padded(praw, plens, P), par)
     lost = ((masks[:, None] >> np.arange(k + r, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
     lost_d = lost[:, :k]
-    broken = data.copy()
-    broken[lost_d] = 0xEE
-    ref = broken.reshape(-1).copy()
-    _, status = oracle.rs_decode(ref, par.reshape(-1), masks, G, k, r, P, nthreads=8)
+    # what a recover is given: junk in every parity row the rule does not read, over the row's whole
+    # length (praw is what the arenas place; `par` stays true for the encode comparisons), and in
+    # every lost data shard of the contiguous image the oracle decodes
+    ro = us.roles(masks, k, r)
+    assert np.array_equal(ro.lost_d, lost_d) and np.array_equal(ro.lost_p, lost[:, k:])
+    praw[ro.unread_p] = us.junk(int(ro.unread_p.sum()) * L, seed).reshape(-1, L)
+    praw[ro.unread_p & (padded(praw, plens, P) == par).all(axis=2)] ^= 0xFF      # a row of a few bytes drew the truth
+    par_in = padded(praw, plens, P)
+    assert np.array_equal(par_in[ro.chosen], par[ro.chosen])
+    assert ((par_in != par).any(axis=2) | (plens == 0))[ro.unread_p].all()
+    broken, _ = us.inputs(data, par, masks, k, r, P, seed, need_lost_below=False, need_unchosen_alive=False)
+    ref = broken.copy()
+    _, status = oracle.rs_decode(ref, par_in.reshape(-1), masks, G, k, r, P, nthreads=8)
     ok = status == 0
     assert np.array_equal(ref.reshape(G, k, P)[ok], data[ok])               # rebuilt = the zero-padded originals
     gi, ji = np.nonzero(lost_d & ok[:, None])
@@ -99,9 +112,10 @@ def make_case(oracle, k, r, P, masks, dlens, plens_min, seed, present=None):
     lens = np.concatenate([dlens, plens], axis=1)
     sym_rec = np.where(lost, 0, np.minimum(lens, P)).max(axis=1)
     c = SimpleNamespace(k=k, r=r, P=P, G=G, masks=masks, lost=lost, present=here, raw=raw, praw=praw, data=data, par=par,
-                        lens=lens, status=status, slots=slots, rows=len(gi), sym_enc=sym_enc.astype(np.uint32),
-                        sym_rec=sym_rec.astype(np.uint32))
-    for a in (c.masks, c.lost, c.present, c.raw, c.praw, c.data, c.par, c.lens, c.status, c.slots, c.sym_enc, c.sym_rec):
+                        par_in=par_in, chosen=ro.chosen, lens=lens, status=status, slots=slots, rows=len(gi),
+                        sym_enc=sym_enc.astype(np.uint32), sym_rec=sym_rec.astype(np.uint32))
+    for a in (c.masks, c.lost, c.present, c.raw, c.praw, c.data, c.par, c.par_in, c.chosen, c.lens, c.status, c.slots,
+              c.sym_enc, c.sym_rec):
         a.setflags(write=False)
     return c
 
@@ -159,6 +173,9 @@ def main_case(oracle, k, r, P):
     # every data shard position is a survivor of a rebuilding group under every edge length
     for s in range(k):
         assert set(edges.tolist()) <= set(c.lens[8:][~c.lost[8:, s], s].tolist()), (k, r, P, s)
+    # a rebuilding group with a surviving row it does not read, junk of P bytes in the arena (group 3)
+    if two:
+        assert e[3] == 1 and (~c.lost[3, k:] & ~c.chosen[3]).any() and (c.lens[3, k:] == P).all()
     return c
 
 
@@ -168,7 +185,8 @@ def main_case(oracle, k, r, P):
 def build_arena(c, seed, encode=False, par_rows=None):
     """Host image of the two arenas and, per table entry, (arena, offset) or (-1, 0) for a lost /
     absent one.  encode: the k data packets only.  par_rows (G, r, P): other parity bytes than the
-    oracle's (the round trip places the encode call's own rows)."""
+    oracle's in the rows the rule reads (the round trip places the encode call's own rows); a present
+    row it does not read holds the case's junk either way."""
     k, r, P, G = c.k, c.r, c.P, c.G
     n = k if encode else k + r
     rng = np.random.default_rng(seed)
@@ -191,7 +209,7 @@ def build_arena(c, seed, encode=False, par_rows=None):
             arenas[a][off:off + ln] = c.raw[g, s, :ln]
         else:
             arenas[a][off:off + ln] = c.praw[g, s - k, :ln]
-            if par_rows is not None:
+            if par_rows is not None and c.chosen[g, s - k]:
                 arenas[a][off:off + min(ln, P)] = par_rows[g, s - k, :min(ln, P)]
     lens = np.where(here, c.lens[:, :n], JUNK_LEN).astype(np.uint32)
     return arenas, where, lens
@@ -231,7 +249,8 @@ def check_recover(b, what=""):
     assert (whole[:GUARD] == 0x5A).all() and (whole[GUARD + c.slots.size:] == 0x5A).all(), what
     got = whole[GUARD:GUARD + c.slots.size].reshape(c.G, c.r, c.P)
     bad = np.nonzero((got != c.slots).any(axis=2))
-    assert np.array_equal(got, c.slots), (what, "first wrong (g, m):", bad[0][:4], bad[1][:4])
+    assert np.array_equal(got, c.slots), (what, "first wrong (g, m):", bad[0][:4], bad[1][:4],
+                                          us.mismatch(c.masks, c.k, c.r, got, c.slots))
     assert np.array_equal(b.st.cpu().numpy(), c.status), what
     assert np.array_equal(b.mo.cpu().numpy().view(np.uint64), c.masks), what
     assert np.array_equal(b.sym.cpu().numpy().view(np.uint32), c.sym_rec), what
@@ -494,7 +513,8 @@ def _contiguous(torch, oracle, k, r, P, G, seed):
     stream's workspace too."""
     from test_gpu_gather import make_case as fixed_case
     c = fixed_case(oracle, k, r, P, perm_masks(k, r, G, seed), seed + 1)
-    d = SimpleNamespace(c=c, dd=torch.from_numpy(np.array(c.broken)).to("cuda"), dp=torch.from_numpy(np.array(c.par)).to("cuda"),
+    d = SimpleNamespace(c=c, dd=torch.from_numpy(np.array(c.broken)).to("cuda"),
+                        dp=torch.from_numpy(np.array(c.par_in)).to("cuda"),
                         dm=torch.from_numpy(np.array(c.masks).view(np.int64)).to("cuda"),
                         st=torch.full((G,), 7, dtype=torch.uint8, device="cuda"))
     d.whole, d.out = guarded(torch, G * r * P, 0x5A)

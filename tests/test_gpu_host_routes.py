@@ -23,6 +23,8 @@ Which test reaches which route:
 import numpy as np
 import pytest
 
+import unread_shards as us
+
 pytestmark = pytest.mark.gpu
 
 K, R, P, G = 4, 2, 17, 7
@@ -36,20 +38,22 @@ NOTHING = np.array([0, 0, 0b110000, 0b010000, 0b000111, 0, 0b100011], dtype=np.u
 
 @pytest.fixture(scope="module")
 def case(oracle_mod):
-    """The data, its parity and, per mask set, the broken data and what the oracle makes of it."""
+    """The data, its parity and, per mask set, the decode's inputs (junk in every lost data shard and
+    every parity row the erasure rule does not read, tests/unread_shards.py) and what the oracle makes
+    of them."""
     data = oracle_mod.splitmix_bytes(G * K * P, 0x5EED0909)
     par = oracle_mod.rs_encode(data, G, K, R, P)
     out = {"data": data, "par": par}
     for name, masks in (("sparse", SPARSE), ("dense", DENSE), ("nothing", NOTHING)):
-        broken = data.copy().reshape(G, K, P)
-        for g in range(G):
-            for j in range(K):
-                if (int(masks[g]) >> j) & 1:
-                    broken[g, j] = 0xEE
-        broken = broken.reshape(-1)
+        # "nothing" rebuilds no group on purpose, so none has a chosen row to have a lost row below
+        broken, par_in = us.inputs(data, par, masks, K, R, P, 0x5EED0909, need_lost_below=name != "nothing")
         ref = broken.copy()
-        bad, st = oracle_mod.rs_decode(ref, par, masks, G, K, R, P)
-        out[name] = (masks, broken, ref, bad, st)
+        bad, st = oracle_mod.rs_decode(ref, par_in, masks, G, K, R, P)
+        ok = st == 0
+        assert np.array_equal(ref.reshape(G, -1)[ok], data.reshape(G, -1)[ok])
+        for a in (broken, par_in, ref):
+            a.setflags(write=False)
+        out[name] = (masks, broken, ref, bad, st, par_in)
     assert out["sparse"][3] == out["dense"][3] == out["nothing"][3] == 2
     return out
 
@@ -62,8 +66,8 @@ def _pinned(torch, a):
 def test_decode_one_buffer_on_the_device(gpu_ctx, torch_cuda, case, on_device):
     """One input on the device, the others and the statuses in pageable host memory: the staged route."""
     torch = torch_cuda
-    masks, broken, ref, bad_exp, st_exp = case["sparse"]
-    bufs = {"data": broken.copy(), "parity": case["par"].copy(), "masks": masks.copy(),
+    masks, broken, ref, bad_exp, st_exp, par_in = case["sparse"]
+    bufs = {"data": broken.copy(), "parity": par_in.copy(), "masks": masks.copy(),
             "status": np.full(G, 0xAA, dtype=np.uint8)}
     host = bufs[on_device]
     bufs[on_device] = torch.from_numpy(host.view(np.int64) if on_device == "masks" else host).cuda()
@@ -71,7 +75,8 @@ def test_decode_one_buffer_on_the_device(gpu_ctx, torch_cuda, case, on_device):
     got = {n: (b.cpu().numpy() if n == on_device else b) for n, b in bufs.items()}
     assert bad == bad_exp
     assert np.array_equal(got["status"], st_exp)
-    assert np.array_equal(got["data"], ref)
+    assert np.array_equal(got["data"], ref), us.mismatch(masks, K, R, got["data"], ref)
+    assert np.array_equal(got["parity"], par_in)
 
 
 @pytest.mark.parametrize("device", ["offsets", "data"])
@@ -99,10 +104,10 @@ def test_encode_offsets_and_data_on_different_sides(gpu_ctx, torch_cuda, case, d
 def test_decode_nothing_to_rebuild(gpu_ctx, torch_cuda, case, pinned):
     """No group has lost data it can rebuild (parity-only losses, unrecoverable groups): the host's
     scan of the masks is the whole answer, the data stays as it is."""
-    masks, broken, ref, bad_exp, st_exp = case["nothing"]
+    masks, broken, ref, bad_exp, st_exp, par_in = case["nothing"]
     assert np.array_equal(ref, broken)
     data = _pinned(torch_cuda, broken) if pinned else broken.copy()
-    par = _pinned(torch_cuda, case["par"]) if pinned else case["par"].copy()
+    par = _pinned(torch_cuda, par_in) if pinned else par_in.copy()
     st = np.full(G, 0xAA, dtype=np.uint8)
     assert gpu_ctx.decode(data, par, masks.copy(), K, R, P, status_out=st, num_groups=G) == bad_exp
     assert np.array_equal(st, st_exp)
@@ -127,11 +132,12 @@ def test_tiny_pipeline(gpu_ctx, torch_cuda, case, monkeypatch, pinned):
     gpu_ctx.encode(host(case["data"]), K, R, P, par, num_groups=G)
     assert np.array_equal(npy(par), case["par"])
     for name in ("dense", "sparse"):
-        masks, broken, ref, bad_exp, st_exp = case[name]
-        data, st = host(broken), np.full(G, 0xAA, dtype=np.uint8)
-        assert gpu_ctx.decode(data, par, masks.copy(), K, R, P, status_out=st, num_groups=G) == bad_exp, name
+        masks, broken, ref, bad_exp, st_exp, par_in = case[name]
+        data, hp, st = host(broken), host(par_in), np.full(G, 0xAA, dtype=np.uint8)
+        assert gpu_ctx.decode(data, hp, masks.copy(), K, R, P, status_out=st, num_groups=G) == bad_exp, name
         assert np.array_equal(st, st_exp), name
-        assert np.array_equal(npy(data), ref), name
+        assert np.array_equal(npy(data), ref), (name, us.mismatch(masks, K, R, npy(data), ref))
+        assert np.array_equal(npy(hp), par_in), name
 
 
 @pytest.mark.parametrize("small", ["0", None])

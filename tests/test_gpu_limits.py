@@ -7,6 +7,8 @@ but any packet_size through the C call (fec_xor_simd.h:68-75)."""
 import numpy as np
 import pytest
 
+import unread_shards as us
+
 pytestmark = pytest.mark.gpu
 
 SEED = 0x5EED4000
@@ -50,20 +52,21 @@ def test_decode_and_recover_extreme_shapes(gpu_ctx, oracle_mod, torch_cuda, k, r
     data = oracle_mod.splitmix_bytes(G * k * P, SEED + 5 + k + r)
     par = oracle_mod.rs_encode(data, G, k, r, P)
     masks = _masks_exact(rng, G, k, r, lost)
-    broken = data.copy().reshape(G, k, P)
-    for g in range(G):
-        for j in range(k):
-            if (int(masks[g]) >> j) & 1:
-                broken[g, j] = 0xEE
-    broken = broken.reshape(-1)
-    got = broken.copy()
+    if r > 1:       # group 0 planted: the lowest data shards and the lowest parity rows, so its rows lie above lost ones
+        e = min(k, lost - 1)
+        masks[0] = np.uint64(sum(1 << j for j in range(e)) | sum(1 << (k + i) for i in range(lost - e)))
+    # junk in every lost shard, parity rows included (tests/unread_shards.py); every group loses
+    # exactly r shards, so every surviving row is read and none is left unchosen
+    broken, par_in = us.inputs(data, par, masks, k, r, P, SEED + 5 + k + r, need_lost_below=r > 1, need_unchosen_alive=False)
+    got, hp = broken.copy(), par_in.copy()
     st = np.full(G, 0xAA, dtype=np.uint8)
-    assert gpu_ctx.decode(got, par, masks, k, r, P, status_out=st) == 0
-    assert np.array_equal(got, data) and not st.any()
+    assert gpu_ctx.decode(got, hp, masks, k, r, P, status_out=st) == 0
+    assert np.array_equal(got, data) and not st.any(), us.mismatch(masks, k, r, got, data)
+    assert np.array_equal(hp, par_in)
     # device-resident recover: group g's m-th lost data shard at (g*r + m)*P
     out = torch_cuda.full((G * r * P,), 0x5A, dtype=torch_cuda.uint8, device="cuda")
     dst = torch_cuda.full((G,), 0xAA, dtype=torch_cuda.uint8, device="cuda")
-    gpu_ctx.recover_dev(_dev(torch_cuda, broken), _dev(torch_cuda, par), _dev(torch_cuda, masks.view(np.int64)),
+    gpu_ctx.recover_dev(_dev(torch_cuda, broken), _dev(torch_cuda, par_in), _dev(torch_cuda, masks.view(np.int64)),
                         G, k, r, P, out, dst)
     gpu_ctx.synchronize()
     assert not dst.cpu().numpy().any()

@@ -1,11 +1,14 @@
 """fec_recover_batch_rs_dev_packed: the rebuilt packets of all groups back to back (the shape of
 decoder.go's Recovered list, :29-34), group g's rows starting at row_start[g] = the rows rebuilt
 for groups 0..g-1.  Bit-exact against the oracle, row starts against a host prefix sum, the
-total, statuses, `data` untouched; one wave per group and the sparse-loss scan form; prefix
+total, statuses, `data` untouched (inputs with junk in every shard the erasure rule does not read,
+tests/unread_shards.py); one wave per group and the sparse-loss scan form; prefix
 sums across many 1024-group scan blocks (both prefix forms), masks at an 8-B-aligned address;
 unsupported shapes refused."""
 import numpy as np
 import pytest
+
+import unread_shards as us
 
 pytestmark = pytest.mark.gpu
 
@@ -17,22 +20,24 @@ def _dev(torch, a):
 
 
 def _case(oracle_mod, k, r, P, G, masks):
+    """(data_in, par_in, statuses, row starts, rows): the inputs hold junk in every lost data shard
+    and every parity row the rule does not read; a lost row below a chosen one needs r > 1."""
     data = oracle_mod.splitmix_bytes(G * k * P, SEED + k * 31 + r * 7 + P)
     par = oracle_mod.rs_encode(data, G, k, r, P, nthreads=8)
-    lost = ((masks[:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-    broken = data.copy().reshape(G, k, P)
-    broken[lost] = 0xEE
-    ref = broken.copy().reshape(-1)
-    _, st_exp = oracle_mod.rs_decode(ref, par, masks, G, k, r, P, nthreads=8)
+    lost = us.roles(masks, k, r).lost_d
+    broken, par_in = us.inputs(data, par, masks, k, r, P, SEED + k * 31 + r * 7 + P + G, need_lost_below=r > 1)
+    ref = broken.copy()
+    _, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
     ok = st_exp == 0
+    assert np.array_equal(ref.reshape(G, k, P)[ok], data.reshape(G, k, P)[ok])
     rows = np.where(ok, lost.sum(axis=1), 0).astype(np.int64)
     start = np.concatenate([[0], np.cumsum(rows)[:-1]]).astype(np.uint32)
     exp = ref.reshape(G, k, P)[lost & ok[:, None]]          # (g, j ascending) order
-    return broken.reshape(-1), par, st_exp, start, exp
+    return broken, par_in, st_exp, start, exp
 
 
-def _run(gpu_ctx, torch, broken, par, masks, G, k, r, P):
-    dd, dp, dm = _dev(torch, broken), _dev(torch, par), _dev(torch, masks.view(np.int64))
+def _run(gpu_ctx, torch, broken, par_in, masks, G, k, r, P):
+    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
     out = torch.full((max(1, G * r) * P,), 0x5A, dtype=torch.uint8, device="cuda")
     rs = torch.full((max(1, G),), 0x7FFFFFFF, dtype=torch.int32, device="cuda")
     tot = torch.full((1,), -1, dtype=torch.int64, device="cuda")
@@ -51,8 +56,8 @@ def test_packed_rows_match_oracle(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
     for g in range(G):
         for s in rng.permutation(k + r)[: rng.integers(0, r + 2)]:
             masks[g] |= np.uint64(1) << np.uint64(int(s))
-    broken, par, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
-    dd, out, rs, tot, st = _run(gpu_ctx, torch_cuda, broken, par, masks, G, k, r, P)
+    broken, par_in, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
+    dd, out, rs, tot, st = _run(gpu_ctx, torch_cuda, broken, par_in, masks, G, k, r, P)
     n = len(exp)
     assert int(tot.item()) == n
     assert np.array_equal(rs.cpu().numpy().view(np.uint32), start)
@@ -81,8 +86,8 @@ def test_packed_rows_sparse_and_many_blocks(gpu_ctx, gpu_ctx_hooks, oracle_mod, 
     rng = np.random.default_rng(int(loss * 1000) + G)
     w = np.left_shift(np.uint64(1), np.arange(k + r, dtype=np.uint64))
     masks = ((rng.random((G, k + r)) < loss) * w).sum(axis=1, dtype=np.uint64)
-    broken, par, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
-    dd, out, rs, tot, st = _run(ctx, torch_cuda, broken, par, masks, G, k, r, P)
+    broken, par_in, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
+    dd, out, rs, tot, st = _run(ctx, torch_cuda, broken, par_in, masks, G, k, r, P)
     n = len(exp)
     assert int(tot.item()) == n
     assert np.array_equal(rs.cpu().numpy().view(np.uint32), start)
@@ -124,8 +129,8 @@ def test_packed_masks_at_odd_word(gpu_ctx, oracle_mod, torch_cuda):
     rng = np.random.default_rng(77)
     w = np.left_shift(np.uint64(1), np.arange(k + r, dtype=np.uint64))
     masks = ((rng.random((G, k + r)) < 0.1) * w).sum(axis=1, dtype=np.uint64)
-    broken, par, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
-    dd, dp = _dev(torch, broken), _dev(torch, par)
+    broken, par_in, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
+    dd, dp = _dev(torch, broken), _dev(torch, par_in)
     dm_all = _dev(torch, np.concatenate([[np.uint64(0)], masks]).view(np.int64))
     dm = dm_all[1:]
     out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
@@ -160,9 +165,9 @@ def test_chunked_launches(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypatch, ap
     for g in range(G):
         for sh in rng.permutation(k + r)[: rng.integers(0, r + 2)]:
             masks[g] |= np.uint64(1) << np.uint64(int(sh))
-    broken, par, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
+    broken, par_in, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
     if api.startswith("packed"):
-        dd, out, rs, tot, st = _run(gpu_ctx, torch, broken, par, masks, G, k, r, P)
+        dd, out, rs, tot, st = _run(gpu_ctx, torch, broken, par_in, masks, G, k, r, P)
         n = len(exp)
         assert int(tot.item()) == n
         assert np.array_equal(rs.cpu().numpy().view(np.uint32), start)
@@ -171,7 +176,7 @@ def test_chunked_launches(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypatch, ap
         assert (o[n:] == 0x5A).all()
         assert np.array_equal(st.cpu().numpy(), st_exp)
         return
-    dd, dp, dm = _dev(torch, broken), _dev(torch, par), _dev(torch, masks.view(np.int64))
+    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
     st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
     lost = ((masks[:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
     ok = st_exp == 0
@@ -181,7 +186,7 @@ def test_chunked_launches(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypatch, ap
         gpu_ctx.synchronize()
         o = out.cpu().numpy().reshape(G, r, P)
         ref = broken.copy().reshape(G, k, P)
-        oracle_mod.rs_decode(ref.reshape(-1), par, masks, G, k, r, P, nthreads=8)
+        oracle_mod.rs_decode(ref.reshape(-1), par_in, masks, G, k, r, P, nthreads=8)
         for g in np.nonzero(ok & lost.any(axis=1))[0]:
             ids = np.nonzero(lost[g])[0]
             assert np.array_equal(o[g, :len(ids)], ref[g, ids]), g
@@ -189,8 +194,8 @@ def test_chunked_launches(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypatch, ap
         gpu_ctx.decode_dev(dd, dp, dm, G, k, r, P, st)
         gpu_ctx.synchronize()
         ref = broken.copy()
-        oracle_mod.rs_decode(ref, par, masks, G, k, r, P, nthreads=8)
-        assert np.array_equal(dd.cpu().numpy(), ref)
+        oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
+        assert np.array_equal(dd.cpu().numpy(), ref), us.mismatch(masks, k, r, dd.cpu().numpy(), ref)
     assert np.array_equal(st.cpu().numpy(), st_exp)
 
 
@@ -221,6 +226,8 @@ def test_full_size_packed_recover(gpu_ctx, oracle_mod, torch_cuda, profile):
         bits = torch.arange(k, device="cuda", dtype=torch.int64)
         lost = ((dm.view(G, 1) >> bits.view(1, k)) & 1).bool()
         data.view(G, k, P)[lost] = 0xEE
+        prow = torch.arange(k, k + r, device="cuda", dtype=torch.int64)
+        par.view(G, r, P)[((dm.view(G, 1) >> prow.view(1, r)) & 1).bool()] = 0xEE     # lost parity rows hold no parity
         out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
         rs = torch.zeros(G, dtype=torch.int32, device="cuda")
         tot = torch.full((1,), -1, dtype=torch.int64, device="cuda")
@@ -263,8 +270,8 @@ def _iid_masks(rng, G, n, loss):
 
 
 def _check_packed(gpu_ctx, torch, oracle_mod, k, r, P, G, masks, out_offset=0):
-    broken, par, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
-    dd, dp, dm = _dev(torch, broken), _dev(torch, par), _dev(torch, masks.view(np.int64))
+    broken, par_in, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
+    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
     base = torch.full((max(1, G * r) * P + out_offset,), 0x5A, dtype=torch.uint8, device="cuda")
     out = base[out_offset:]
     rs = torch.full((max(1, G),), 0x7FFFFFFF, dtype=torch.int32, device="cuda")
@@ -280,7 +287,8 @@ def _check_packed(gpu_ctx, torch, oracle_mod, k, r, P, G, masks, out_offset=0):
     assert np.array_equal(o[:n], exp)
     assert (o[n:] == 0x5A).all()                                   # nothing past the last row
     assert (base[:out_offset].cpu().numpy() == 0x5A).all()        # nothing before the first
-    assert np.array_equal(dd.cpu().numpy(), broken)                # data untouched
+    assert np.array_equal(dd.cpu().numpy(), broken)                # data and parity untouched
+    assert np.array_equal(dp.cpu().numpy(), par_in)
 
 
 @pytest.mark.parametrize("k,r,P", [(10, 3, 1200), (10, 3, 700), (10, 3, 1400), (10, 3, 2000), (10, 3, 300),
@@ -335,13 +343,14 @@ def test_packed_runs_edges(gpu_ctx, gpu_ctx_hooks, oracle_mod, torch_cuda, monke
         monkeypatch.setenv("QUICFEC_PACKED_RUNS", "1")
         for G in range(1, 8):
             masks = _iid_masks(rng, G, k + r, 0.3)
+            masks[0] = 1 | 1 << k                   # planted: row 0 lost, row 1 chosen, row 2 survives unread
             _check_packed(gpu_ctx, torch, oracle_mod, k, r, P, G, masks)
         return
     else:
         monkeypatch.setenv("QUICFEC_PACKED_RUNS", "1")
         G = 4_096
         masks = np.zeros(G, dtype=np.uint64)
-        masks[::700] = np.uint64(0b101)                                 # 2 lost data shards
+        masks[::700] = np.uint64(0b101 | 1 << k)                        # 2 lost data shards and parity row 0
     try:
         _check_packed(gpu_ctx, torch, oracle_mod, k, r, P, G, masks, out_offset=off)
     finally:
@@ -360,8 +369,9 @@ def test_packed_runs_back_to_back(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeyp
     runs = []
     for G in (1_031, 60_000, 7, 60_000, 300):
         masks = _iid_masks(rng, G, k + r, 0.06)
-        broken, par, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
-        dd, dp, dm = _dev(torch, broken), _dev(torch, par), _dev(torch, masks.view(np.int64))
+        masks[0] = 1 | 1 << k                       # planted (7 groups draw none): row 0 lost, row 1 chosen, row 2 unread
+        broken, par_in, st_exp, start, exp = _case(oracle_mod, k, r, P, G, masks)
+        dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
         out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
         rs = torch.zeros(G, dtype=torch.int32, device="cuda")
         tot = torch.full((1,), -1, dtype=torch.int64, device="cuda")
@@ -400,6 +410,8 @@ def test_full_size_slot_recover(gpu_ctx, oracle_mod, torch_cuda, profile):
         bits = torch.arange(k, device="cuda", dtype=torch.int64)
         lost = ((dm.view(G, 1) >> bits.view(1, k)) & 1).bool()
         data.view(G, k, P)[lost] = 0xEE
+        prow = torch.arange(k, k + r, device="cuda", dtype=torch.int64)
+        par.view(G, r, P)[((dm.view(G, 1) >> prow.view(1, r)) & 1).bool()] = 0xEE     # lost parity rows hold no parity
         out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
         st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
         gpu_ctx.recover_dev(data, par, dm, G, k, r, P, out, st)

@@ -8,6 +8,8 @@ the size-independent encode -> erase -> decode round trip.
 import numpy as np
 import pytest
 
+import unread_shards as us
+
 pytestmark = pytest.mark.gpu
 
 SEED = 0x5EED0000
@@ -149,13 +151,13 @@ def _random_masks(rng, G, k, r, max_lost):
     return masks
 
 
-def _poison(data, masks, G, k, P):
-    d = data.copy().reshape(G, k, P)
-    for g in range(G):
-        for j in range(k):
-            if (int(masks[g]) >> j) & 1:
-                d[g, j, :] = 0xEE
-    return d.reshape(-1)
+def _junked(data, par, masks, G, k, r, P, **need):
+    """(data_in, par_in): what a decode is given, with seeded junk in every lost data shard and in
+    every parity row the erasure rule does not read (tests/unread_shards.py).  `par` stays the true
+    parity, for encode comparisons only.  A lost row below a chosen one needs r > 1."""
+    assert len(masks) == G
+    need.setdefault("need_lost_below", r > 1)
+    return us.inputs(data, par, masks, k, r, P, SEED + 13 * k + r + P, **need)
 
 
 @pytest.mark.parametrize("k,r,P", SHAPES + [(16, 16, 32), (32, 8, 48)])
@@ -166,26 +168,29 @@ def test_rs_decode_matches_oracle(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
     data = oracle_mod.splitmix_bytes(G * k * P, SEED + 77 + k + r + P)
     par = oracle_mod.rs_encode(data, G, k, r, P)
     masks = _random_masks(rng, G, k, r, r + 1)
-    broken = _poison(data, masks, G, k, P)
+    broken, par_in = _junked(data, par, masks, G, k, r, P)
     exp = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(exp, par, masks, G, k, r, P)
-    got = broken.copy()
+    bad_exp, st_exp = oracle_mod.rs_decode(exp, par_in, masks, G, k, r, P)
+    got, hp = broken.copy(), par_in.copy()
     st = np.zeros(G, dtype=np.uint8)
-    bad = gpu_ctx.decode(got, par, masks, k, r, P, status_out=st)
+    bad = gpu_ctx.decode(got, hp, masks, k, r, P, status_out=st)
     assert bad == bad_exp
     assert np.array_equal(st, st_exp)
-    assert np.array_equal(got, exp)
+    assert np.array_equal(got, exp), us.mismatch(masks, k, r, got, exp)
+    assert np.array_equal(hp, par_in)
     # device-resident API
-    dd, dpar, dm = _dev(torch_cuda, broken), _dev(torch_cuda, par), _dev(torch_cuda, masks.view(np.int64))
+    dd, dpar, dm = _dev(torch_cuda, broken), _dev(torch_cuda, par_in), _dev(torch_cuda, masks.view(np.int64))
     # 0xAA: every status byte must be written by the device (inline classify included)
     dst = torch_cuda.full((G,), 0xAA, dtype=torch_cuda.uint8, device="cuda")
     gpu_ctx.decode_dev(dd, dpar, dm, G, k, r, P, dst)
     gpu_ctx.synchronize()
-    assert np.array_equal(dd.cpu().numpy(), exp)
+    assert np.array_equal(dd.cpu().numpy(), exp), us.mismatch(masks, k, r, dd.cpu().numpy(), exp)
     assert np.array_equal(dst.cpu().numpy(), st_exp)
+    assert np.array_equal(dpar.cpu().numpy(), par_in)
 
 
 def test_gf_golden_fixtures(gpu_ctx, oracle_mod, manifest, gf_golden):
+    lost_below = 0
     for c in manifest["cases"]:
         if not c["name"].startswith("rs_"):
             continue
@@ -195,11 +200,20 @@ def test_gf_golden_fixtures(gpu_ctx, oracle_mod, manifest, gf_golden):
         gpu_ctx.encode(data, k, r, P, par, num_groups=G)
         assert np.array_equal(par, gf_golden[c["name"] + "_parity"]), c["name"]
         masks = gf_golden[c["name"] + "_masks"]
-        broken = _poison(data, masks, G, k, P)
+        # the committed masks of 4 to 16 groups: two of the four fixtures draw no lost row below a
+        # chosen one, so that is asserted of the fixtures together
+        broken, par_in = _junked(data, par, masks, G, k, r, P, need_lost_below=False)
+        lost_below += int(us.has_lost_row_below_chosen(us.roles(masks, k, r)).sum())
+        golden = gf_golden[c["name"] + "_decoded"].reshape(G, k, P)
+        ro = us.roles(masks, k, r)
+        # the committed result was made with 0xEE in lost shards: an unrecoverable group keeps them
+        broken.reshape(G, k, P)[ro.lost_d & ~ro.ok[:, None]] = 0xEE
+        assert (golden[ro.lost_d & ~ro.ok[:, None]] == 0xEE).all()
         st = np.zeros(G, dtype=np.uint8)
-        bad = gpu_ctx.decode(broken, par, masks, k, r, P, status_out=st)
+        bad = gpu_ctx.decode(broken, par_in.copy(), masks, k, r, P, status_out=st)
         assert bad == c["unrecoverable"]
-        assert np.array_equal(broken, gf_golden[c["name"] + "_decoded"]), c["name"]
+        assert np.array_equal(broken.reshape(G, k, P), golden), (c["name"], us.mismatch(masks, k, r, broken, golden))
+    assert lost_below >= 2
 
 
 def test_single_loss_is_reference_xor_recovery(gpu_ctx, oracle_mod):
@@ -210,8 +224,9 @@ def test_single_loss_is_reference_xor_recovery(gpu_ctx, oracle_mod):
     rng = np.random.default_rng(3)
     lost = rng.integers(0, k, size=G)
     masks = np.array([1 << int(j) for j in lost], dtype=np.uint64)
-    got = _poison(data, masks, G, k, P)
-    assert gpu_ctx.decode(got, par, masks, k, r, P) == 0
+    # no parity row is lost on purpose (the XOR row must be the chosen one); rows 1 and 2 are unread junk
+    got, par_in = _junked(data, par, masks, G, k, r, P, need_lost_below=False)
+    assert gpu_ctx.decode(got, par_in.copy(), masks, k, r, P) == 0
     for g in range(G):
         pk = [None if j == lost[g] else data[(g * k + j) * P:(g * k + j + 1) * P] for j in range(k)]
         mid, rec = oracle_mod.go_recover_single(pk, par[g * r * P:g * r * P + P], P)
@@ -238,20 +253,22 @@ def test_host_pipeline_multi_chunk(gpu_ctx, oracle_mod, torch_cuda, monkeypatch,
     assert np.array_equal(got, exp)
     rng = np.random.default_rng(12)
     masks = _random_masks(rng, G, k, r, r + 1)
-    broken = _poison(data, masks, G, k, P)
+    broken, par_in = _junked(data, exp, masks, G, k, r, P)
     ref = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, exp, masks, G, k, r, P, nthreads=8)
+    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
     if pinned:
         hb = torch_cuda.from_numpy(broken).pin_memory()
+        hp = torch_cuda.from_numpy(par_in.copy()).pin_memory()
         st = torch_cuda.zeros(G, dtype=torch_cuda.uint8).pin_memory()
-        bad = gpu_ctx.decode(hb, h_par, masks, k, r, P, status_out=st, num_groups=G)
-        hb, st = hb.numpy(), st.numpy()
+        bad = gpu_ctx.decode(hb, hp, masks, k, r, P, status_out=st, num_groups=G)
+        hb, hp, st = hb.numpy(), hp.numpy(), st.numpy()
     else:
-        hb, st = broken, np.zeros(G, dtype=np.uint8)
-        bad = gpu_ctx.decode(hb, exp, masks, k, r, P, status_out=st)
+        hb, hp, st = broken, par_in.copy(), np.zeros(G, dtype=np.uint8)
+        bad = gpu_ctx.decode(hb, hp, masks, k, r, P, status_out=st)
     assert bad == bad_exp
     assert np.array_equal(st, st_exp)
-    assert np.array_equal(hb, ref)
+    assert np.array_equal(hb, ref), us.mismatch(masks, k, r, hb, ref)
+    assert np.array_equal(hp, par_in)
 
 
 @pytest.mark.parametrize("k,r,P,pinned,dma", [(10, 3, 1200, True, True), (10, 3, 1200, True, False),
@@ -271,22 +288,23 @@ def test_host_decode_compacted_sparse_loss(gpu_ctx, oracle_mod, torch_cuda, monk
     masks = ((rng.random((G, k + r)) < 0.02) * w).sum(axis=1, dtype=np.uint64)
     masks[rng.integers(0, G, size=9)] = np.uint64((1 << (r + 1)) - 1)   # r+1 data shards lost
     masks[5] = np.uint64(0)
-    broken = _poison(data, masks, G, k, P)
+    broken, par_in = _junked(data, par, masks, G, k, r, P)
     ref = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, par, masks, G, k, r, P, nthreads=8)
+    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
     assert 0 < bad_exp and (st_exp == 0).sum() > 0
     if pinned:
         hb = torch_cuda.from_numpy(broken).pin_memory()
-        hp = torch_cuda.from_numpy(par).pin_memory()
+        hp = torch_cuda.from_numpy(par_in.copy()).pin_memory()
         st = np.zeros(G, dtype=np.uint8)
         bad = gpu_ctx.decode(hb, hp, masks, k, r, P, status_out=st, num_groups=G)
-        got = hb.numpy()
+        got, hp = hb.numpy(), hp.numpy()
     else:
-        got, st = broken.copy(), np.zeros(G, dtype=np.uint8)
-        bad = gpu_ctx.decode(got, par, masks, k, r, P, status_out=st)
+        got, hp, st = broken.copy(), par_in.copy(), np.zeros(G, dtype=np.uint8)
+        bad = gpu_ctx.decode(got, hp, masks, k, r, P, status_out=st)
     assert bad == bad_exp
     assert np.array_equal(st, st_exp)
-    assert np.array_equal(got, ref)
+    assert np.array_equal(got, ref), us.mismatch(masks, k, r, got, ref)
+    assert np.array_equal(hp, par_in)
 
 
 @pytest.mark.parametrize("devices", [None, [0, 0, 0]])
@@ -298,20 +316,21 @@ def test_device_group_shards_host_batches(quicfec_mod, oracle_mod, torch_cuda, d
     exp = oracle_mod.rs_encode(data, G, k, r, P, nthreads=8)
     rng = np.random.default_rng(31)
     masks = _random_masks(rng, G, k, r, r + 1)
-    broken = _poison(data, masks, G, k, P)
+    broken, par_in = _junked(data, exp, masks, G, k, r, P)
     ref = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, exp, masks, G, k, r, P, nthreads=8)
+    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
     with quicfec_mod.DeviceGroup(devices) as grp:
         assert len(grp) == (3 if devices else quicfec_mod.device_count())
         par = np.zeros(G * r * P, dtype=np.uint8)
         grp.encode(data, k, r, P, par)
         assert np.array_equal(par, exp)
-        h_par = torch_cuda.from_numpy(par).pin_memory()         # page-locked parity
+        h_par = torch_cuda.from_numpy(par_in.copy()).pin_memory()         # page-locked parity, junk where unread
         st = np.zeros(G, dtype=np.uint8)
         bad = grp.decode(broken, h_par, masks, k, r, P, status_out=st)
         assert bad == bad_exp
         assert np.array_equal(st, st_exp)
-        assert np.array_equal(broken, ref)
+        assert np.array_equal(broken, ref), us.mismatch(masks, k, r, broken, ref)
+        assert np.array_equal(h_par.numpy(), par_in)
         dd = torch_cuda.from_numpy(data).cuda()                  # device buffers are refused
         with pytest.raises(quicfec_mod.FecError) as ei:
             grp.encode(dd, k, r, P, par, num_groups=G)
@@ -381,6 +400,8 @@ def test_full_size_c2_c3_round_trip(gpu_ctx, oracle_mod, torch_cuda):
     bits = torch.arange(k, device="cuda", dtype=torch.int64)
     lost = ((dm.view(G, 1) >> bits.view(1, k)) & 1).bool()
     data.view(G, k, P)[lost] = 0xEE
+    rows = torch.arange(k, k + r, device="cuda", dtype=torch.int64)
+    par.view(G, r, P)[((dm.view(G, 1) >> rows.view(1, r)) & 1).bool()] = 0xEE       # lost parity rows hold no parity
     st = torch.zeros(G, dtype=torch.uint8, device="cuda")
     gpu_ctx.decode_dev(data, par, dm, G, k, r, P, st, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
@@ -409,6 +430,8 @@ def test_full_size_c4_shard_encode(gpu_ctx, oracle_mod, torch_cuda):
     bits = torch.arange(k, device="cuda", dtype=torch.int64)
     lost = ((dm.view(Gs, 1) >> bits.view(1, k)) & 1).bool()
     sub.view(Gs, k, P)[lost] = 0x11
+    rows = torch.arange(k, k + r, device="cuda", dtype=torch.int64)
+    par[:Gs * r * P].view(Gs, r, P)[((dm.view(Gs, 1) >> rows.view(1, r)) & 1).bool()] = 0x11   # lost parity rows too
     gpu_ctx.decode_dev(sub, par[:Gs * r * P], dm, Gs, k, r, P, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert torch.equal(sub, orig)
@@ -444,14 +467,14 @@ def test_any_packet_size_round_trip(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
     assert np.array_equal(par, exp_par)
     rng = np.random.default_rng(P * 31 + k)
     masks = _random_masks(rng, G, k, r, r + 1)
-    broken = _poison(data, masks, G, k, P)
+    broken, par_in = _junked(data, exp_par, masks, G, k, r, P)
     exp = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(exp, exp_par, masks, G, k, r, P)
+    bad_exp, st_exp = oracle_mod.rs_decode(exp, par_in, masks, G, k, r, P)
     got = broken.copy()
     st = np.zeros(G, dtype=np.uint8)
-    assert gpu_ctx.decode(got, exp_par, masks, k, r, P, status_out=st) == bad_exp
+    assert gpu_ctx.decode(got, par_in.copy(), masks, k, r, P, status_out=st) == bad_exp
     assert np.array_equal(st, st_exp)
-    assert np.array_equal(got, exp)
+    assert np.array_equal(got, exp), us.mismatch(masks, k, r, got, exp)
     # Device views at odd byte addresses (packet bases misaligned for every dword / 16-B access).
     for shift_d, shift_p in [(1, 3), (5, 15), (8, 0)]:
         bd = torch.zeros(G * k * P + 32, dtype=torch.uint8, device="cuda")
@@ -465,12 +488,14 @@ def test_any_packet_size_round_trip(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
         # guard bytes around the views untouched
         assert int(bp[:shift_p].sum().item()) == 0 and int(bp[shift_p + G * r * P:].sum().item()) == 0
         dd.copy_(torch.from_numpy(broken))
+        dp.copy_(torch.from_numpy(par_in))
         dm = _dev(torch, masks.view(np.int64))
         dst = torch.full((G,), 0xAA, dtype=torch.uint8, device="cuda")  # every byte written
         gpu_ctx.decode_dev(dd, dp, dm, G, k, r, P, dst)
         gpu_ctx.synchronize()
-        assert np.array_equal(dd.cpu().numpy(), exp), (shift_d, shift_p)
+        assert np.array_equal(dd.cpu().numpy(), exp), (shift_d, shift_p, us.mismatch(masks, k, r, dd.cpu().numpy(), exp))
         assert np.array_equal(dst.cpu().numpy(), st_exp)
+        assert np.array_equal(dp.cpu().numpy(), par_in)
         assert int(bd[:shift_d].sum().item()) == 0 and int(bd[shift_d + G * k * P:].sum().item()) == 0
 
 
@@ -534,15 +559,17 @@ def test_small_calls_zero_copy_and_dma(gpu_ctx, quicfec_mod, oracle_mod, xor_gol
         assert np.array_equal(npy(hp), exp), (k, r, P, G)
         rng = np.random.default_rng(G + P)
         masks = _random_masks(rng, G, k, r, r + 1)
-        masks[0] = np.uint64(1)  # at least one rebuilt group
-        broken = _poison(data, masks, G, k, P)
+        masks[0] = np.uint64(1 | 1 << k)  # at least one rebuilt group: from row 1, row 0 being lost
+        # one group of k=10 r=3 has a surviving unread row (2); k=4 r=2 finds one among its 40 groups
+        broken, par_in = _junked(data, exp, masks, G, k, r, P)
         ref = broken.copy()
-        bad_exp, st_exp = oracle_mod.rs_decode(ref, exp, masks, G, k, r, P)
-        hb = host(broken)
+        bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P)
+        hb, hp_in = host(broken), host(par_in)
         st = np.zeros(G, dtype=np.uint8)
-        assert gpu_ctx.decode(hb, hp, masks, k, r, P, status_out=st, num_groups=G) == bad_exp
+        assert gpu_ctx.decode(hb, hp_in, masks, k, r, P, status_out=st, num_groups=G) == bad_exp
         assert np.array_equal(st, st_exp)
-        assert np.array_equal(npy(hb), ref), (k, r, P, G)
+        assert np.array_equal(npy(hb), ref), (k, r, P, G, us.mismatch(masks, k, r, npy(hb), ref))
+        assert np.array_equal(npy(hp_in), par_in)
     # xor_packets_* (context-free entry point): ten host packets
     pk = [oracle_mod.splitmix_bytes(1200, 77 + i) for i in range(10)]
     out = np.zeros(1200, dtype=np.uint8)
@@ -578,10 +605,9 @@ def test_concurrent_decodes_on_two_streams(gpu_ctx, oracle_mod, torch_cuda, k, r
         rng = np.random.default_rng(100 + b)
         pos = np.argsort(rng.random((G, k + r)), axis=1)[:, :erasures].astype(np.uint64)
         masks = np.left_shift(np.uint64(1), pos).sum(axis=1, dtype=np.uint64)
-        lost = ((masks[:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-        broken = data.copy().reshape(G, k, P)
-        broken[lost] = 0xEE
-        batches.append((data, _dev(torch, broken.reshape(-1)), _dev(torch, par), _dev(torch, masks.view(np.int64))))
+        # a group that loses exactly r shards reads every surviving row: k=20 r=5 has no unread survivor
+        broken, par_in = _junked(data, par, masks, G, k, r, P, need_unchosen_alive=erasures < r)
+        batches.append((data, _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))))
     torch.cuda.synchronize()
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     sts = [torch.full((G,), 7, dtype=torch.uint8, device="cuda") for _ in range(2)]
@@ -626,16 +652,16 @@ def test_device_decode_scan_form(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypa
     w = np.left_shift(np.uint64(1), np.arange(k + r, dtype=np.uint64))
     masks = ((rng.random((G, k + r)) < loss) * w).sum(axis=1, dtype=np.uint64)
     masks[rng.integers(0, G, size=7)] = np.uint64(0xF)          # 4 data shards lost: unrecoverable
-    broken = _poison(data, masks, G, k, P)
+    broken, par_in = _junked(data, par, masks, G, k, r, P)
     ref = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, par, masks, G, k, r, P, nthreads=8)
-    dd, dp, dm = _dev(torch, broken), _dev(torch, par), _dev(torch, masks.view(np.int64))
+    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
+    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
     st = torch.full((G,), 0x55, dtype=torch.uint8, device="cuda")
     gpu_ctx.decode_dev(dd, dp, dm, G, k, r, P, st)
     gpu_ctx.synchronize()
     assert np.array_equal(st.cpu().numpy(), st_exp)
     assert int((st_exp != 0).sum()) == bad_exp
-    assert np.array_equal(dd.cpu().numpy(), ref)
+    assert np.array_equal(dd.cpu().numpy(), ref), us.mismatch(masks, k, r, dd.cpu().numpy(), ref)
 
 
 RECOVER_SHAPES = [(10, 3, 1200), (10, 3, 700), (10, 3, 1400), (20, 5, 1200), (20, 5, 96), (4, 2, 256), (7, 4, 48),
@@ -658,24 +684,24 @@ def test_recover_compact_output(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
     for g in range(G):
         for s in rng.permutation(k + r)[: rng.integers(0, r + 2)]:
             masks[g] |= np.uint64(1) << np.uint64(int(s))
-    lost = ((masks[:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-    broken = data.copy().reshape(G, k, P)
-    broken[lost] = 0xEE
-    ref = broken.copy().reshape(-1)
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, par, masks, G, k, r, P, nthreads=8)
+    lost = us.roles(masks, k, r).lost_d
+    broken, par_in = _junked(data, par, masks, G, k, r, P)
+    ref = broken.copy()
+    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
     exp = np.full((G, r, P), 0x5A, dtype=np.uint8)
     ref3 = ref.reshape(G, k, P)
     for g in np.nonzero(st_exp == 0)[0]:
         for m, j in enumerate(np.nonzero(lost[g])[0]):
             exp[g, m] = ref3[g, j]
-    dd, dp, dm = _dev(torch, broken.reshape(-1)), _dev(torch, par), _dev(torch, masks.view(np.int64))
+    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
     out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
     st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
     gpu_ctx.recover_dev(dd, dp, dm, G, k, r, P, out, st)
     gpu_ctx.synchronize()
     assert np.array_equal(st.cpu().numpy(), st_exp)
-    assert np.array_equal(out.cpu().numpy().reshape(G, r, P), exp)
-    assert np.array_equal(dd.cpu().numpy(), broken.reshape(-1))     # data untouched
+    assert np.array_equal(out.cpu().numpy().reshape(G, r, P), exp), us.mismatch(masks, k, r, out.cpu().numpy(), exp)
+    assert np.array_equal(dd.cpu().numpy(), broken)                 # data and parity untouched
+    assert np.array_equal(dp.cpu().numpy(), par_in)
 
 
 @pytest.mark.parametrize("loss,P", [(0.01, 1200), (0.3, 1400)])
@@ -691,20 +717,23 @@ def test_recover_scan_form(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypatch, l
     rng = np.random.default_rng(int(loss * 100) + P)
     w = np.left_shift(np.uint64(1), np.arange(k + r, dtype=np.uint64))
     masks = ((rng.random((G, k + r)) < loss) * w).sum(axis=1, dtype=np.uint64)
-    lost = ((masks[:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-    _, st_exp = oracle_mod.rs_decode(_poison(data, masks, G, k, P), par, masks, G, k, r, P, nthreads=8)
+    lost = us.roles(masks, k, r).lost_d
+    broken, par_in = _junked(data, par, masks, G, k, r, P)
+    ref = broken.copy()
+    _, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
+    assert np.array_equal(ref.reshape(G, k, P)[st_exp == 0], data.reshape(G, k, P)[st_exp == 0])
     exp = np.full((G, r, P), 0x5A, dtype=np.uint8)
     d3 = data.reshape(G, k, P)
     for g in np.nonzero(st_exp == 0)[0]:
         for m, j in enumerate(np.nonzero(lost[g])[0]):
             exp[g, m] = d3[g, j]
-    dd, dp, dm = _dev(torch, data), _dev(torch, par), _dev(torch, masks.view(np.int64))
+    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
     out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
     st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
     gpu_ctx.recover_dev(dd, dp, dm, G, k, r, P, out, st)
     gpu_ctx.synchronize()
     assert np.array_equal(st.cpu().numpy(), st_exp)
-    assert np.array_equal(out.cpu().numpy().reshape(G, r, P), exp)
+    assert np.array_equal(out.cpu().numpy().reshape(G, r, P), exp), us.mismatch(masks, k, r, out.cpu().numpy(), exp)
 
 
 @pytest.mark.parametrize("k,r", [(6, 3), (12, 4), (10, 2)])   # record-addressed, and one mask-addressed
@@ -717,7 +746,6 @@ def test_recover_back_to_back_on_one_stream(gpu_ctx, oracle_mod, torch_cuda, k, 
     G, P, calls = 1500, 1200, 12
     data = oracle_mod.splitmix_bytes(G * k * P, SEED + 71 + k + r)
     par = oracle_mod.rs_encode(data, G, k, r, P, nthreads=8)
-    dd, dp = _dev(torch, data), _dev(torch, par)
     rng = np.random.default_rng(k + r)
     runs = []
     stream = torch.cuda.Stream()
@@ -727,10 +755,11 @@ def test_recover_back_to_back_on_one_stream(gpu_ctx, oracle_mod, torch_cuda, k, 
             for g in range(G):
                 for s in rng.permutation(k + r)[: rng.integers(1, r + 1)]:
                     masks[g] |= np.uint64(1) << np.uint64(int(s))
-            dm = _dev(torch, masks.view(np.int64))
+            broken, par_in = _junked(data, par, masks, G, k, r, P)       # each call its own junked inputs
+            dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
             out = torch.zeros(G * r * P, dtype=torch.uint8, device="cuda")
             gpu_ctx.recover_dev(dd, dp, dm, G, k, r, P, out, None, stream=stream.cuda_stream)
-            runs.append((masks, dm, out))
+            runs.append((masks, (dd, dp, dm), out))
     stream.synchronize()
     d3 = data.reshape(G, k, P)
     for masks, _, out in runs:

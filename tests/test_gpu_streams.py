@@ -6,8 +6,9 @@ host synchronise after each call.  Here calls are queued on side streams (non-bl
 nothing orders them against torch's default stream) with no host synchronise until the end, from
 several streams and host threads of one context, and everything every call wrote is compared with
 the oracle afterwards: rebuilt bytes, statuses, row starts, totals, `data` untouched by the recover
-calls, 0x5A wherever nothing may be written (slots m >= e, everything past the last packed row),
-7 in statuses never written.
+calls, the inputs of the recover calls as they were (seeded junk in every shard the erasure rule
+does not read, tests/unread_shards.py), 0x5A wherever nothing may be written (slots m >= e,
+everything past the last packed row), 7 in statuses never written.
 
 Each test makes its own quicfec.Context, so no plan, workspace or epoch of another test is there
 when it starts.  Expected bytes come from the oracle, once per shape (`_case`); a call of fewer
@@ -25,6 +26,8 @@ from types import SimpleNamespace
 
 import numpy as np
 import pytest
+
+import unread_shards as us
 
 pytestmark = pytest.mark.gpu
 
@@ -78,14 +81,14 @@ class Case:
         G = len(masks)
         self.k, self.r, self.P, self.G, self.masks, self.seed = k, r, P, G, masks, seed
         data = oracle.splitmix_bytes(G * k * P, seed)
-        self.par = oracle.rs_encode(data, G, k, r, P, nthreads=8)
-        lost = ((masks[:, None] >> np.arange(k, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
-        broken = data.reshape(G, k, P).copy()
-        broken[lost] = 0xEE
+        self.par = oracle.rs_encode(data, G, k, r, P, nthreads=8)          # true: what an encode must give
+        lost = us.roles(masks, k, r).lost_d
         self.data = data
-        self.broken = broken.reshape(-1)
+        # what a decode is given: junk in every lost data shard and every parity row the rule does
+        # not read (every shape here has r > 1, so every case has a lost row below a chosen one)
+        self.broken, self.par_in = us.inputs(data, self.par, masks, k, r, P, seed)
         ref = self.broken.copy()
-        _, self.status = oracle.rs_decode(ref, self.par, masks, G, k, r, P, nthreads=8)
+        _, self.status = oracle.rs_decode(ref, self.par_in, masks, G, k, r, P, nthreads=8)
         self.ref = ref                                    # in-place result
         ok = self.status == 0
         # the oracle's rebuilt packets are the original ones
@@ -98,8 +101,8 @@ class Case:
         per_group = (lost & ok[:, None]).sum(axis=1)
         self.row_end = np.cumsum(per_group)
         self.row_start = np.concatenate([[0], self.row_end[:-1]]).astype(np.uint32)
-        for a in (self.data, self.par, self.broken, self.ref, self.status, self.rows, self.slots, self.row_start,
-                  self.masks):
+        for a in (self.data, self.par, self.par_in, self.broken, self.ref, self.status, self.rows, self.slots,
+                  self.row_start, self.masks):
             a.setflags(write=False)
 
     def head(self, G):
@@ -111,7 +114,8 @@ class Case:
         k, r, P = self.k, self.r, self.P
         n = int(self.row_end[G - 1])
         return SimpleNamespace(k=k, r=r, P=P, G=G, seed=self.seed, masks=self.masks[:G], data=self.data[:G * k * P],
-                               par=self.par[:G * r * P], broken=self.broken[:G * k * P], ref=self.ref[:G * k * P],
+                               par=self.par[:G * r * P], par_in=self.par_in[:G * r * P], broken=self.broken[:G * k * P],
+                               ref=self.ref[:G * k * P],
                                status=self.status[:G], rows=self.rows[:n], slots=self.slots[:G],
                                row_start=self.row_start[:G])
 
@@ -157,8 +161,8 @@ def _dev(torch, a):
 
 
 def upload(torch, c):
-    """Fresh device copies of a case's inputs (lost shards 0xEE)."""
-    return _dev(torch, c.broken), _dev(torch, c.par), _dev(torch, c.masks.view(np.int64))
+    """Fresh device copies of a case's inputs (junk in every shard the rule does not read)."""
+    return _dev(torch, c.broken), _dev(torch, c.par_in), _dev(torch, c.masks.view(np.int64))
 
 
 def make_call(torch, c, api, inputs=None, env=None):
@@ -197,9 +201,9 @@ def launch(ctx, b, stream, monkeypatch=None):
 
 
 def check_inputs(c, dd, dp, dm):
-    """The recover calls only read: data (lost shards still 0xEE), parity and masks unchanged."""
+    """The recover calls only read: data, parity (the junk of both included) and masks unchanged."""
     assert np.array_equal(dd.cpu().numpy()[:c.G * c.k * c.P], c.broken)
-    assert np.array_equal(dp.cpu().numpy()[:c.G * c.r * c.P], c.par)
+    assert np.array_equal(dp.cpu().numpy()[:c.G * c.r * c.P], c.par_in)
     assert np.array_equal(dm.cpu().numpy().view(np.uint64)[:c.G], c.masks)
 
 
@@ -209,10 +213,11 @@ def check(b, what=""):
     k, r, P, G = c.k, c.r, c.P, c.G
     assert np.array_equal(b.st.cpu().numpy(), c.status), what
     if b.api == "in_place":
-        assert np.array_equal(b.dd.cpu().numpy(), c.ref), what
-        assert np.array_equal(b.dp.cpu().numpy(), c.par), what
+        assert np.array_equal(b.dd.cpu().numpy(), c.ref), (what, us.mismatch(c.masks, k, r, b.dd.cpu().numpy(), c.ref))
+        assert np.array_equal(b.dp.cpu().numpy(), c.par_in), what
     elif b.api == "slots":
-        assert np.array_equal(b.out.cpu().numpy().reshape(G, r, P), c.slots), what     # slots m >= e still 0x5A
+        assert np.array_equal(b.out.cpu().numpy().reshape(G, r, P), c.slots), \
+            (what, us.mismatch(c.masks, k, r, b.out.cpu().numpy(), c.slots))              # slots m >= e still 0x5A
     else:
         n = len(c.rows)
         assert int(b.tot.item()) == n, what
@@ -467,7 +472,8 @@ def test_four_threads_on_one_context(quicfec_mod, oracle_mod, torch_cuda):
 # ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("k,r,P,G", [(10, 3, 1200, 1031), (20, 5, 1200, 1031), (6, 3, 48, 1031), (16, 16, 32, 131)])
 def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda, k, r, P, G):
-    """fill -> encode -> lost shards overwritten (a torch op) -> masks copied in (a torch copy) ->
+    """fill -> encode -> every shard the rule does not read overwritten with the case's junk (a
+    torch op) -> masks copied in (a torch copy) ->
     the decode calls, all queued on one non-blocking side stream with one synchronise at the end.
     Nothing but stream order makes a call see its producer's bytes: before the chain runs the data
     is 0x11, the parity 0x5A and the masks say "every shard lost".  The data are the oracle's
@@ -478,8 +484,9 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda, k, 
     c = _case(oracle_mod, k, r, P, G)
     sparse = (k, r) == (16, 16)
     packed_ok = (k, r) == (10, 3)                                      # the other shapes: refused, nothing written
-    lost = (c.masks[:, None] >> np.arange(k + r, dtype=np.uint64)[None, :]) & np.uint64(1)
-    d_lost = _dev(torch, lost.astype(bool))
+    ro = us.roles(c.masks, k, r)
+    d_junk_d, d_junk_p = _dev(torch, ro.lost_d), _dev(torch, ro.unread_p)       # which shards get junk
+    d_broken, d_par_in = _dev(torch, c.broken).view(G, k, P), _dev(torch, c.par_in).view(G, r, P)   # where it comes from
     d_masks_src = _dev(torch, c.masks.view(np.int64))
     dd = torch.full((G * k * P,), 0x11, dtype=torch.uint8, device="cuda")
     par = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
@@ -495,8 +502,8 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda, k, 
         ctx.encode_dev(dd, G, k, r, P, par, stream=s)
         with torch.cuda.stream(stream):
             par_made = par.clone()
-            dd.view(G, k, P).masked_fill_(d_lost[:, :k, None], 0xEE)
-            par.view(G, r, P).masked_fill_(d_lost[:, k:, None], 0xEE)
+            dd.view(G, k, P).copy_(torch.where(d_junk_d[:, :, None], d_broken, dd.view(G, k, P)))     # no host wait
+            par.view(G, r, P).copy_(torch.where(d_junk_p[:, :, None], d_par_in, par.view(G, r, P)))
             dm.copy_(d_masks_src, non_blocking=True)
         if not sparse:
             launch(ctx, slots, stream)
@@ -514,9 +521,7 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda, k, 
     assert np.array_equal(dm.cpu().numpy().view(np.uint64), c.masks)
     assert np.array_equal(st.cpu().numpy(), c.status)
     assert np.array_equal(dd.cpu().numpy(), c.ref)
-    plost = lost[:, k:].astype(bool)
-    got_par = par.cpu().numpy().reshape(G, r, P)
-    assert (got_par[plost] == 0xEE).all() and np.array_equal(got_par[~plost], c.par.reshape(G, r, P)[~plost])
+    assert np.array_equal(par.cpu().numpy(), c.par_in)                 # chosen rows as encoded, the rest junk still
     if not sparse:
         assert np.array_equal(broken_seen.cpu().numpy(), c.broken)
         check(slots)

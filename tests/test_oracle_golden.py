@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 from hypothesis import given, settings, strategies as st
 
+import unread_shards
+
 
 def _groups(data, G, k, P):
     return [[data[(g * k + j) * P:(g * k + j + 1) * P] for j in range(k)] for g in range(G)]
@@ -119,6 +121,7 @@ def test_parity_matrix_fixture(oracle_mod, golden_dir):
 
 
 def test_gf_fixtures(oracle_mod, manifest, gf_golden):
+    lost_below = 0
     for c in manifest["cases"]:
         if not c["name"].startswith("rs_"):
             continue
@@ -133,13 +136,19 @@ def test_gf_fixtures(oracle_mod, manifest, gf_golden):
                 if (int(masks[g]) >> j) & 1:
                     broken[g, j, :] = 0xEE
         broken = broken.reshape(-1)
-        bad, st = oracle_mod.rs_decode(broken, par, masks, G, k, r, P)
+        # junk in every parity row the rule does not read (tests/unread_shards.py): the same result.
+        # Two of the four committed mask sets (4 to 16 groups) draw no lost row below a chosen one,
+        # so that is asserted of the fixtures together.
+        _, par_in = unread_shards.inputs(data, par, masks, k, r, P, c["seed"], need_lost_below=False)
+        lost_below += int(unread_shards.has_lost_row_below_chosen(unread_shards.roles(masks, k, r)).sum())
+        bad, st = oracle_mod.rs_decode(broken, par_in, masks, G, k, r, P)
         assert np.array_equal(broken, gf_golden[c["name"] + "_decoded"])
         assert np.array_equal(st, gf_golden[c["name"] + "_status"])
         assert bad == c["unrecoverable"]
         # every recoverable group is restored exactly
         ok = st == 0
         assert np.array_equal(broken.reshape(G, -1)[ok], data.reshape(G, -1)[ok])
+    assert lost_below >= 2
 
 
 def test_gf_field_axioms(oracle_mod):
