@@ -78,7 +78,10 @@ int fec_encode_batch_rs(FECEncoderCtx* ctx, const uint8_t* data, const uint64_t*
                         uint64_t num_groups, uint32_t k, uint32_t r, uint32_t packet_size,
                         uint8_t* parity_out);
 
-/* status_out (nullable): one byte per group, 0 = recovered or nothing lost,
+/* erasure_masks: one u64 per group.  Bit j < k set: data shard j is lost.  Bit k + i set (i < r):
+ * parity row i is lost.  Bits at and above k + r are ignored: a caller need not clear them.  The
+ * masks are only read.
+ * status_out (nullable): one byte per group, 0 = recovered or nothing lost,
  * 1 = unrecoverable.  unrecoverable_out (nullable): count of status 1. */
 int fec_decode_batch_rs(FECEncoderCtx* ctx, uint8_t* data, const uint8_t* parity,
                         const uint64_t* erasure_masks, uint64_t num_groups, uint32_t k,
@@ -96,7 +99,8 @@ int fec_encode_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, uint64_t 
                             uint32_t k, uint32_t r, uint32_t packet_size, uint8_t* d_parity,
                             void* stream);
 
-/* d_status (nullable) as status_out above, written on the device. */
+/* d_erasure_masks: the bits as fec_decode_batch_rs reads them, bits at and above k + r ignored.
+ * d_status (nullable) as status_out above, written on the device. */
 int fec_decode_batch_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
                             const uint64_t* d_erasure_masks, uint64_t num_groups, uint32_t k,
                             uint32_t r, uint32_t packet_size, uint8_t* d_status, void* stream);
@@ -108,7 +112,8 @@ int fec_decode_batch_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* 
  * consumes them the same way.  d_rebuilt holds num_groups*r*P bytes; slots m >= e of a
  * group, and all slots of an unrecoverable group, are left unwritten.  Writing the rebuilt
  * packets back to back (the write pattern of encode's parity rows) instead of scattered
- * among the data shards measured 2.32 vs 2.47 ms at k=10 r=3, 2 erasures, 1M groups. */
+ * among the data shards measured 2.32 vs 2.47 ms at k=10 r=3, 2 erasures, 1M groups.
+ * d_erasure_masks: the bits as fec_decode_batch_rs reads them. */
 int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
                              const uint64_t* d_erasure_masks, uint64_t num_groups, uint32_t k, uint32_t r,
                              uint32_t packet_size, uint8_t* d_rebuilt, uint8_t* d_status, void* stream);
@@ -135,7 +140,8 @@ int fec_decode_prepare(FECEncoderCtx* ctx, uint32_t k, uint32_t r, uint64_t* byt
  * only (k + r with an inline-classify form, r <= 3: k=10 with r = 1, 2, 3 and k=4 r=2), at
  * 256 < P <= 2047 (2048 has no inline-classify form); k=10 r=2, which has no tiled form for
  * short packets, also at 16 <= P <= 256.  Every other shape or size returns FEC_ERR_RANGE with
- * nothing written.  Asynchronous on `stream` like the call above. */
+ * nothing written.  Asynchronous on `stream` like the call above.  d_masks: the bits as
+ * fec_decode_batch_rs reads them. */
 int fec_recover_batch_rs_dev_packed(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
                                     const uint64_t* d_masks, uint64_t num_groups, uint32_t k, uint32_t r,
                                     uint32_t packet_size, uint8_t* d_rebuilt, uint32_t* d_row_start,

@@ -7,7 +7,8 @@
 // The mask-addressed forms do NOT call fec_mask.hpp: fused_group keeps its own hand-written
 // statement of the rule, because every call into the header that was tried changed their
 // instructions (profiles/mask_rule/VERDICT.md).  They share ChooseSmall, low_bits(K) and
-// piece_load only, and only the GPU every-mask tests check their copy.
+// piece_load only, and only the GPU tests check their copy: test_every_mask (tests/test_gpu_forms.py), clean
+// and with junk in the bits at and above k + r, and the decode cases, whose masks all carry such junk.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -79,7 +80,8 @@ __device__ __forceinline__ void fused_group(uint64_t gw, uint64_t m, uint32_t la
   constexpr int NW = 4 * NM + NT;  // dwords per lane and survivor
   // (the classify, the ranks and the pick below restate fec_mask.hpp's mask_losses, mask_record and
   // mask_pick by hand: calling them, colex_rank alone, or low_bits(r) for the rows' mask, moves all
-  // 90 mask-addressed decode_fused instantiations.  Not checked on the CPU.)
+  // 90 mask-addressed decode_fused instantiations.  Not checked on the CPU: `& kmask` and both `& rmask`
+  // are held by the GPU cases' junk in the mask bits at and above k + r, tests/unread_shards.py high_bits.)
   constexpr uint64_t kmask = low_bits(K);
   uint64_t rec_byte_off;
   if constexpr (INLINE) {

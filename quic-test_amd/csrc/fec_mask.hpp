@@ -21,8 +21,10 @@
 // forms, fec_runs.hip recover_runs) keep their own hand-written statement of this rule, with compile-time K and
 // their own guards, because calling these functions changes their instructions
 // (profiles/mask_rule/VERDICT.md); they take only low_bits(K) and ChooseSmall from here.  A change
-// to the rule has to be made there too, and only the GPU every-mask tests (tests/test_gpu_forms.py)
-// check their copy.
+// to the rule has to be made there too, and only the GPU tests check their copy: the every-mask
+// test (tests/test_gpu_forms.py test_every_mask: every mask with the bits at and above k + r clean,
+// all set, only bit k + r set, and drawn) and the decode cases, whose masks all carry junk in those
+// bits (tests/unread_shards.py high_bits; its wrong readers on the CPU show what that junk catches).
 #pragma once
 
 #include <cstdint>

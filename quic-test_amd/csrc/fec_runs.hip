@@ -53,7 +53,10 @@ constexpr uint32_t kRunEpochShift = 34;
 // finds the record, runs_compute forms the rows.  Same survivor choice, record and arithmetic as
 // fused_group's DIRECT + INLINE path (the rule of fec_mask.hpp).
 // (one function for both stages moves all 36 recover_runs instantiations, and so does colex_rank
-// or for_each_chosen in place of the loops below: two stages, the rule restated by hand)
+// or for_each_chosen in place of the loops below: two stages, the rule restated by hand.  Not
+// checked on the CPU: the GPU tests check this copy, tests/test_gpu_forms.py test_every_mask clean
+// and with junk in the mask bits at and above k + r, and the packed cases, whose masks all carry
+// such junk -- that is what holds `& kmask` and `& rmask` here and in the kernel's classify)
 struct RunMeta {
   const Tab* tabs;
   uint32_t e;

@@ -7,7 +7,9 @@ Contexts are product-library contexts switched to FEC_PLAN_DEVICE unless a test 
 trace or a switch.  The table-recover cases, arenas, guards and checks are those of
 test_gpu_gather.py, test_gpu_gather_var.py, test_gpu_scatter.py and test_gpu_address_limits.py,
 taken by import (0xEE arenas, 0x5A outputs between guard bytes, 7 in the statuses); the contiguous
-calls' are test_gpu_streams.py's, with the statuses pre-filled 0xAA.  Every case is G = 67 (more
+calls' are test_gpu_streams.py's, with the statuses pre-filled 0xAA and, like them, masks with junk
+in the bits at and above k + r (12+12, 20+7 and 16+16 have such bits, and build_records reads the
+masks on the device; the table recovers derive their masks from the tables).  Every case is G = 67 (more
 than one workgroup of four waves, no multiple of 4) or G = 131.
 """
 import os
@@ -286,7 +288,7 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda):
     ro = us.roles(c.masks, k, r)
     d_junk_d, d_junk_p = st._dev(torch, ro.lost_d), st._dev(torch, ro.unread_p)
     d_broken, d_par_in = st._dev(torch, c.broken).view(G, k, P), st._dev(torch, c.par_in).view(G, r, P)
-    d_masks_src = st._dev(torch, c.masks.view(np.int64))
+    d_masks_src = st._dev(torch, c.masks_in.view(np.int64))        # junk in the bits at and above k + r = 32
     dd = torch.full((G * k * P,), 0x11, dtype=torch.uint8, device="cuda")
     par = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
     dm = torch.full((G,), -1, dtype=torch.int64, device="cuda")
@@ -318,7 +320,7 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda):
         torch.cuda.synchronize()
     assert still_busy
     st.check(warm)
-    assert np.array_equal(dm.cpu().numpy().view(np.uint64), c.masks)
+    assert np.array_equal(dm.cpu().numpy().view(np.uint64), c.masks_in)
     assert np.array_equal(broken_seen.cpu().numpy(), c.broken)
     st.check(slots)
     assert np.array_equal(status.cpu().numpy(), c.status)

@@ -4,9 +4,8 @@ Every other GPU test checks the bytes a call produced; a call that quietly fell 
 correct form would pass them all.  These run through libfec_hip_test.so (gpu_ctx_hooks), whose
 launchers record every kernel launch (csrc/fec_knobs.hpp LaunchRecord, quicfec.launch_trace), and
 check two things per case: the bytes, statuses, row starts and totals against the oracle (seeded junk in
-every shard the erasure rule does not read -- tests/unread_shards.py -- 0x5A in unwritten output,
-7 in unwritten status), and the launches against the table
-below.
+every shard and in every mask bit the erasure rule does not read -- tests/unread_shards.py -- 0x5A in
+unwritten output, 7 in unwritten status), and the launches against the table below.
 
 The table (expected_decode / expected_encode) is written from the dispatch rules as documented --
 DESIGN.md §5b, include/fec_hip.h and the comments of the lists and rules in csrc/fec_forms.hpp
@@ -240,9 +239,18 @@ def perm_masks(k, r, G, seed):
 class Case:
     """One batch and everything the oracle says about it, computed once and never modified."""
 
-    def __init__(self, oracle, k, r, P, masks, need_unchosen_alive=True):
+    def __init__(self, oracle, k, r, P, masks, need_unchosen_alive=True, need_full=True, need_short=True,
+                 need_untouched=True, masks_in=None):
         G = len(masks)
         self.k, self.r, self.P, self.G, self.masks = k, r, P, G, masks
+        # what a decode is given as masks: junk in the bits at and above k + r, which the rule ignores
+        # (masks_in given: the caller's own pattern up there)
+        if masks_in is None:
+            masks_in = us.high_bits(masks, k, r, SEED + k * 31 + r * 7 + P, need_full=need_full, need_short=need_short,
+                                    need_untouched=need_untouched)
+        low = np.uint64((1 << (k + r)) - 1)
+        assert masks_in.dtype == np.uint64 and np.array_equal(masks_in & low, masks)
+        self.masks_in = masks_in
         data = oracle.splitmix_bytes(G * k * P, SEED + k * 31 + r * 7 + P)
         self.par = oracle.rs_encode(data, G, k, r, P, nthreads=8)          # true: what an encode must give
         lost = us.roles(masks, k, r).lost_d
@@ -251,8 +259,11 @@ class Case:
         self.broken, self.par_in = us.inputs(data, self.par, masks, k, r, P, SEED + k * 31 + r * 7 + P,
                                              need_lost_below=r > 1, need_unchosen_alive=need_unchosen_alive)
         ref = self.broken.copy()
-        _, self.status = oracle.rs_decode(ref, self.par_in, masks, G, k, r, P, nthreads=8)
+        _, self.status = oracle.rs_decode(ref, self.par_in, masks_in, G, k, r, P, nthreads=8)
         self.ref = ref                                    # in-place result
+        clean = self.broken.copy()                        # the oracle itself ignores those bits
+        _, clean_status = oracle.rs_decode(clean, self.par_in, masks, G, k, r, P, nthreads=8)
+        assert np.array_equal(clean, ref) and np.array_equal(clean_status, self.status)
         ok = self.status == 0
         # the oracle's rebuilt packets are the original ones
         assert np.array_equal(ref.reshape(G, k, P)[ok], data.reshape(G, k, P)[ok])
@@ -263,7 +274,8 @@ class Case:
         self.slots[gi, mi] = self.rows
         per_group = (lost & ok[:, None]).sum(axis=1)
         self.row_start = np.concatenate([[0], np.cumsum(per_group)[:-1]]).astype(np.uint32)
-        for a in (self.par, self.par_in, self.broken, self.ref, self.status, self.rows, self.slots, self.row_start, self.masks):
+        for a in (self.par, self.par_in, self.broken, self.ref, self.status, self.rows, self.slots, self.row_start, self.masks,
+                  self.masks_in):
             a.setflags(write=False)
 
 
@@ -276,7 +288,7 @@ def run_decode(ctx, quicfec, torch, c, api, expected):
     """One decode call of `api` on case c: bytes against the oracle, launches against `expected`
     (None: the call must be refused with FEC_ERR_RANGE and touch nothing)."""
     k, r, P, G = c.k, c.r, c.P, c.G
-    dd, dp, dm = _dev(torch, c.broken), _dev(torch, c.par_in), _dev(torch, c.masks.view(np.int64))
+    dd, dp, dm = _dev(torch, c.broken), _dev(torch, c.par_in), _dev(torch, c.masks_in.view(np.int64))
     st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
     ctx.synchronize()
     quicfec.launch_trace(ctx.lib)                          # clear
@@ -305,6 +317,7 @@ def run_decode(ctx, quicfec, torch, c, api, expected):
             assert bool((out == 0x5A).all()) and bool((rs == 0x3C3C3C3C).all()) and int(tot.item()) == -5
             assert bool((st == 7).all())
             assert np.array_equal(dd.cpu().numpy(), c.broken) and np.array_equal(dp.cpu().numpy(), c.par_in)
+            assert np.array_equal(dm.cpu().numpy().view(np.uint64), c.masks_in)
             return []
         ctx.recover_packed_dev(dd, dp, dm, G, k, r, P, out, rs, tot, st)
         ctx.synchronize()
@@ -318,6 +331,7 @@ def run_decode(ctx, quicfec, torch, c, api, expected):
         assert np.array_equal(dd.cpu().numpy(), c.broken)
     assert np.array_equal(st.cpu().numpy(), c.status), us.mismatch(c.masks, k, r, st.cpu().numpy(), c.status)
     assert np.array_equal(dp.cpu().numpy(), c.par_in)              # parity only read, junk rows included
+    assert np.array_equal(dm.cpu().numpy().view(np.uint64), c.masks_in)   # masks only read, junk bits included
     return assert_forms(trace, G, expected)
 
 
@@ -378,7 +392,8 @@ def test_host_decode_scan_choice(gpu_ctx_hooks, quicfec_mod, oracle_mod, torch_c
     w = np.left_shift(np.uint64(1), np.arange(k + r, dtype=np.uint64))
     masks = ((rng.random((G, k + r)) < loss) * w).sum(axis=1, dtype=np.uint64)
     masks[0] = 1 | 1 << k                  # planted: row 0 lost, row 1 chosen, row 2 survives unread
-    c = Case(oracle_mod, k, r, P, masks)
+    # 1 % iid loss over 131 groups leaves too few groups that use every surviving row, or are one short
+    c = Case(oracle_mod, k, r, P, masks, need_full=loss > 0.1, need_short=loss > 0.1)
     lost = (masks & np.uint64((1 << k) - 1)) != 0
     share = float((lost & (c.status == 0)).sum()) / G
     assert share > 0 and (share < SCAN_MAX_SHARE) == (loss < 0.1), share   # the two cases sit on either side
@@ -386,9 +401,10 @@ def test_host_decode_scan_choice(gpu_ctx_hooks, quicfec_mod, oracle_mod, torch_c
     data, st = c.broken.copy(), np.full(G, 7, dtype=np.uint8)
     quicfec_mod.launch_trace(ctx.lib)
     par_in = c.par_in.copy()
-    bad = ctx.decode(data, par_in, masks, k, r, P, st)
+    masks_in = c.masks_in.copy()
+    bad = ctx.decode(data, par_in, masks_in, k, r, P, st)   # the loss share must not count the junk bits
     trace = quicfec_mod.launch_trace(ctx.lib)
-    assert np.array_equal(par_in, c.par_in)
+    assert np.array_equal(par_in, c.par_in) and np.array_equal(masks_in, c.masks_in)
     assert np.array_equal(data, c.ref) and np.array_equal(st, c.status) and bad == int((c.status != 0).sum())
     assert_forms(trace, G, expected_decode("in_place", k, r, P, scan=share < SCAN_MAX_SHARE))
 
@@ -603,8 +619,8 @@ def test_every_codebook_record(gpu_ctx_hooks, quicfec_mod, oracle_mod, torch_cud
     hide as an 'unrecoverable' group."""
     masks = record_masks(k, r, k * 100 + r)
     assert len(masks) == records
-    # every group rebuilds: with one parity row none survives unchosen
-    c = Case(oracle_mod, k, r, P, masks, need_unchosen_alive=r > 1)
+    # every group rebuilds: with one parity row none survives unchosen, and no group is one row short or untouched
+    c = Case(oracle_mod, k, r, P, masks, need_unchosen_alive=r > 1, need_short=False, need_untouched=False)
     assert (c.status == 0).all() and len(c.rows) == int(sum(bin(int(m) & ((1 << k) - 1)).count("1") for m in masks))
     for api in ("in_place", "slots"):
         run_decode(gpu_ctx_hooks, quicfec_mod, torch_cuda, c, api, expected_decode(api, k, r, P))
@@ -614,15 +630,18 @@ def test_every_codebook_record(gpu_ctx_hooks, quicfec_mod, oracle_mod, torch_cud
 @pytest.mark.parametrize("k,r", [(10, 3), (10, 2), (10, 1), (4, 2)])
 def test_every_mask(gpu_ctx_hooks, quicfec_mod, oracle_mod, torch_cuda, monkeypatch, k, r):
     """All 2^(k+r) erasure masks, shuffled, at 272 B through every API and form: statuses, rows,
-    row starts and the total equal the oracle's."""
+    row starts and the total equal the oracle's.  Four passes: the bits at and above k + r clean,
+    all set, only bit k + r set, and the helper's draw."""
     P = 272
     masks = np.arange(1 << (k + r), dtype=np.uint64)
     np.random.default_rng(k + r).shuffle(masks)
-    c = Case(oracle_mod, k, r, P, masks)
-    for name, api, env in [("in_place", "in_place", {}), ("slots", "slots", {}), ("packed", "packed", {}),
+    every = np.uint64(((1 << (64 - k - r)) - 1) << (k + r))
+    cases = [Case(oracle_mod, k, r, P, masks, masks_in=masks_in)
+             for masks_in in (masks.copy(), masks | every, masks | np.uint64(1 << (k + r)))] + [Case(oracle_mod, k, r, P, masks)]
+    for (name, api, env), c in itertools.product([("in_place", "in_place", {}), ("slots", "slots", {}), ("packed", "packed", {}),
                            ("packed_runs", "packed", {"QUICFEC_PACKED_RUNS": "1"}),
                            ("scan", "in_place", {"QUICFEC_DECODE_SCAN": "8"}),
-                           ("slots+scan", "slots", {"QUICFEC_DECODE_SCAN": "8"})]:
+                           ("slots+scan", "slots", {"QUICFEC_DECODE_SCAN": "8"})], cases):
         with monkeypatch.context() as mp:
             for key, val in env.items():
                 mp.setenv(key, val)

@@ -4,7 +4,7 @@ count, erasure patterns (up to r + 1 lost, so some groups are unrecoverable) and
 generator.  Each case is small, the whole sweep runs in seconds; it exists to catch the
 interaction bugs that the per-shape parity tests do not pin (form selection, workspace and
 staging reuse across calls of different shapes on one context).  Decode inputs hold junk in every
-shard the erasure rule does not read (tests/unread_shards.py)."""
+shard and every mask bit the erasure rule does not read (tests/unread_shards.py)."""
 import os
 
 import numpy as np
@@ -49,11 +49,30 @@ def _junked(data, par, masks, k, r, P, seed, seen):
     return us.inputs(data, par, masks, k, r, P, seed, need_lost_below=False, need_unchosen_alive=False)
 
 
+def _high(masks, k, r, seed, seen):
+    """masks_in of one drawn case: the helper's junk in the bits at and above k + r (every drawn
+    shape has k + r <= 28).  A drawn case may be a single group, so none promises the planted
+    groups; `seen` collects whether a group that uses every surviving row, and one that is one row
+    short, carried junk, and the test asserts both at its end."""
+    masks_in = us.high_bits(masks, k, r, seed, need_full=False, need_short=False, need_untouched=False)
+    ro, junked = us.roles(masks, k, r), masks_in != masks
+    seen["full"] |= bool((us.full_groups(ro) & junked).any())
+    seen["short"] |= bool((us.short_groups(ro) & junked).any())
+    return masks_in
+
+
+def _same_on_clean(oracle_mod, broken, par_in, masks, k, r, P, ref, st_exp):
+    """ref / st_exp are the oracle's on masks_in; it says the same on the clean masks."""
+    clean = np.array(broken).reshape(-1)
+    _, st_clean = oracle_mod.rs_decode(clean, par_in, masks, len(masks), k, r, P, nthreads=4)
+    assert np.array_equal(clean, ref) and np.array_equal(st_clean, st_exp)
+
+
 @pytest.mark.parametrize("block", range(BLOCKS))
 def test_random_shapes_all_apis(gpu_ctx, oracle_mod, torch_cuda, block):
     torch = torch_cuda
     rng = np.random.default_rng(SEED + block)
-    seen = {"lost_below": False, "unchosen_alive": False}
+    seen = {"lost_below": False, "unchosen_alive": False, "full": False, "short": False}
     for _ in range(10):   # one context, shapes and APIs interleaved
         k, r, P, G, api = _case(rng)
         data = oracle_mod.splitmix_bytes(G * k * P, int(rng.integers(0, 1 << 30)))
@@ -63,7 +82,9 @@ def test_random_shapes_all_apis(gpu_ctx, oracle_mod, torch_cuda, block):
         broken, par_in = _junked(data, par_exp, masks, k, r, P, SEED + block, seen)
         broken = broken.reshape(G, k, P)
         ref = broken.copy().reshape(-1)
-        bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=4)
+        masks_in = _high(masks, k, r, SEED + block, seen)
+        bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks_in, G, k, r, P, nthreads=4)
+        _same_on_clean(oracle_mod, broken, par_in, masks, k, r, P, ref, st_exp)
         tag = (k, r, P, G, api)
         if api in ("host", "pinned"):
             if api == "pinned":
@@ -74,7 +95,8 @@ def test_random_shapes_all_apis(gpu_ctx, oracle_mod, torch_cuda, block):
                 dd = torch.from_numpy(broken.reshape(-1)).pin_memory()
                 par.copy_(torch.from_numpy(par_in))                         # the same page-locked buffer, junk where unread
                 st = torch.zeros(G, dtype=torch.uint8).pin_memory()
-                bad = gpu_ctx.decode(dd, par, torch.from_numpy(masks.view(np.int64)), k, r, P, st, num_groups=G)
+                m_after = masks_in.copy()
+                bad = gpu_ctx.decode(dd, par, torch.from_numpy(m_after.view(np.int64)), k, r, P, st, num_groups=G)
                 got, st_np, par_after = dd.numpy(), st.numpy(), par.numpy()
             else:
                 par_np = np.zeros(G * r * P, dtype=np.uint8)
@@ -82,11 +104,12 @@ def test_random_shapes_all_apis(gpu_ctx, oracle_mod, torch_cuda, block):
                 got = broken.reshape(-1).copy()
                 st_np = np.zeros(G, dtype=np.uint8)
                 par_after = par_in.copy()
-                bad = gpu_ctx.decode(got, par_after, masks, k, r, P, st_np, num_groups=G)
+                m_after = masks_in.copy()
+                bad = gpu_ctx.decode(got, par_after, m_after, k, r, P, st_np, num_groups=G)
             assert np.array_equal(par_np, par_exp), tag
             assert bad == bad_exp and np.array_equal(st_np, st_exp), tag
             assert np.array_equal(got, ref), tag + (us.mismatch(masks, k, r, got, ref),)
-            assert np.array_equal(par_after, par_in), tag
+            assert np.array_equal(par_after, par_in) and np.array_equal(m_after, masks_in), tag
             continue
         dd = torch.from_numpy(broken.reshape(-1)).cuda()
         d_src = torch.from_numpy(data).cuda()
@@ -95,7 +118,7 @@ def test_random_shapes_all_apis(gpu_ctx, oracle_mod, torch_cuda, block):
         gpu_ctx.synchronize()
         assert np.array_equal(dp.cpu().numpy(), par_exp), tag
         dp.copy_(torch.from_numpy(par_in))                                  # junk where the rule does not read
-        dm = torch.from_numpy(masks.view(np.int64)).cuda()
+        dm = torch.from_numpy(masks_in.view(np.int64)).cuda()
         st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
         if api == "dev_inplace":
             gpu_ctx.decode_dev(dd, dp, dm, G, k, r, P, st)
@@ -111,8 +134,9 @@ def test_random_shapes_all_apis(gpu_ctx, oracle_mod, torch_cuda, block):
                 for m, j in enumerate(np.nonzero(lost[g])[0]):
                     assert np.array_equal(o3[g, m], ref3[g, j]), tag + (int(g), int(j))
         assert np.array_equal(dp.cpu().numpy(), par_in), tag
+        assert np.array_equal(dm.cpu().numpy().view(np.uint64), masks_in), tag
         assert np.array_equal(st.cpu().numpy(), st_exp), tag
-    assert seen["lost_below"] and seen["unchosen_alive"], seen
+    assert all(seen.values()), seen
 
 
 @pytest.mark.parametrize("block", range(4))
@@ -181,7 +205,7 @@ def test_random_packed_recover(gpu_ctx_hooks, oracle_mod, torch_cuda, block):
     torch = torch_cuda
     rng = np.random.default_rng(SEED + 200 + block)
     shapes = [(10, 3), (10, 2), (10, 1), (4, 2)]
-    seen = {"lost_below": False, "unchosen_alive": False}
+    seen = {"lost_below": False, "unchosen_alive": False, "full": False, "short": False}
     saved = os.environ.get("QUICFEC_PACKED_RUNS")
     try:
         for _ in range(8):
@@ -202,14 +226,16 @@ def test_random_packed_recover(gpu_ctx_hooks, oracle_mod, torch_cuda, block):
             lost = us.roles(masks, k, r).lost_d
             broken, par_in = _junked(data, par, masks, k, r, P, SEED + 200 + block, seen)
             ref = broken.copy()
-            _, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=4)
+            masks_in = _high(masks, k, r, SEED + 200 + block, seen)
+            _, st_exp = oracle_mod.rs_decode(ref, par_in, masks_in, G, k, r, P, nthreads=4)
+            _same_on_clean(oracle_mod, broken, par_in, masks, k, r, P, ref, st_exp)
             ok = st_exp == 0
             rows = np.where(ok, lost.sum(axis=1), 0)
             start = np.concatenate([[0], np.cumsum(rows)[:-1]]).astype(np.uint32)
             exp = ref.reshape(G, k, P)[lost & ok[:, None]]
             dd = torch.from_numpy(broken).cuda()
             dp = torch.from_numpy(par_in).cuda()
-            dm = torch.from_numpy(masks.view(np.int64)).cuda()
+            dm = torch.from_numpy(masks_in.view(np.int64)).cuda()
             out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
             rs = torch.zeros(G, dtype=torch.int32, device="cuda")
             tot = torch.full((1,), -1, dtype=torch.int64, device="cuda")
@@ -225,7 +251,8 @@ def test_random_packed_recover(gpu_ctx_hooks, oracle_mod, torch_cuda, block):
             assert np.array_equal(o[:n], exp), tag
             assert (o[n:] == 0x5A).all(), tag
             assert np.array_equal(dd.cpu().numpy(), broken) and np.array_equal(dp.cpu().numpy(), par_in), tag
-        assert seen["lost_below"] and seen["unchosen_alive"], seen
+            assert np.array_equal(dm.cpu().numpy().view(np.uint64), masks_in), tag
+        assert all(seen.values()), seen
     finally:
         gpu_ctx.decode_loss_hint(-1.0)
         if saved is None:

@@ -38,22 +38,28 @@ NOTHING = np.array([0, 0, 0b110000, 0b010000, 0b000111, 0, 0b100011], dtype=np.u
 
 @pytest.fixture(scope="module")
 def case(oracle_mod):
-    """The data, its parity and, per mask set, the decode's inputs (junk in every lost data shard and
-    every parity row the erasure rule does not read, tests/unread_shards.py) and what the oracle makes
-    of them."""
+    """The data, its parity and, per mask set, the decode's inputs (junk in every lost data shard,
+    every parity row and every mask bit the erasure rule does not read, tests/unread_shards.py) and
+    what the oracle makes of them."""
     data = oracle_mod.splitmix_bytes(G * K * P, 0x5EED0909)
     par = oracle_mod.rs_encode(data, G, K, R, P)
     out = {"data": data, "par": par}
     for name, masks in (("sparse", SPARSE), ("dense", DENSE), ("nothing", NOTHING)):
         # "nothing" rebuilds no group on purpose, so none has a chosen row to have a lost row below
         broken, par_in = us.inputs(data, par, masks, K, R, P, 0x5EED0909, need_lost_below=name != "nothing")
-        ref = broken.copy()
-        bad, st = oracle_mod.rs_decode(ref, par_in, masks, G, K, R, P)
+        # seven groups written out by hand: of the six planted groups those that exist get their pattern
+        # (the two one row short and an untouched one in every set, two that use every row in two)
+        masks_in = us.high_bits(masks, K, R, 0x5EED0909, need_full=False, need_short=False, need_untouched=False)
+        assert len(us.planted(masks, K, R, 0x5EED0909, False, False, False)) >= 3
+        ref, clean = broken.copy(), broken.copy()
+        bad, st = oracle_mod.rs_decode(ref, par_in, masks_in, G, K, R, P)
+        bad_clean, st_clean = oracle_mod.rs_decode(clean, par_in, masks, G, K, R, P)
+        assert bad == bad_clean and np.array_equal(st, st_clean) and np.array_equal(ref, clean)
         ok = st == 0
         assert np.array_equal(ref.reshape(G, -1)[ok], data.reshape(G, -1)[ok])
-        for a in (broken, par_in, ref):
+        for a in (broken, par_in, ref, masks_in):
             a.setflags(write=False)
-        out[name] = (masks, broken, ref, bad, st, par_in)
+        out[name] = (masks, broken, ref, bad, st, par_in, masks_in)
     assert out["sparse"][3] == out["dense"][3] == out["nothing"][3] == 2
     return out
 
@@ -66,8 +72,8 @@ def _pinned(torch, a):
 def test_decode_one_buffer_on_the_device(gpu_ctx, torch_cuda, case, on_device):
     """One input on the device, the others and the statuses in pageable host memory: the staged route."""
     torch = torch_cuda
-    masks, broken, ref, bad_exp, st_exp, par_in = case["sparse"]
-    bufs = {"data": broken.copy(), "parity": par_in.copy(), "masks": masks.copy(),
+    masks, broken, ref, bad_exp, st_exp, par_in, masks_in = case["sparse"]
+    bufs = {"data": broken.copy(), "parity": par_in.copy(), "masks": masks_in.copy(),
             "status": np.full(G, 0xAA, dtype=np.uint8)}
     host = bufs[on_device]
     bufs[on_device] = torch.from_numpy(host.view(np.int64) if on_device == "masks" else host).cuda()
@@ -77,6 +83,7 @@ def test_decode_one_buffer_on_the_device(gpu_ctx, torch_cuda, case, on_device):
     assert np.array_equal(got["status"], st_exp)
     assert np.array_equal(got["data"], ref), us.mismatch(masks, K, R, got["data"], ref)
     assert np.array_equal(got["parity"], par_in)
+    assert np.array_equal(got["masks"].view(np.uint64), masks_in)
 
 
 @pytest.mark.parametrize("device", ["offsets", "data"])
@@ -104,15 +111,17 @@ def test_encode_offsets_and_data_on_different_sides(gpu_ctx, torch_cuda, case, d
 def test_decode_nothing_to_rebuild(gpu_ctx, torch_cuda, case, pinned):
     """No group has lost data it can rebuild (parity-only losses, unrecoverable groups): the host's
     scan of the masks is the whole answer, the data stays as it is."""
-    masks, broken, ref, bad_exp, st_exp, par_in = case["nothing"]
+    masks, broken, ref, bad_exp, st_exp, par_in, masks_in = case["nothing"]
     assert np.array_equal(ref, broken)
     data = _pinned(torch_cuda, broken) if pinned else broken.copy()
     par = _pinned(torch_cuda, par_in) if pinned else par_in.copy()
     st = np.full(G, 0xAA, dtype=np.uint8)
-    assert gpu_ctx.decode(data, par, masks.copy(), K, R, P, status_out=st, num_groups=G) == bad_exp
+    hm = masks_in.copy()
+    assert gpu_ctx.decode(data, par, hm, K, R, P, status_out=st, num_groups=G) == bad_exp
     assert np.array_equal(st, st_exp)
     assert np.array_equal(data.numpy() if pinned else data, ref)
-    assert gpu_ctx.decode(data, par, masks.copy(), K, R, P, num_groups=G) == bad_exp     # without statuses
+    assert gpu_ctx.decode(data, par, hm, K, R, P, num_groups=G) == bad_exp     # without statuses
+    assert np.array_equal(hm, masks_in)
 
 
 @pytest.mark.parametrize("pinned", [False, True])
@@ -132,9 +141,10 @@ def test_tiny_pipeline(gpu_ctx, torch_cuda, case, monkeypatch, pinned):
     gpu_ctx.encode(host(case["data"]), K, R, P, par, num_groups=G)
     assert np.array_equal(npy(par), case["par"])
     for name in ("dense", "sparse"):
-        masks, broken, ref, bad_exp, st_exp, par_in = case[name]
-        data, hp, st = host(broken), host(par_in), np.full(G, 0xAA, dtype=np.uint8)
-        assert gpu_ctx.decode(data, hp, masks.copy(), K, R, P, status_out=st, num_groups=G) == bad_exp, name
+        masks, broken, ref, bad_exp, st_exp, par_in, masks_in = case[name]
+        data, hp, st, hm = host(broken), host(par_in), np.full(G, 0xAA, dtype=np.uint8), masks_in.copy()
+        assert gpu_ctx.decode(data, hp, hm, K, R, P, status_out=st, num_groups=G) == bad_exp, name
+        assert np.array_equal(hm, masks_in), name
         assert np.array_equal(st, st_exp), name
         assert np.array_equal(npy(data), ref), (name, us.mismatch(masks, K, R, npy(data), ref))
         assert np.array_equal(npy(hp), par_in), name

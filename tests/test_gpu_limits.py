@@ -58,18 +58,28 @@ def test_decode_and_recover_extreme_shapes(gpu_ctx, oracle_mod, torch_cuda, k, r
     # junk in every lost shard, parity rows included (tests/unread_shards.py); every group loses
     # exactly r shards, so every surviving row is read and none is left unchosen
     broken, par_in = us.inputs(data, par, masks, k, r, P, SEED + 5 + k + r, need_lost_below=r > 1, need_unchosen_alive=False)
-    got, hp = broken.copy(), par_in.copy()
+    # junk in the mask bits at and above k + r too (k + r = 64 has none: a copy).  Every group loses
+    # exactly r shards, so each uses every surviving row and none is one short or untouched; the
+    # single group of k=20 r=5 cannot be three planted ones
+    masks_in = us.high_bits(masks, k, r, SEED + 5 + k + r, need_full=G >= 3, need_short=False, need_untouched=False)
+    assert (masks_in != masks).any() == (k + r < 64)
+    ref = broken.copy()
+    assert oracle_mod.rs_decode(ref, par_in, masks_in, G, k, r, P)[0] == 0 and np.array_equal(ref, data)
+    ref = broken.copy()
+    assert oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P)[0] == 0 and np.array_equal(ref, data)
+    got, hp, hm = broken.copy(), par_in.copy(), masks_in.copy()
     st = np.full(G, 0xAA, dtype=np.uint8)
-    assert gpu_ctx.decode(got, hp, masks, k, r, P, status_out=st) == 0
+    assert gpu_ctx.decode(got, hp, hm, k, r, P, status_out=st) == 0
     assert np.array_equal(got, data) and not st.any(), us.mismatch(masks, k, r, got, data)
-    assert np.array_equal(hp, par_in)
+    assert np.array_equal(hp, par_in) and np.array_equal(hm, masks_in)
     # device-resident recover: group g's m-th lost data shard at (g*r + m)*P
     out = torch_cuda.full((G * r * P,), 0x5A, dtype=torch_cuda.uint8, device="cuda")
     dst = torch_cuda.full((G,), 0xAA, dtype=torch_cuda.uint8, device="cuda")
-    gpu_ctx.recover_dev(_dev(torch_cuda, broken), _dev(torch_cuda, par_in), _dev(torch_cuda, masks.view(np.int64)),
-                        G, k, r, P, out, dst)
+    dm = _dev(torch_cuda, masks_in.view(np.int64))
+    gpu_ctx.recover_dev(_dev(torch_cuda, broken), _dev(torch_cuda, par_in), dm, G, k, r, P, out, dst)
     gpu_ctx.synchronize()
     assert not dst.cpu().numpy().any()
+    assert np.array_equal(dm.cpu().numpy().view(np.uint64), masks_in)
     o = out.cpu().numpy().reshape(G, r, P)
     d = data.reshape(G, k, P)
     for g in range(G):

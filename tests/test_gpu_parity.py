@@ -160,6 +160,29 @@ def _junked(data, par, masks, G, k, r, P, **need):
     return us.inputs(data, par, masks, k, r, P, SEED + 13 * k + r + P, **need)
 
 
+def _high(masks, k, r, P, **need):
+    """masks_in: what a decode is given as masks, with seeded junk in the bits at and above k + r,
+    which the rule ignores (tests/unread_shards.py high_bits, its planted groups included)."""
+    masks_in = us.high_bits(masks, k, r, SEED + 13 * k + r + P, **need)
+    return masks_in
+
+
+def _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P, nthreads=1):
+    """(result, unrecoverable count, statuses) of the oracle on masks_in, checked to be what it
+    says on the clean masks."""
+    ref, clean = broken.copy(), broken.copy()
+    bad, st = oracle_mod.rs_decode(ref, par_in, masks_in, G, k, r, P, nthreads=nthreads)
+    bad_clean, st_clean = oracle_mod.rs_decode(clean, par_in, masks, G, k, r, P, nthreads=nthreads)
+    assert bad == bad_clean and np.array_equal(st, st_clean) and np.array_equal(ref, clean)
+    return ref, bad, st
+
+
+def _masks_unwritten(dm, masks_in):
+    """A mask buffer after a call (device tensor or host array): masks are const, junk bits included."""
+    after = dm.cpu().numpy().view(np.uint64) if hasattr(dm, "cpu") else np.asarray(dm).view(np.uint64)
+    return np.array_equal(after, masks_in)
+
+
 @pytest.mark.parametrize("k,r,P", SHAPES + [(16, 16, 32), (32, 8, 48)])
 def test_rs_decode_matches_oracle(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
     """Dense codebook shapes and, for (30,20), (16,16), (32,8), the per-call sparse plan."""
@@ -169,24 +192,24 @@ def test_rs_decode_matches_oracle(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
     par = oracle_mod.rs_encode(data, G, k, r, P)
     masks = _random_masks(rng, G, k, r, r + 1)
     broken, par_in = _junked(data, par, masks, G, k, r, P)
-    exp = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(exp, par_in, masks, G, k, r, P)
-    got, hp = broken.copy(), par_in.copy()
+    masks_in = _high(masks, k, r, P)
+    exp, bad_exp, st_exp = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P)
+    got, hp, hm = broken.copy(), par_in.copy(), masks_in.copy()
     st = np.zeros(G, dtype=np.uint8)
-    bad = gpu_ctx.decode(got, hp, masks, k, r, P, status_out=st)
+    bad = gpu_ctx.decode(got, hp, hm, k, r, P, status_out=st)
     assert bad == bad_exp
     assert np.array_equal(st, st_exp)
     assert np.array_equal(got, exp), us.mismatch(masks, k, r, got, exp)
-    assert np.array_equal(hp, par_in)
+    assert np.array_equal(hp, par_in) and _masks_unwritten(hm, masks_in)
     # device-resident API
-    dd, dpar, dm = _dev(torch_cuda, broken), _dev(torch_cuda, par_in), _dev(torch_cuda, masks.view(np.int64))
+    dd, dpar, dm = _dev(torch_cuda, broken), _dev(torch_cuda, par_in), _dev(torch_cuda, masks_in.view(np.int64))
     # 0xAA: every status byte must be written by the device (inline classify included)
     dst = torch_cuda.full((G,), 0xAA, dtype=torch_cuda.uint8, device="cuda")
     gpu_ctx.decode_dev(dd, dpar, dm, G, k, r, P, dst)
     gpu_ctx.synchronize()
     assert np.array_equal(dd.cpu().numpy(), exp), us.mismatch(masks, k, r, dd.cpu().numpy(), exp)
     assert np.array_equal(dst.cpu().numpy(), st_exp)
-    assert np.array_equal(dpar.cpu().numpy(), par_in)
+    assert np.array_equal(dpar.cpu().numpy(), par_in) and _masks_unwritten(dm, masks_in)
 
 
 def test_gf_golden_fixtures(gpu_ctx, oracle_mod, manifest, gf_golden):
@@ -210,7 +233,9 @@ def test_gf_golden_fixtures(gpu_ctx, oracle_mod, manifest, gf_golden):
         broken.reshape(G, k, P)[ro.lost_d & ~ro.ok[:, None]] = 0xEE
         assert (golden[ro.lost_d & ~ro.ok[:, None]] == 0xEE).all()
         st = np.zeros(G, dtype=np.uint8)
-        bad = gpu_ctx.decode(broken, par_in.copy(), masks, k, r, P, status_out=st)
+        # 4 to 16 committed masks: no room for the planted groups; the drawn junk goes in all the same
+        masks_in = _high(masks, k, r, P, need_full=False, need_short=False, need_untouched=False)
+        bad = gpu_ctx.decode(broken, par_in.copy(), masks_in.copy(), k, r, P, status_out=st)
         assert bad == c["unrecoverable"]
         assert np.array_equal(broken.reshape(G, k, P), golden), (c["name"], us.mismatch(masks, k, r, broken, golden))
     assert lost_below >= 2
@@ -226,7 +251,9 @@ def test_single_loss_is_reference_xor_recovery(gpu_ctx, oracle_mod):
     masks = np.array([1 << int(j) for j in lost], dtype=np.uint64)
     # no parity row is lost on purpose (the XOR row must be the chosen one); rows 1 and 2 are unread junk
     got, par_in = _junked(data, par, masks, G, k, r, P, need_lost_below=False)
-    assert gpu_ctx.decode(got, par_in.copy(), masks, k, r, P) == 0
+    # one lost data shard and three surviving rows in every group: none uses every row, is short or untouched
+    masks_in = _high(masks, k, r, P, need_full=False, need_short=False, need_untouched=False)
+    assert gpu_ctx.decode(got, par_in.copy(), masks_in.copy(), k, r, P) == 0
     for g in range(G):
         pk = [None if j == lost[g] else data[(g * k + j) * P:(g * k + j + 1) * P] for j in range(k)]
         mid, rec = oracle_mod.go_recover_single(pk, par[g * r * P:g * r * P + P], P)
@@ -254,21 +281,22 @@ def test_host_pipeline_multi_chunk(gpu_ctx, oracle_mod, torch_cuda, monkeypatch,
     rng = np.random.default_rng(12)
     masks = _random_masks(rng, G, k, r, r + 1)
     broken, par_in = _junked(data, exp, masks, G, k, r, P)
-    ref = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
+    masks_in = _high(masks, k, r, P)
+    ref, bad_exp, st_exp = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P, nthreads=8)
+    hm = masks_in.copy()
     if pinned:
         hb = torch_cuda.from_numpy(broken).pin_memory()
         hp = torch_cuda.from_numpy(par_in.copy()).pin_memory()
         st = torch_cuda.zeros(G, dtype=torch_cuda.uint8).pin_memory()
-        bad = gpu_ctx.decode(hb, hp, masks, k, r, P, status_out=st, num_groups=G)
+        bad = gpu_ctx.decode(hb, hp, hm, k, r, P, status_out=st, num_groups=G)
         hb, hp, st = hb.numpy(), hp.numpy(), st.numpy()
     else:
         hb, hp, st = broken, par_in.copy(), np.zeros(G, dtype=np.uint8)
-        bad = gpu_ctx.decode(hb, hp, masks, k, r, P, status_out=st)
+        bad = gpu_ctx.decode(hb, hp, hm, k, r, P, status_out=st)
     assert bad == bad_exp
     assert np.array_equal(st, st_exp)
     assert np.array_equal(hb, ref), us.mismatch(masks, k, r, hb, ref)
-    assert np.array_equal(hp, par_in)
+    assert np.array_equal(hp, par_in) and _masks_unwritten(hm, masks_in)
 
 
 @pytest.mark.parametrize("k,r,P,pinned,dma", [(10, 3, 1200, True, True), (10, 3, 1200, True, False),
@@ -289,22 +317,25 @@ def test_host_decode_compacted_sparse_loss(gpu_ctx, oracle_mod, torch_cuda, monk
     masks[rng.integers(0, G, size=9)] = np.uint64((1 << (r + 1)) - 1)   # r+1 data shards lost
     masks[5] = np.uint64(0)
     broken, par_in = _junked(data, par, masks, G, k, r, P)
-    ref = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
+    # the planted r + 1 losses are the short groups; 2 % iid loss over 25 shards draws no three groups of
+    # k=20 r=5 with exactly five losses
+    masks_in = _high(masks, k, r, P, need_full=(k, r) != (20, 5))
+    ref, bad_exp, st_exp = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P, nthreads=8)
     assert 0 < bad_exp and (st_exp == 0).sum() > 0
+    hm = masks_in.copy()
     if pinned:
         hb = torch_cuda.from_numpy(broken).pin_memory()
         hp = torch_cuda.from_numpy(par_in.copy()).pin_memory()
         st = np.zeros(G, dtype=np.uint8)
-        bad = gpu_ctx.decode(hb, hp, masks, k, r, P, status_out=st, num_groups=G)
+        bad = gpu_ctx.decode(hb, hp, hm, k, r, P, status_out=st, num_groups=G)
         got, hp = hb.numpy(), hp.numpy()
     else:
         got, hp, st = broken.copy(), par_in.copy(), np.zeros(G, dtype=np.uint8)
-        bad = gpu_ctx.decode(got, hp, masks, k, r, P, status_out=st)
+        bad = gpu_ctx.decode(got, hp, hm, k, r, P, status_out=st)
     assert bad == bad_exp
     assert np.array_equal(st, st_exp)
     assert np.array_equal(got, ref), us.mismatch(masks, k, r, got, ref)
-    assert np.array_equal(hp, par_in)
+    assert np.array_equal(hp, par_in) and _masks_unwritten(hm, masks_in)
 
 
 @pytest.mark.parametrize("devices", [None, [0, 0, 0]])
@@ -317,8 +348,8 @@ def test_device_group_shards_host_batches(quicfec_mod, oracle_mod, torch_cuda, d
     rng = np.random.default_rng(31)
     masks = _random_masks(rng, G, k, r, r + 1)
     broken, par_in = _junked(data, exp, masks, G, k, r, P)
-    ref = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
+    masks_in = _high(masks, k, r, P)
+    ref, bad_exp, st_exp = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P, nthreads=8)
     with quicfec_mod.DeviceGroup(devices) as grp:
         assert len(grp) == (3 if devices else quicfec_mod.device_count())
         par = np.zeros(G * r * P, dtype=np.uint8)
@@ -326,11 +357,12 @@ def test_device_group_shards_host_batches(quicfec_mod, oracle_mod, torch_cuda, d
         assert np.array_equal(par, exp)
         h_par = torch_cuda.from_numpy(par_in.copy()).pin_memory()         # page-locked parity, junk where unread
         st = np.zeros(G, dtype=np.uint8)
-        bad = grp.decode(broken, h_par, masks, k, r, P, status_out=st)
+        hm = masks_in.copy()
+        bad = grp.decode(broken, h_par, hm, k, r, P, status_out=st)
         assert bad == bad_exp
         assert np.array_equal(st, st_exp)
         assert np.array_equal(broken, ref), us.mismatch(masks, k, r, broken, ref)
-        assert np.array_equal(h_par.numpy(), par_in)
+        assert np.array_equal(h_par.numpy(), par_in) and _masks_unwritten(hm, masks_in)
         dd = torch_cuda.from_numpy(data).cuda()                  # device buffers are refused
         with pytest.raises(quicfec_mod.FecError) as ei:
             grp.encode(dd, k, r, P, par, num_groups=G)
@@ -395,7 +427,9 @@ def test_full_size_c2_c3_round_trip(gpu_ctx, oracle_mod, torch_cuda):
     pos = np.argsort(keys, axis=1)[:, :2]
     masks = (np.left_shift(np.uint64(1), pos.astype(np.uint64))).sum(axis=1, dtype=np.uint64)
     orig = data.clone()
-    dm = torch.from_numpy(masks.view(np.int64)).cuda()
+    # exactly two losses per group: none uses every row, is one short or is untouched
+    masks_in = _high(masks, k, r, P, need_full=False, need_short=False, need_untouched=False)
+    dm = torch.from_numpy(masks_in.view(np.int64)).cuda()
     lost = torch.zeros((G, k), dtype=torch.bool, device="cuda")
     bits = torch.arange(k, device="cuda", dtype=torch.int64)
     lost = ((dm.view(G, 1) >> bits.view(1, k)) & 1).bool()
@@ -406,7 +440,7 @@ def test_full_size_c2_c3_round_trip(gpu_ctx, oracle_mod, torch_cuda):
     gpu_ctx.decode_dev(data, par, dm, G, k, r, P, st, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert int(st.sum().item()) == 0
-    assert torch.equal(data, orig)
+    assert torch.equal(data, orig) and _masks_unwritten(dm, masks_in)
 
 
 @pytest.mark.slow
@@ -424,7 +458,9 @@ def test_full_size_c4_shard_encode(gpu_ctx, oracle_mod, torch_cuda):
     rng = np.random.default_rng(5)
     pos = np.argsort(rng.random((Gs, k + r)), axis=1)[:, :r]
     masks = (np.left_shift(np.uint64(1), pos.astype(np.uint64))).sum(axis=1, dtype=np.uint64)
-    dm = torch.from_numpy(masks.view(np.int64)).cuda()
+    # exactly r losses per group: every rebuilding group uses every surviving row, none is short or untouched
+    masks_in = _high(masks, k, r, P, need_short=False, need_untouched=False)
+    dm = torch.from_numpy(masks_in.view(np.int64)).cuda()
     sub = data[:Gs * k * P]
     orig = sub.clone()
     bits = torch.arange(k, device="cuda", dtype=torch.int64)
@@ -434,7 +470,7 @@ def test_full_size_c4_shard_encode(gpu_ctx, oracle_mod, torch_cuda):
     par[:Gs * r * P].view(Gs, r, P)[((dm.view(Gs, 1) >> rows.view(1, r)) & 1).bool()] = 0x11   # lost parity rows too
     gpu_ctx.decode_dev(sub, par[:Gs * r * P], dm, Gs, k, r, P, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    assert torch.equal(sub, orig)
+    assert torch.equal(sub, orig) and _masks_unwritten(dm, masks_in)
 
 
 # ---------------- any packet size, any packet address ----------------
@@ -468,11 +504,11 @@ def test_any_packet_size_round_trip(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
     rng = np.random.default_rng(P * 31 + k)
     masks = _random_masks(rng, G, k, r, r + 1)
     broken, par_in = _junked(data, exp_par, masks, G, k, r, P)
-    exp = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(exp, par_in, masks, G, k, r, P)
+    masks_in = _high(masks, k, r, P)
+    exp, bad_exp, st_exp = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P)
     got = broken.copy()
     st = np.zeros(G, dtype=np.uint8)
-    assert gpu_ctx.decode(got, par_in.copy(), masks, k, r, P, status_out=st) == bad_exp
+    assert gpu_ctx.decode(got, par_in.copy(), masks_in.copy(), k, r, P, status_out=st) == bad_exp
     assert np.array_equal(st, st_exp)
     assert np.array_equal(got, exp), us.mismatch(masks, k, r, got, exp)
     # Device views at odd byte addresses (packet bases misaligned for every dword / 16-B access).
@@ -489,13 +525,13 @@ def test_any_packet_size_round_trip(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
         assert int(bp[:shift_p].sum().item()) == 0 and int(bp[shift_p + G * r * P:].sum().item()) == 0
         dd.copy_(torch.from_numpy(broken))
         dp.copy_(torch.from_numpy(par_in))
-        dm = _dev(torch, masks.view(np.int64))
+        dm = _dev(torch, masks_in.view(np.int64))
         dst = torch.full((G,), 0xAA, dtype=torch.uint8, device="cuda")  # every byte written
         gpu_ctx.decode_dev(dd, dp, dm, G, k, r, P, dst)
         gpu_ctx.synchronize()
         assert np.array_equal(dd.cpu().numpy(), exp), (shift_d, shift_p, us.mismatch(masks, k, r, dd.cpu().numpy(), exp))
         assert np.array_equal(dst.cpu().numpy(), st_exp)
-        assert np.array_equal(dp.cpu().numpy(), par_in)
+        assert np.array_equal(dp.cpu().numpy(), par_in) and _masks_unwritten(dm, masks_in)
         assert int(bd[:shift_d].sum().item()) == 0 and int(bd[shift_d + G * k * P:].sum().item()) == 0
 
 
@@ -562,11 +598,12 @@ def test_small_calls_zero_copy_and_dma(gpu_ctx, quicfec_mod, oracle_mod, xor_gol
         masks[0] = np.uint64(1 | 1 << k)  # at least one rebuilt group: from row 1, row 0 being lost
         # one group of k=10 r=3 has a surviving unread row (2); k=4 r=2 finds one among its 40 groups
         broken, par_in = _junked(data, exp, masks, G, k, r, P)
-        ref = broken.copy()
-        bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P)
+        # 1 to 40 groups: no room for the planted groups; the drawn junk goes in all the same
+        masks_in = _high(masks, k, r, P, need_full=False, need_short=False, need_untouched=False)
+        ref, bad_exp, st_exp = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P)
         hb, hp_in = host(broken), host(par_in)
         st = np.zeros(G, dtype=np.uint8)
-        assert gpu_ctx.decode(hb, hp_in, masks, k, r, P, status_out=st, num_groups=G) == bad_exp
+        assert gpu_ctx.decode(hb, hp_in, masks_in.copy(), k, r, P, status_out=st, num_groups=G) == bad_exp
         assert np.array_equal(st, st_exp)
         assert np.array_equal(npy(hb), ref), (k, r, P, G, us.mismatch(masks, k, r, npy(hb), ref))
         assert np.array_equal(npy(hp_in), par_in)
@@ -607,19 +644,24 @@ def test_concurrent_decodes_on_two_streams(gpu_ctx, oracle_mod, torch_cuda, k, r
         masks = np.left_shift(np.uint64(1), pos).sum(axis=1, dtype=np.uint64)
         # a group that loses exactly r shards reads every surviving row: k=20 r=5 has no unread survivor
         broken, par_in = _junked(data, par, masks, G, k, r, P, need_unchosen_alive=erasures < r)
-        batches.append((data, _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))))
+        # exactly `erasures` losses per group: it uses every surviving row where that is r, and none is short or untouched
+        masks_in = _high(masks, k, r, P + b, need_full=erasures == r, need_short=False, need_untouched=False)
+        ref, bad_exp, _ = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P, nthreads=4)
+        assert bad_exp == 0 and np.array_equal(ref, data)
+        batches.append((data, _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks_in.view(np.int64)), masks_in))
     torch.cuda.synchronize()
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     sts = [torch.full((G,), 7, dtype=torch.uint8, device="cuda") for _ in range(2)]
     for rep in range(3):                        # several rounds, no host sync between streams
         for b in range(2):
-            _, dd, dp, dm = batches[b]
+            _, dd, dp, dm, _ = batches[b]
             gpu_ctx.decode_dev(dd, dp, dm, G, k, r, P, sts[b], stream=streams[b].cuda_stream)
     torch.cuda.synchronize()
     for b in range(2):
-        data, dd, _, _ = batches[b]
+        data, dd, _, dm, masks_in = batches[b]
         assert int(sts[b].sum().item()) == 0
         assert np.array_equal(dd.cpu().numpy(), data), b
+        assert _masks_unwritten(dm, masks_in), b
 
 
 def test_ctx_last_error_set_on_failure(gpu_ctx, quicfec_mod):
@@ -653,12 +695,13 @@ def test_device_decode_scan_form(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypa
     masks = ((rng.random((G, k + r)) < loss) * w).sum(axis=1, dtype=np.uint64)
     masks[rng.integers(0, G, size=7)] = np.uint64(0xF)          # 4 data shards lost: unrecoverable
     broken, par_in = _junked(data, par, masks, G, k, r, P)
-    ref = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
-    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
+    masks_in = _high(masks, k, r, P)            # the planted four-shard losses are the short groups at 1 %
+    ref, bad_exp, st_exp = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P, nthreads=8)
+    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks_in.view(np.int64))
     st = torch.full((G,), 0x55, dtype=torch.uint8, device="cuda")
     gpu_ctx.decode_dev(dd, dp, dm, G, k, r, P, st)
     gpu_ctx.synchronize()
+    assert _masks_unwritten(dm, masks_in)
     assert np.array_equal(st.cpu().numpy(), st_exp)
     assert int((st_exp != 0).sum()) == bad_exp
     assert np.array_equal(dd.cpu().numpy(), ref), us.mismatch(masks, k, r, dd.cpu().numpy(), ref)
@@ -686,18 +729,19 @@ def test_recover_compact_output(gpu_ctx, oracle_mod, torch_cuda, k, r, P):
             masks[g] |= np.uint64(1) << np.uint64(int(s))
     lost = us.roles(masks, k, r).lost_d
     broken, par_in = _junked(data, par, masks, G, k, r, P)
-    ref = broken.copy()
-    bad_exp, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
+    masks_in = _high(masks, k, r, P)
+    ref, bad_exp, st_exp = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P, nthreads=8)
     exp = np.full((G, r, P), 0x5A, dtype=np.uint8)
     ref3 = ref.reshape(G, k, P)
     for g in np.nonzero(st_exp == 0)[0]:
         for m, j in enumerate(np.nonzero(lost[g])[0]):
             exp[g, m] = ref3[g, j]
-    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
+    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks_in.view(np.int64))
     out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
     st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
     gpu_ctx.recover_dev(dd, dp, dm, G, k, r, P, out, st)
     gpu_ctx.synchronize()
+    assert _masks_unwritten(dm, masks_in)
     assert np.array_equal(st.cpu().numpy(), st_exp)
     assert np.array_equal(out.cpu().numpy().reshape(G, r, P), exp), us.mismatch(masks, k, r, out.cpu().numpy(), exp)
     assert np.array_equal(dd.cpu().numpy(), broken)                 # data and parity untouched
@@ -719,19 +763,21 @@ def test_recover_scan_form(gpu_ctx_hooks, oracle_mod, torch_cuda, monkeypatch, l
     masks = ((rng.random((G, k + r)) < loss) * w).sum(axis=1, dtype=np.uint64)
     lost = us.roles(masks, k, r).lost_d
     broken, par_in = _junked(data, par, masks, G, k, r, P)
-    ref = broken.copy()
-    _, st_exp = oracle_mod.rs_decode(ref, par_in, masks, G, k, r, P, nthreads=8)
+    # 1 % iid loss over 10 007 groups: a group one row short needs four losses, and no two are drawn
+    masks_in = _high(masks, k, r, P, need_short=loss > 0.01)
+    ref, _, st_exp = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P, nthreads=8)
     assert np.array_equal(ref.reshape(G, k, P)[st_exp == 0], data.reshape(G, k, P)[st_exp == 0])
     exp = np.full((G, r, P), 0x5A, dtype=np.uint8)
     d3 = data.reshape(G, k, P)
     for g in np.nonzero(st_exp == 0)[0]:
         for m, j in enumerate(np.nonzero(lost[g])[0]):
             exp[g, m] = d3[g, j]
-    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
+    dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks_in.view(np.int64))
     out = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
     st = torch.full((G,), 7, dtype=torch.uint8, device="cuda")
     gpu_ctx.recover_dev(dd, dp, dm, G, k, r, P, out, st)
     gpu_ctx.synchronize()
+    assert _masks_unwritten(dm, masks_in)
     assert np.array_equal(st.cpu().numpy(), st_exp)
     assert np.array_equal(out.cpu().numpy().reshape(G, r, P), exp), us.mismatch(masks, k, r, out.cpu().numpy(), exp)
 
@@ -756,13 +802,18 @@ def test_recover_back_to_back_on_one_stream(gpu_ctx, oracle_mod, torch_cuda, k, 
                 for s in rng.permutation(k + r)[: rng.integers(1, r + 1)]:
                     masks[g] |= np.uint64(1) << np.uint64(int(s))
             broken, par_in = _junked(data, par, masks, G, k, r, P)       # each call its own junked inputs
-            dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks.view(np.int64))
+            # 1 to r losses per group: none is one row short or untouched
+            masks_in = _high(masks, k, r, P + c, need_short=False, need_untouched=False)
+            ref, bad_exp, _ = _oracle_decode(oracle_mod, broken, par_in, masks, masks_in, G, k, r, P, nthreads=8)
+            assert bad_exp == 0 and np.array_equal(ref, data)
+            dd, dp, dm = _dev(torch, broken), _dev(torch, par_in), _dev(torch, masks_in.view(np.int64))
             out = torch.zeros(G * r * P, dtype=torch.uint8, device="cuda")
             gpu_ctx.recover_dev(dd, dp, dm, G, k, r, P, out, None, stream=stream.cuda_stream)
-            runs.append((masks, (dd, dp, dm), out))
+            runs.append((masks, (dd, dp, dm), out, masks_in))
     stream.synchronize()
     d3 = data.reshape(G, k, P)
-    for masks, _, out in runs:
+    for masks, (_, _, dm), out, masks_in in runs:
+        assert _masks_unwritten(dm, masks_in)
         o3 = out.cpu().numpy().reshape(G, r, P)
         for g in range(0, G, 7):
             lost = [j for j in range(k) if (int(masks[g]) >> j) & 1]

@@ -87,8 +87,12 @@ class Case:
         # what a decode is given: junk in every lost data shard and every parity row the rule does
         # not read (every shape here has r > 1, so every case has a lost row below a chosen one)
         self.broken, self.par_in = us.inputs(data, self.par, masks, k, r, P, seed)
-        ref = self.broken.copy()
-        _, self.status = oracle.rs_decode(ref, self.par_in, masks, G, k, r, P, nthreads=8)
+        # what a decode is given as masks: junk in the bits at and above k + r, which the rule ignores
+        self.masks_in = us.high_bits(masks, k, r, seed)
+        ref, clean = self.broken.copy(), self.broken.copy()
+        _, self.status = oracle.rs_decode(ref, self.par_in, self.masks_in, G, k, r, P, nthreads=8)
+        _, clean_status = oracle.rs_decode(clean, self.par_in, masks, G, k, r, P, nthreads=8)
+        assert np.array_equal(clean, ref) and np.array_equal(clean_status, self.status)   # the oracle ignores them
         self.ref = ref                                    # in-place result
         ok = self.status == 0
         # the oracle's rebuilt packets are the original ones
@@ -102,7 +106,7 @@ class Case:
         self.row_end = np.cumsum(per_group)
         self.row_start = np.concatenate([[0], self.row_end[:-1]]).astype(np.uint32)
         for a in (self.data, self.par, self.par_in, self.broken, self.ref, self.status, self.rows, self.slots,
-                  self.row_start, self.masks):
+                  self.row_start, self.masks, self.masks_in):
             a.setflags(write=False)
 
     def head(self, G):
@@ -113,7 +117,8 @@ class Case:
         assert 3 <= G < self.G
         k, r, P = self.k, self.r, self.P
         n = int(self.row_end[G - 1])
-        return SimpleNamespace(k=k, r=r, P=P, G=G, seed=self.seed, masks=self.masks[:G], data=self.data[:G * k * P],
+        return SimpleNamespace(k=k, r=r, P=P, G=G, seed=self.seed, masks=self.masks[:G], masks_in=self.masks_in[:G],
+                               data=self.data[:G * k * P],
                                par=self.par[:G * r * P], par_in=self.par_in[:G * r * P], broken=self.broken[:G * k * P],
                                ref=self.ref[:G * k * P],
                                status=self.status[:G], rows=self.rows[:n], slots=self.slots[:G],
@@ -161,8 +166,8 @@ def _dev(torch, a):
 
 
 def upload(torch, c):
-    """Fresh device copies of a case's inputs (junk in every shard the rule does not read)."""
-    return _dev(torch, c.broken), _dev(torch, c.par_in), _dev(torch, c.masks.view(np.int64))
+    """Fresh device copies of a case's inputs (junk in every shard and mask bit the rule does not read)."""
+    return _dev(torch, c.broken), _dev(torch, c.par_in), _dev(torch, c.masks_in.view(np.int64))
 
 
 def make_call(torch, c, api, inputs=None, env=None):
@@ -204,7 +209,7 @@ def check_inputs(c, dd, dp, dm):
     """The recover calls only read: data, parity (the junk of both included) and masks unchanged."""
     assert np.array_equal(dd.cpu().numpy()[:c.G * c.k * c.P], c.broken)
     assert np.array_equal(dp.cpu().numpy()[:c.G * c.r * c.P], c.par_in)
-    assert np.array_equal(dm.cpu().numpy().view(np.uint64)[:c.G], c.masks)
+    assert np.array_equal(dm.cpu().numpy().view(np.uint64)[:c.G], c.masks_in)
 
 
 def check(b, what=""):
@@ -212,6 +217,7 @@ def check(b, what=""):
     c = b.c
     k, r, P, G = c.k, c.r, c.P, c.G
     assert np.array_equal(b.st.cpu().numpy(), c.status), what
+    assert np.array_equal(b.dm.cpu().numpy().view(np.uint64)[:G], c.masks_in), what       # masks only read, junk bits included
     if b.api == "in_place":
         assert np.array_equal(b.dd.cpu().numpy(), c.ref), (what, us.mismatch(c.masks, k, r, b.dd.cpu().numpy(), c.ref))
         assert np.array_equal(b.dp.cpu().numpy(), c.par_in), what
@@ -487,7 +493,7 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda, k, 
     ro = us.roles(c.masks, k, r)
     d_junk_d, d_junk_p = _dev(torch, ro.lost_d), _dev(torch, ro.unread_p)       # which shards get junk
     d_broken, d_par_in = _dev(torch, c.broken).view(G, k, P), _dev(torch, c.par_in).view(G, r, P)   # where it comes from
-    d_masks_src = _dev(torch, c.masks.view(np.int64))
+    d_masks_src = _dev(torch, c.masks_in.view(np.int64))
     dd = torch.full((G * k * P,), 0x11, dtype=torch.uint8, device="cuda")
     par = torch.full((G * r * P,), 0x5A, dtype=torch.uint8, device="cuda")
     dm = torch.full((G,), -1, dtype=torch.int64, device="cuda")
@@ -518,7 +524,7 @@ def test_queued_pipeline_on_side_stream(quicfec_mod, oracle_mod, torch_cuda, k, 
         ctx.decode_dev(dd, par, dm, G, k, r, P, st, stream=s)
         torch.cuda.synchronize()
     assert np.array_equal(par_made.cpu().numpy(), c.par)
-    assert np.array_equal(dm.cpu().numpy().view(np.uint64), c.masks)
+    assert np.array_equal(dm.cpu().numpy().view(np.uint64), c.masks_in)
     assert np.array_equal(st.cpu().numpy(), c.status)
     assert np.array_equal(dd.cpu().numpy(), c.ref)
     assert np.array_equal(par.cpu().numpy(), c.par_in)                 # chosen rows as encoded, the rest junk still

@@ -6,6 +6,11 @@ lowest surviving parity rows"; include/fec_hip.h: "a lost shard's entry, and a p
 does not use, is never read".  The GPU tests hold the library to the oracle on inputs with junk in
 every such shard; here the oracle itself is held to the original data on them, `roles` to a plain
 loop, and a deliberately wrong decoder shows what true bytes in lost rows let through.
+
+fec_mask.hpp again: "Bits at and above k + r are ignored."  The GPU tests hand over masks with junk
+up there (`high_bits`); here the helper's promises are checked, the oracle is held to say the same
+with and without the junk, and four deliberately wrong readers of the rule show that clean masks
+let each of them through and the helper's masks do not.
 """
 import numpy as np
 import pytest
@@ -116,6 +121,208 @@ def test_oracle_reads_no_unread_shard_every_mask(oracle_mod, k, r):
 def test_oracle_reads_no_unread_shard_drawn_masks(oracle_mod, k, r):
     """3000 drawn masks at 32 B with junk in the bits at and above k + r."""
     check_oracle(oracle_mod, k, r, 32, drawn_masks(k, r, 3000, k * 100 + r), k * 10 + r)
+
+
+# ---- junk in the mask bits at and above k + r ------------------------------------------------------
+def _every_high(k, r):
+    return np.uint64(((1 << (64 - k - r)) - 1) << (k + r))
+
+
+def test_high_bits_keeps_the_rule_and_plants_its_groups():
+    k, r = 10, 3
+    masks = all_masks(k, r)
+    np.random.default_rng(3).shuffle(masks)
+    out = us.high_bits(masks, k, r, seed=5)
+    low = np.uint64((1 << (k + r)) - 1)
+    assert out.dtype == np.uint64 and out is not masks and np.array_equal(out & low, masks)
+    assert np.array_equal(us.high_bits(masks, k, r, seed=5), out)                  # seeded
+    assert not np.array_equal(us.high_bits(masks, k, r, seed=6), out)
+    assert np.array_equal(us.high_bits(out, k, r, seed=5), out)                    # junk that comes in is replaced
+    high = out & ~low
+    every = _every_high(k, r)
+    share = lambda sel: float(sel.mean())
+    assert 0.2 < share(high == 0) < 0.3 and 0.2 < share(high == every) < 0.3       # a quarter clean, a quarter all set
+    assert len(np.unique(high)) > len(masks) // 3                                  # the rest drawn per group
+    ro, pl = us.roles(masks, k, r), us.planted(masks, k, r, seed=5)
+    assert tuple(pl) == us.PLANTED and len({g for g, _ in pl.values()}) == len(us.PLANTED)     # six distinct groups
+    want = {"full_first": 1 << (k + r), "full_all": int(every), "full_top": 1 << 63,
+            "short_all_but_first": int(every) & ~(1 << (k + r)), "short_clean": 0, "untouched_all": int(every)}
+    for name, (g, pat) in pl.items():
+        assert pat == want[name] and int(high[g]) == pat, name
+        kind = us.full_groups if name.startswith("full") else us.short_groups if name.startswith("short") else us.untouched_groups
+        assert kind(ro)[g], name
+    e, alive = ro.lost_d.sum(axis=1), (~ro.lost_p).sum(axis=1)
+    for name in us.PLANTED[:3]:
+        g = pl[name][0]
+        assert ro.ok[g] and e[g] >= 1 and e[g] == alive[g]
+    for name in us.PLANTED[3:5]:
+        g = pl[name][0]
+        assert not ro.ok[g] and e[g] == alive[g] + 1
+    assert masks[pl["untouched_all"][0]] == 0
+    # k + r = 64: no such bit, a copy, and no condition is checked
+    one = np.array([1], dtype=np.uint64)
+    same = us.high_bits(one, 60, 4, seed=1)
+    assert np.array_equal(same, one) and same is not one
+    # a case without the groups is refused unless the caller says it has none
+    lost_two = np.array([0b11] * 8, dtype=np.uint64)                               # e = 2, three rows alive
+    for need in ({}, dict(need_full=False), dict(need_full=False, need_short=False)):
+        with pytest.raises(AssertionError):
+            us.high_bits(lost_two, k, r, seed=1, **need)
+    got = us.high_bits(lost_two, k, r, seed=1, need_full=False, need_short=False, need_untouched=False)
+    assert np.array_equal(got & low, lost_two)
+    two_full = np.array([0b111, 0b111, 0], dtype=np.uint64)                        # three are planted, not two
+    with pytest.raises(AssertionError):
+        us.high_bits(two_full, k, r, seed=1, need_short=False)
+    us.high_bits(two_full, k, r, seed=1, need_full=False, need_short=False)
+
+
+def check_oracle_ignores(oracle, k, r, P, masks, masks_in, seed):
+    """rs_decode and rs_decode_fast: byte-identical data, statuses and counts for masks_in and masks."""
+    G = len(masks)
+    low = np.uint64((1 << (k + r)) - 1)
+    assert np.array_equal(masks_in & low, masks) and (masks_in != masks).any()
+    data = oracle.splitmix_bytes(G * k * P, 0x5EED9100 + seed)
+    par = oracle.rs_encode(data, G, k, r, P, nthreads=8)
+    d_in, p_in = us.inputs(data, par, masks, k, r, P, seed, need_lost_below=r > 1)
+    for decode in (oracle.rs_decode, oracle.rs_decode_fast):
+        got = []
+        for m in (masks, masks_in):
+            out, p, m = d_in.copy(), p_in.copy(), m.copy()
+            bad, st = decode(out, p, m, G, k, r, P, nthreads=8)
+            got.append((out, st, bad, p))
+        (o0, s0, b0, p0), (o1, s1, b1, p1) = got
+        assert b0 == b1 and np.array_equal(s0, s1), (decode.__name__, us.mismatch(masks, k, r, s1, s0))
+        assert np.array_equal(o0, o1), (decode.__name__, us.mismatch(masks, k, r, o1, o0))
+        assert np.array_equal(p0, p_in) and np.array_equal(p1, p_in)
+
+
+def junk_patterns(masks, k, r, seed):
+    """The three patterns of the GPU every-mask passes: only bit k + r, every high bit, the helper's draw."""
+    return {"first": masks | np.uint64(1 << (k + r)), "every": masks | _every_high(k, r),
+            "drawn": us.high_bits(masks, k, r, seed)}
+
+
+@pytest.mark.parametrize("pattern", ["first", "every", "drawn"])
+@pytest.mark.parametrize("k,r", EXHAUSTIVE)
+def test_oracle_ignores_high_bits_every_mask(oracle_mod, k, r, pattern):
+    """Every mask at 48 B with junk at and above k + r: the oracle says what it says without it."""
+    masks = all_masks(k, r)
+    check_oracle_ignores(oracle_mod, k, r, 48, masks, junk_patterns(masks, k, r, k * 10 + r)[pattern], k * 10 + r)
+
+
+@pytest.mark.parametrize("pattern", ["first", "every", "drawn"])
+@pytest.mark.parametrize("k,r", [s for s in DRAWN if sum(s) < 64])
+def test_oracle_ignores_high_bits_drawn_masks(oracle_mod, k, r, pattern):
+    """3000 drawn masks at 32 B, the shapes with a bit to spare."""
+    masks = drawn_masks(k, r, 3000, k * 100 + r) & np.uint64((1 << (k + r)) - 1)
+    check_oracle_ignores(oracle_mod, k, r, 32, masks, junk_patterns(masks, k, r, k * 10 + r)[pattern], k * 10 + r)
+
+
+# ---- four wrong readers of "bits at and above k + r are ignored" ----------------------------------
+def _pop(x):
+    return bin(x).count("1")
+
+
+def wrong_reader(kind, m, k, r):
+    """(ok, chosen rows, untouched) of mask m as one wrong restatement of the rule reads it, written
+    like the kernels' hand-written copy (fec_decode_fused.hip fused_group): e = popc(m & kmask),
+    pm = (m >> k) & rmask, bad = e > r - popc(pm), rows = the e lowest bits of ~pm & rmask.
+      lost_unmasked  pm without `& rmask` in the count: junk bits count as lost rows
+      wide           rmask one bit too wide in the count: bit k + r counts as a lost row
+      alive_unmasked both `& rmask` gone and the kernel's own uint32 arithmetic: enough junk wraps
+                     r - popc(pm), the group is accepted, and a clear bit k + r is 'surviving row r'
+      zero           'nothing lost' judged from m == 0"""
+    kmask, rmask, u64 = (1 << k) - 1, (1 << r) - 1, (1 << 64) - 1
+    e = _pop(m & kmask)
+    pm, alive = (m >> k) & rmask, ~(m >> k) & rmask
+    if kind == "lost_unmasked":
+        ok = e <= r - _pop(m >> k)
+    elif kind == "wide":
+        ok = e <= r - _pop((m >> k) & ((1 << (r + 1)) - 1))
+    elif kind == "alive_unmasked":
+        ok = e <= (r - _pop(m >> k)) % (1 << 32)
+        alive = ~(m >> k) & u64
+    else:
+        ok = e <= r - _pop(pm)
+    rows = []
+    if ok and e >= 1:
+        for _ in range(e):
+            rows.append((alive & -alive).bit_length() - 1)
+            alive &= alive - 1
+    untouched = m == 0 if kind == "zero" else (m & ((1 << (k + r)) - 1)) == 0
+    return ok, tuple(rows), untouched
+
+
+# the planted group each wrong reader trips on
+TRIPS_ON = {"lost_unmasked": "full_top", "wide": "full_first", "alive_unmasked": "short_all_but_first", "zero": "untouched_all"}
+
+
+def disagreements(kind, masks, k, r):
+    """Groups where the reader and `roles` differ in status, chosen rows or 'nothing lost'."""
+    ro = us.roles(masks, k, r)
+    untouched = us.untouched_groups(ro)
+    out = []
+    for g, m in enumerate(int(x) for x in masks):
+        truth = (bool(ro.ok[g]), tuple(np.flatnonzero(ro.chosen[g]).tolist()), bool(untouched[g]))
+        if wrong_reader(kind, m, k, r) != truth:
+            out.append(g)
+    return out
+
+
+def check_readers_trip(masks, k, r, seed):
+    masks_in = us.high_bits(masks, k, r, seed)
+    pl = us.planted(masks, k, r, seed)
+    for kind, name in TRIPS_ON.items():
+        wrong = disagreements(kind, masks_in, k, r)
+        assert pl[name][0] in wrong, (kind, name, k, r)
+    # what each planted pattern does to its reader
+    g = pl["full_top"][0]
+    assert wrong_reader("lost_unmasked", int(masks_in[g]), k, r)[0] is False          # a good group refused
+    assert wrong_reader("wide", int(masks_in[g]), k, r)[0] is True                    # bit 63 is outside the wide mask
+    assert wrong_reader("wide", int(masks_in[pl["full_first"][0]]), k, r)[0] is False
+    assert wrong_reader("lost_unmasked", int(masks_in[pl["full_all"][0]]), k, r)[0] is False
+    g = pl["short_all_but_first"][0]
+    ok, rows, _ = wrong_reader("alive_unmasked", int(masks_in[g]), k, r)
+    assert ok and rows[-1] == r                                                       # rebuilt from past the parity rows
+    for kind in TRIPS_ON:                                                             # the clean short group: refused by all
+        assert wrong_reader(kind, int(masks_in[pl["short_clean"][0]]), k, r)[0] is False
+    assert wrong_reader("zero", int(masks_in[pl["untouched_all"][0]]), k, r)[2] is False
+    return masks_in
+
+
+@pytest.mark.parametrize("k,r", [(4, 2), (10, 3)])
+def test_control_wrong_readers_pass_clean_masks_and_fail_junk(k, r):
+    """Each wrong reader agrees with `roles` on every clean mask -- what the GPU every-mask pass used
+    to hand over -- and disagrees on the helper's masks, on the group planted for it.  (With only the
+    guard of the row pick gone and the status right, a reader is the rule: the pick of a recoverable
+    group never leaves the r rows.  That guard shows only together with a wrong status.)"""
+    masks = all_masks(k, r)
+    for kind in TRIPS_ON:
+        assert disagreements(kind, masks, k, r) == [], kind
+    masks_in = check_readers_trip(masks, k, r, seed=k * 10 + r)
+    ro, rmask = us.roles(masks_in, k, r), (1 << r) - 1
+    for g in np.flatnonzero(ro.ok & ro.lost_d.any(axis=1)):                           # the pick alone, unmasked: the same rows
+        alive, rows = ~(int(masks_in[g]) >> k) & ((1 << 64) - 1), []
+        for _ in range(int(ro.lost_d[g].sum())):
+            rows.append((alive & -alive).bit_length() - 1)
+            alive &= alive - 1
+        assert rows == np.flatnonzero(ro.chosen[g]).tolist() and max(rows) < r and (1 << max(rows)) & rmask
+
+
+def test_control_wrong_readers_fail_the_gpu_cases_masks():
+    """The same on the masks the GPU decode matrix hands over: perm_masks of the five shapes at their
+    real group counts and seeds (both ends of the size list and 1024 B), through the helper as Case
+    applies it."""
+    import test_gpu_forms as forms
+    for k, r in forms.DECODE_SHAPES:
+        G = 261 if (k, r) == (20, 5) else 1031
+        for P in (forms.DECODE_P[0], 1024, forms.DECODE_P[-1]):
+            masks = forms.perm_masks(k, r, G, k * 1000 + r * 100 + P)
+            for kind in TRIPS_ON:
+                assert disagreements(kind, masks, k, r) == [], (kind, k, r, P)
+            masks_in = check_readers_trip(masks, k, r, forms.SEED + k * 31 + r * 7 + P)
+            # many groups, not only the planted ones
+            assert len(disagreements("lost_unmasked", masks_in, k, r)) > G // 20
 
 
 # ---- the definition's own decode, and a wrong one -------------------------------------------------

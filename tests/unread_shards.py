@@ -7,6 +7,14 @@ that picks its rows wrongly but consistently, so the decode cases of the suite t
 from here: seeded per-byte random junk in every lost data shard and in every parity row that is
 not chosen (lost rows, surviving rows past the e-th, every row of a group that rebuilds nothing).
 
+The masks have a part the rule does not read either: "bits at and above k + r are ignored".  A
+receiver that keeps one u64 per group has no reason to clear them, and a case whose masks come
+clean up there cannot see a decoder that counts or picks rows from an unmasked `m >> k`.  So the
+decode cases hand over `high_bits(masks, ...)`: the same bits below k + r, seeded junk above, with
+groups planted where such a decoder shows (full: every surviving row used, one more row believed
+lost and the group is refused; short: one row missing, one more row believed alive and it is
+rebuilt from past the parity rows; untouched: no bit below k + r).
+
 `roles` is written in numpy from the sentences of fec_mask.hpp; it calls neither the library nor
 the oracle.  A plain module like forms_support.py: no fixtures, no tests.
 """
@@ -78,6 +86,83 @@ def inputs(data, par, masks, k, r, P, seed, need_lost_below=True, need_unchosen_
     if need_unchosen_alive:
         assert has_unchosen_alive_row(ro).any(), "no group with a surviving parity row the rule does not use"
     return d_in.reshape(-1), p_in.reshape(-1)
+
+
+_HIGH_SALT = 0x41B175
+# the planted groups of high_bits, in the order they are drawn
+PLANTED = ("full_first", "full_all", "full_top", "short_all_but_first", "short_clean", "untouched_all")
+
+
+def full_groups(ro):
+    """Recoverable groups that use every surviving row: e >= 1 and e == surviving rows.  One more
+    row believed lost and they are refused."""
+    e = ro.lost_d.sum(axis=1)
+    return ro.ok & (e >= 1) & (e == (~ro.lost_p).sum(axis=1))
+
+
+def short_groups(ro):
+    """Unrecoverable groups one row short: e == surviving rows + 1.  One more row believed alive
+    and they are rebuilt, from a row that does not exist."""
+    return ro.lost_d.sum(axis=1) == (~ro.lost_p).sum(axis=1) + 1
+
+
+def untouched_groups(ro):
+    """Groups with no bit set below k + r."""
+    return ~ro.lost_d.any(axis=1) & ~ro.lost_p.any(axis=1)
+
+
+def planted(masks, k, r, seed, need_full=True, need_short=True, need_untouched=True):
+    """{name: (group, high bits as an int already shifted to k + r)} of the groups high_bits
+    plants, distinct groups drawn from the seed.  A kind the case does not hold (fewer than three
+    full groups, two short ones, one untouched one) is an assertion unless need_* says so; then
+    as many as exist are planted."""
+    n_high = 64 - k - r
+    if n_high <= 0:
+        return {}
+    every = ((1 << n_high) - 1) << (k + r)
+    first, top = 1 << (k + r), 1 << 63
+    ro = roles(masks, k, r)
+    rng = np.random.default_rng([_HIGH_SALT, 1, int(seed) & 0xFFFFFFFFFFFFFFFF])
+    out = {}
+    for kind, need, names, pats in (
+            (full_groups(ro), need_full, PLANTED[0:3], (first, every, top)),
+            (short_groups(ro), need_short, PLANTED[3:5], (every & ~first, 0)),
+            (untouched_groups(ro), need_untouched, PLANTED[5:6], (every,))):
+        found = np.flatnonzero(kind)
+        if need:
+            assert len(found) >= len(names), f"{len(found)} groups for {names}: the case cannot plant them"
+        picks = rng.permutation(found)[:len(names)]
+        out.update({name: (int(g), pat) for name, g, pat in zip(names, picks, pats)})
+    return out
+
+
+def high_bits(masks, k, r, seed, need_full=True, need_short=True, need_untouched=True):
+    """masks with seeded junk in the bits at and above k + r, which the rule ignores: bits below
+    k + r as given.  Per group a quarter stay clean, a quarter get every high bit, the rest random
+    ones; then the groups of `planted` get exactly their pattern: three full groups (junk only bit
+    k + r, every high bit, only bit 63), two short ones (every high bit but k + r, none) and an
+    untouched one (every high bit).  A case that cannot hold a kind says so with its reason
+    (need_* = False, as for `inputs`).  k + r = 64 has no such bit: a copy, nothing checked."""
+    m = np.array(masks, dtype=np.uint64).reshape(-1)
+    n_high = 64 - k - r
+    if n_high <= 0:
+        return m
+    G = len(m)
+    rng = np.random.default_rng([_HIGH_SALT, 0, int(seed) & 0xFFFFFFFFFFFFFFFF])
+    coin = rng.random(G)
+    high = rng.integers(0, np.iinfo(np.uint64).max, size=G, dtype=np.uint64, endpoint=True)
+    high = (high >> np.uint64(k + r)) << np.uint64(k + r)
+    every = np.uint64(((1 << n_high) - 1) << (k + r))
+    high[coin < 0.25] = 0
+    high[(coin >= 0.25) & (coin < 0.5)] = every
+    for g, pat in planted(m, k, r, seed, need_full, need_short, need_untouched).values():
+        high[g] = pat
+    low = np.uint64((1 << (k + r)) - 1)
+    out = (m & low) | high
+    assert np.array_equal(out & low, m & low)
+    a, b = roles(m, k, r), roles(out, k, r)
+    assert all(np.array_equal(getattr(a, f), getattr(b, f)) for f in ("lost_d", "lost_p", "chosen", "unread_p", "ok"))
+    return out
 
 
 def describe(ro, masks, k, r, wrong):
