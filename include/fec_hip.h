@@ -13,7 +13,10 @@
  *   data   : G*k*P bytes, data shard (g,j) at (g*k + j)*P
  *   parity : G*r*P bytes, parity row (g,i) at (g*r + i)*P
  * Erasure mask of a group: bit s set (s < k+r) => shard s lost; s < k is data shard s,
- * s >= k is parity row s-k.  Decode requires k + r <= 64.
+ * s >= k is parity row s-k.  Every decode, recover and batcher call that takes one u64 mask per
+ * group (or derives one from an address table) requires k + r <= 64; the two wide calls
+ * (fec_decode_wide_rs_dev, fec_recover_wide_rs_dev) take four u64 per group and serve k + r <= 256
+ * with min(k, r) <= 32.
  *
  * Decode rule: erased data shards are rebuilt in place in `data` from every surviving
  * data shard plus the lowest-indexed surviving parity rows (as many as there are erased
@@ -117,6 +120,43 @@ int fec_decode_batch_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* 
 int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
                              const uint64_t* d_erasure_masks, uint64_t num_groups, uint32_t k, uint32_t r,
                              uint32_t packet_size, uint8_t* d_rebuilt, uint8_t* d_status, void* stream);
+
+/* ---- wide shapes: decode what encode accepts, k + r <= 256 ----
+ * fec_decode_batch_rs_dev and fec_recover_batch_rs_dev for groups of more than 64 shards: the same
+ * layouts, status bytes and stream behaviour, with an erasure mask of FEC_WIDE_MASK_WORDS u64 per
+ * group.
+ *   - Masks: group g's words are d_erasure_masks[4g .. 4g + 3]; shard s is bit s & 63 of word
+ *     s >> 6.  The rule is the one-word rule: data shards are bits 0..k-1, parity rows are bits
+ *     k..k+r-1; bits at and above k + r are ignored, in the partial word and in the whole words
+ *     above it; a group is unrecoverable when fewer parity rows survive than data shards are lost;
+ *     the survivors read are the surviving data shards and the lowest-indexed surviving parity
+ *     rows, as many as data shards are lost.  The masks are only read.
+ *   - fec_decode_wide_rs_dev rebuilds in place in d_data.  fec_recover_wide_rs_dev only reads
+ *     d_data and writes the m-th lost data shard of group g (ascending) to d_rebuilt + (g*r + m)*P;
+ *     slots m >= e of a group and every slot of an unrecoverable group are left unwritten.
+ *     d_status (nullable): one byte per group, every one written, 0 or 1 as above.
+ *   - Asynchronous on `stream` (NULL = the context's own); fec_encoder_free drains them like every
+ *     _dev call.  The recovery records are built on the device per call, in the caller stream's
+ *     workspace (at most 64 MiB of records at a time; larger calls are walked in chunks), whatever
+ *     fec_decode_plan_mode says: there is no codebook and no host synchronise for a wide shape.
+ *   - Served: k >= 1, r >= 1, k + r <= 256, min(k, r) <= 32, packet_size >= 16,
+ *     0 < num_groups < 2^32.  Shapes with k + r <= 64 are served too, and give byte for byte what
+ *     the one-word calls give, whatever words 1..3 hold.
+ *   - Why min(k, r) <= 32: a group with e lost data shards needs the inverse of an e x e matrix,
+ *     e <= min(k, r), which one wave computes in its slice of a compute unit's local memory.  At
+ *     e = 32 the slice is about 9.5 KiB; at e = 128 it would be 48 KiB per wave, 192 KiB for a
+ *     workgroup of four waves, and a compute unit has 160 KiB.
+ * Refusals launch nothing and write nothing (fec_hip_last_error names the case): FEC_ERR_NULL for a
+ * NULL context or required pointer; FEC_ERR_RANGE for k = 0, r = 0, k + r > 256, min(k, r) > 32,
+ * packet_size < 16, num_groups == 0 or >= 2^32.  There are no host-pointer, batcher, packed or
+ * address-table forms of the wide calls. */
+#define FEC_WIDE_MASK_WORDS 4
+int fec_decode_wide_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
+                           const uint64_t* d_erasure_masks, uint64_t num_groups, uint32_t k, uint32_t r,
+                           uint32_t packet_size, uint8_t* d_status, void* stream);
+int fec_recover_wide_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
+                            const uint64_t* d_erasure_masks, uint64_t num_groups, uint32_t k, uint32_t r,
+                            uint32_t packet_size, uint8_t* d_rebuilt, uint8_t* d_status, void* stream);
 
 /* Build (and upload) the decode codebook for (k, r) ahead of the first decode.  The
  * codebook holds the recovery tables of every recoverable erasure pattern; its size is

@@ -606,6 +606,61 @@ inline TableRecoverLaunch plan_chunk(const TableRecoverLaunch& a, uint64_t g0, u
   return c;
 }
 
+// ---- wide shapes: k + r <= 256 with four-word masks (fec_decode_wide_rs_dev, fec_recover_wide_rs_dev;
+// fec_wide.hip, fec_mask_wide.hpp, fec_plan_build_wide.hpp) ----
+// A wide shape is one more shape without a codebook: every call builds its records on the device,
+// whatever fec_decode_plan_mode says, into an arena sized by plan_arena's arithmetic with the wide
+// slot below.  The record builder inverts an e x e matrix in a per-wave LDS slice, e <= min(k, r):
+// about 9.5 KiB at e = 32; e = 128 would take 48 KiB per wave, 192 KiB for a workgroup of four
+// waves against the CU's 160 KiB.  Hence min(k, r) <= 32.
+constexpr uint32_t kWideMaxShards = 256;
+constexpr uint32_t kWideMaxRows = 32;      // min(k, r), so e
+constexpr uint64_t kWideHeader = 512;      // fec_plan_build_wide.hpp kWideHeaderBytes
+constexpr uint32_t kWidePassRows = 8;      // rows per pass of decode_wide (decode_piece<0, 8>)
+// Whether the wide calls serve (k, r, P, G), and if not, why: the one statement of that rule.
+enum class WideRefusal : int { kServed = 0, kShape, kRows, kPacket, kNoGroups, kGroups };
+constexpr WideRefusal wide_served(uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  if (k == 0 || r == 0 || uint64_t{k} + r > kWideMaxShards) return WideRefusal::kShape;
+  if ((k < r ? k : r) > kWideMaxRows) return WideRefusal::kRows;
+  if (P < kVecMinP) return WideRefusal::kPacket;
+  if (G == 0) return WideRefusal::kNoGroups;
+  if (G >= (1ull << 32)) return WideRefusal::kGroups;
+  return WideRefusal::kServed;
+}
+// A slot holds the largest wide record of the shape: 229,888 B at 224 + 32, so kPlanArenaBytes holds
+// 291 groups per chunk there.
+constexpr uint64_t wide_slot_stride(uint32_t k, uint32_t r) { return kWideHeader + uint64_t{k < r ? k : r} * k * 32u; }
+// plan_arena with the wide slot: max(1, budget / stride) slots, at most G.
+inline PlanArena wide_arena(uint32_t k, uint32_t r, uint64_t G, uint64_t budget) {
+  const uint64_t stride = wide_slot_stride(k, r);
+  uint64_t per = budget / stride;
+  if (per == 0) per = 1;
+  if (per > G) per = G;
+  return {stride, per, per * stride};
+}
+// The workspace of a wide call, in the caller stream's stream_workspace: G record offsets, then the
+// arena (plan_workspace without masks or symbol lengths of its own: the masks are the caller's).
+inline PlanWorkspace wide_workspace(uint64_t G, const PlanArena& a) { return plan_workspace(G, false, false, a); }
+// Row passes of a wide call's decode_wide per plan chunk.
+constexpr uint32_t wide_passes(uint32_t k, uint32_t r) { return ((k < r ? k : r) + kWidePassRows - 1) / kWidePassRows; }
+// The policy bits of decode_wide: those of the runtime-k decode_wave<0, 8> forms decode_form picks
+// for the two layouts (in place; the recover's slots).
+constexpr int kWidePolInPlace = kNtStore | kNoCoefBranch;
+constexpr int kWidePolSlots = kNtStore | kNoCoefBranch | kCompactOut;
+// One wide call (fec_wide.hip launch_decode_wide).
+struct WideLaunch {
+  const uint8_t* data;       // the data shards, only read when out != nullptr
+  const uint8_t* parity;
+  uint8_t* out;              // in place: the data shards again; slots: row (g, m) at (g * r + m) * P
+  bool slots;                // the recover's layout
+  const uint64_t* masks;     // four words per group, only read
+  uint32_t* rec_off;         // workspace, one u32 per group
+  uint8_t* status;           // nullable
+  uint64_t groups;
+  uint32_t k, r, P;
+  PlanLaunch plan;           // arena, stride = wide_slot_stride, per_chunk, the r x k matrix
+};
+
 // The passes of a runtime-k encode: at most kEncodePassRows parity rows per launch, pass p the rows
 // [p * 8, min(r, p * 8 + 8)), the first pass owning the XOR row.  The rule of encode_v16<0, R> (the
 // route the fixed-length gather encode takes for every shape but k=10 r=1) and of the table

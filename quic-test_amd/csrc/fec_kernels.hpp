@@ -2,7 +2,7 @@
 // gfx950 kernels, one translation unit per kernel family: fec_encode.hip, fec_decode.hip,
 // fec_decode_fused.hip, fec_runs.hip, fec_server.hip, fec_util.hip; the address-table units
 // fec_gather.hip, fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip with their shared
-// fec_table.hpp; fec_plan.hip.  Internal to libfec_hip.so.
+// fec_table.hpp; fec_plan.hip; fec_wide.hip.  Internal to libfec_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -69,6 +69,10 @@ hipError_t launch_encode_scatter(const TableEncodeLaunch& a, hipStream_t s);
 // chunk's place in the call, for the launch trace.
 hipError_t launch_build_records(const PlanLaunch& p, const uint64_t* masks, uint32_t* rec_off, uint8_t* status,
                                 uint64_t first_group, uint64_t groups, uint32_t k, uint32_t r, hipStream_t s);
+// The wide calls (fec_wide.hip; k + r <= 256, four mask words per group): classify_wide over every
+// group, then per chunk of a.plan's arena build_records_wide and wide_passes(k, r) launches of
+// decode_wide, in stream order.
+hipError_t launch_decode_wide(const WideLaunch& a, hipStream_t s);
 // Packed recover rows (fec_runs.hip): row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.

@@ -110,6 +110,14 @@ enum class PlanLaunchForm : int64_t {
                        // arena slot of the launch's first group
 };
 
+// The kernels of the wide calls (fec_wide.hip), numbered on in a list of their own; named by
+// quicfec.WIDE_LAUNCH_FORMS.
+enum class WideLaunchForm : int64_t {
+  kClassifyWide = 27,      // first_item / items: the launch's first group and its groups
+  kBuildRecordsWide = 28,  // as kBuildRecords: the plan chunk's groups; aux: the arena slot of the first
+  kDecodeWide = 29,        // first_item / items: groups of the call; k = 0, r = 8; pol; aux: first row of the pass
+};
+
 // One launch: 16 words, -1 where a field does not apply to the form.
 struct LaunchRecord {
   int64_t form;          // LaunchForm

@@ -312,6 +312,8 @@ struct FECEncoderCtx {
   PipeSlot pipe[kPipeSlots];
   std::map<std::pair<uint32_t, uint32_t>, std::unique_ptr<EncodePlan>> enc_plans;
   std::map<std::pair<uint32_t, uint32_t>, std::unique_ptr<DecodePlan>> dec_plans;
+  // the r x k parity matrix on the device, one per shape the wide calls met (wide_call)
+  std::map<std::pair<uint32_t, uint32_t>, std::unique_ptr<DevBuf>> wide_matrices;
   // Message of the last failing call on this context (fec_ctx_last_error): callers whose
   // threads migrate between the failing call and the read (Go goroutines) cannot rely on the
   // thread-local fec_hip_last_error.  Own lock: readable while a call holds `mu`.
@@ -362,6 +364,7 @@ struct FECEncoderCtx {
     }
     enc_plans.clear();
     dec_plans.clear();
+    wide_matrices.clear();
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -1692,6 +1695,103 @@ QFEC_EXPORT int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_da
     c.shape = {G, k, r, P}, c.status = d_status, c.stream = pick_stream(ctx, stream);
     c.device_masks = true;
     return decode_dev_locked(ctx, c);
+  });
+}
+
+// ---- wide calls: k + r <= 256, four mask words per group (fec_wide.hip) ----
+namespace {
+
+// What both wide calls do after their own NULL checks.  Refused before any lock or device call:
+// whatever fec_forms.hpp wide_served refuses.  Then, under the context's lock and on its device:
+// the shape's parity matrix on the device (one copy per (k, r), uploaded at the shape's first
+// call), the stream -- a caller's stream counts for fec_encoder_free's drain as in every _dev call,
+// and so does the workspace -- and the caller stream's workspace: G record offsets, then the record
+// arena (wide_workspace).  The records are always built on the device; fec_decode_plan_mode is not
+// consulted.
+int wide_call(const char* what, FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
+              const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P, uint8_t* d_out, bool slots,
+              uint8_t* d_status, void* stream) {
+  switch (qfec::wide_served(G, k, r, P)) {
+    case qfec::WideRefusal::kServed:
+      break;
+    case qfec::WideRefusal::kShape:
+      set_error("%s: unsupported k=%u r=%u (need k>0, r>0, k+r<=%u)", what, k, r, qfec::kWideMaxShards);
+      return FEC_ERR_RANGE;
+    case qfec::WideRefusal::kRows:
+      set_error("%s: k=%u r=%u: min(k, r) exceeds %u rows per group", what, k, r, qfec::kWideMaxRows);
+      return FEC_ERR_RANGE;
+    case qfec::WideRefusal::kPacket:
+      set_error("%s: packet_size %u is below %u bytes", what, P, qfec::kVecMinP);
+      return FEC_ERR_RANGE;
+    case qfec::WideRefusal::kNoGroups:
+      set_error("%s: num_groups is 0", what);
+      return FEC_ERR_RANGE;
+    case qfec::WideRefusal::kGroups:
+      set_error("%s: %llu groups exceed 32-bit group indices", what, static_cast<unsigned long long>(G));
+      return FEC_ERR_RANGE;
+  }
+  CtxBound bound(ctx, what);
+  if (bound.rc != FEC_OK) return bound.rc;
+  auto& matrix = ctx->wide_matrices[std::make_pair(k, r)];
+  if (!matrix) {
+    std::vector<uint8_t> M;
+    if (!qfec::parity_matrix(k, r, M)) {
+      ctx->wide_matrices.erase(std::make_pair(k, r));
+      set_error("%s: no parity matrix for k=%u r=%u", what, k, r);
+      return FEC_ERR_RANGE;
+    }
+    auto buf = std::make_unique<DevBuf>();
+    QFEC_HIP(buf->ensure(M.size()));
+    QFEC_HIP(hipMemcpy(buf->ptr, M.data(), M.size(), hipMemcpyHostToDevice));
+    matrix = std::move(buf);
+  }
+  const hipStream_t s = pick_stream(ctx, stream);
+  const qfec::PlanArena arena = qfec::wide_arena(k, r, G, qfec::plan_arena_budget());
+  const qfec::PlanWorkspace w = qfec::wide_workspace(G, arena);
+  void* ws = nullptr;
+  QFEC_HIP(stream_workspace(ctx, s, w.bytes, &ws));
+  qfec::WideLaunch a{};
+  a.data = d_data;
+  a.parity = d_parity;
+  a.out = d_out;
+  a.slots = slots;
+  a.masks = d_masks;
+  a.rec_off = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws) + w.rec_off);
+  a.status = d_status;
+  a.groups = G;
+  a.k = k, a.r = r, a.P = P;
+  a.plan.arena = static_cast<uint8_t*>(ws) + w.arena;
+  a.plan.stride = arena.stride;
+  a.plan.per_chunk = arena.per_chunk;
+  a.plan.matrix = matrix->as<uint8_t>();
+  QFEC_HIP(qfec::launch_decode_wide(a, s));
+  return FEC_OK;
+}
+
+}  // namespace
+
+QFEC_EXPORT int fec_decode_wide_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
+                                       const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
+                                       uint8_t* d_status, void* stream) {
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_data || !d_parity || !d_masks) {
+      set_error("fec_decode_wide_rs_dev: %s is NULL", !ctx ? "the context" : !d_data ? "d_data" : !d_parity ? "d_parity" : "d_erasure_masks");
+      return FEC_ERR_NULL;
+    }
+    return wide_call("fec_decode_wide_rs_dev", ctx, d_data, d_parity, d_masks, G, k, r, P, d_data, false, d_status, stream);
+  });
+}
+
+QFEC_EXPORT int fec_recover_wide_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
+                                        const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
+                                        uint8_t* d_rebuilt, uint8_t* d_status, void* stream) {
+  return api_call(ctx, [&]() -> int {
+    if (!ctx || !d_data || !d_parity || !d_masks || !d_rebuilt) {
+      set_error("fec_recover_wide_rs_dev: %s is NULL",
+                !ctx ? "the context" : !d_data ? "d_data" : !d_parity ? "d_parity" : !d_masks ? "d_erasure_masks" : "d_rebuilt");
+      return FEC_ERR_NULL;
+    }
+    return wide_call("fec_recover_wide_rs_dev", ctx, d_data, d_parity, d_masks, G, k, r, P, d_rebuilt, true, d_status, stream);
   });
 }
 

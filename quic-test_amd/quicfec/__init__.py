@@ -37,6 +37,8 @@ FEC_ERR_UNRECOVERABLE = -7
 # fec_decode_plan_mode (Context.decode_plan_mode)
 FEC_PLAN_CODEBOOK = 0
 FEC_PLAN_DEVICE = 1
+# u64 words per group of the wide calls' erasure masks (fec_hip.h FEC_WIDE_MASK_WORDS)
+WIDE_MASK_WORDS = 4
 
 # Every function the headers declare (tests check the library exports all of them).
 REFERENCE_SYMBOLS = (
@@ -60,6 +62,7 @@ HIP_SYMBOLS = (
     "fec_recover_gather_rs_dev", "fec_encode_gather_rs_dev",
     "fec_recover_gather_var_rs_dev", "fec_encode_gather_var_rs_dev",
     "fec_recover_scatter_rs_dev", "fec_encode_scatter_rs_dev", "fec_decode_plan_mode",
+    "fec_decode_wide_rs_dev", "fec_recover_wide_rs_dev",
 )
 
 
@@ -159,6 +162,8 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
         "fec_encode_gather_var_rs_dev": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
         "fec_recover_scatter_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
         "fec_encode_scatter_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
+        "fec_decode_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
+        "fec_recover_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -379,6 +384,22 @@ class Context:
         rc = self.lib.fec_encode_scatter_rs_dev(self.handle, _opt(d_packet_addrs), _opt(d_packet_lens), _opt(d_dest_addrs),
                                                 num_groups, k, r, packet_size, _opt(d_symbol_len_out), stream)
         _check(rc, "fec_encode_scatter_rs_dev", self.lib)
+
+    def decode_wide_dev(self, d_data, d_parity, d_masks, num_groups: int, k: int, r: int, packet_size: int,
+                        d_status=None, stream: Optional[int] = None) -> None:
+        """decode_dev for k + r <= 256, min(k, r) <= 32: d_masks holds WIDE_MASK_WORDS u64 per group,
+        shard s at bit s & 63 of word s >> 6."""
+        rc = self.lib.fec_decode_wide_rs_dev(self.handle, _opt(d_data), _opt(d_parity), _opt(d_masks), num_groups, k, r,
+                                             packet_size, _opt(d_status), stream)
+        _check(rc, "fec_decode_wide_rs_dev", self.lib)
+
+    def recover_wide_dev(self, d_data, d_parity, d_masks, num_groups: int, k: int, r: int, packet_size: int,
+                         d_rebuilt, d_status=None, stream: Optional[int] = None) -> None:
+        """recover_dev for k + r <= 256, min(k, r) <= 32, masks as decode_wide_dev: rebuilt shards of
+        group g at d_rebuilt[(g*r + m)*P:...]; d_data is not modified."""
+        rc = self.lib.fec_recover_wide_rs_dev(self.handle, _opt(d_data), _opt(d_parity), _opt(d_masks), num_groups, k, r,
+                                              packet_size, _opt(d_rebuilt), _opt(d_status), stream)
+        _check(rc, "fec_recover_wide_rs_dev", self.lib)
 
     def decode_prepare(self, k: int, r: int) -> int:
         n = ctypes.c_uint64(0)
@@ -635,6 +656,10 @@ SCATTER_ENCODE_LAUNCH_FORMS = {25: "encode_scatter"}
 # the record builder of the device plans (csrc/fec_plan.hip; PlanLaunchForm), again its own:
 # first_item / items = the plan chunk's first group and its groups, aux = the launch's first arena slot
 PLAN_LAUNCH_FORMS = {26: "build_records"}
+# the kernels of the wide calls (csrc/fec_wide.hip; WideLaunchForm), again their own: first_item / items =
+# the launch's first group in the call and its groups; build_records_wide's aux = its first arena slot,
+# decode_wide's = the first row of the pass
+WIDE_LAUNCH_FORMS = {27: "classify_wide", 28: "build_records_wide", 29: "decode_wide"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -663,7 +688,7 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
         rec = dict(zip(LAUNCH_FIELDS, (int(x) for x in row)))
         form = rec["form"]
         for names in (LAUNCH_FORMS, GATHER_LAUNCH_FORMS, GATHER_VAR_LAUNCH_FORMS, SCATTER_LAUNCH_FORMS,
-                      SCATTER_ENCODE_LAUNCH_FORMS, PLAN_LAUNCH_FORMS):
+                      SCATTER_ENCODE_LAUNCH_FORMS, PLAN_LAUNCH_FORMS, WIDE_LAUNCH_FORMS):
             if form in names:
                 rec["form"] = names[form]
         out.append(rec)
