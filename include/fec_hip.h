@@ -14,9 +14,10 @@
  *   parity : G*r*P bytes, parity row (g,i) at (g*r + i)*P
  * Erasure mask of a group: bit s set (s < k+r) => shard s lost; s < k is data shard s,
  * s >= k is parity row s-k.  Every decode, recover and batcher call that takes one u64 mask per
- * group (or derives one from an address table) requires k + r <= 64; the two wide calls
- * (fec_decode_wide_rs_dev, fec_recover_wide_rs_dev) take four u64 per group and serve k + r <= 256
- * with min(k, r) <= 32.
+ * group (or derives one from an address table) requires k + r <= 64; the wide calls
+ * (fec_decode_wide_rs_dev, fec_recover_wide_rs_dev, and from an address table
+ * fec_recover_scatter_wide_rs_dev) work with four u64 per group and serve k + r <= 256 with
+ * min(k, r) <= 32.
  *
  * Decode rule: erased data shards are rebuilt in place in `data` from every surviving
  * data shard plus the lowest-indexed surviving parity rows (as many as there are erased
@@ -148,8 +149,9 @@ int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const ui
  *     workgroup of four waves, and a compute unit has 160 KiB.
  * Refusals launch nothing and write nothing (fec_hip_last_error names the case): FEC_ERR_NULL for a
  * NULL context or required pointer; FEC_ERR_RANGE for k = 0, r = 0, k + r > 256, min(k, r) > 32,
- * packet_size < 16, num_groups == 0 or >= 2^32.  There are no host-pointer, batcher, packed or
- * address-table forms of the wide calls. */
+ * packet_size < 16, num_groups == 0 or >= 2^32.  There are no host-pointer, batcher or packed forms
+ * of the wide calls, and no wide address-table encode; the wide address-table recover is
+ * fec_recover_scatter_wide_rs_dev, below. */
 #define FEC_WIDE_MASK_WORDS 4
 int fec_decode_wide_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
                            const uint64_t* d_erasure_masks, uint64_t num_groups, uint32_t k, uint32_t r,
@@ -288,6 +290,61 @@ int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs
                                uint64_t num_groups, uint32_t k, uint32_t r, uint32_t packet_size,
                                uint8_t* d_status, uint64_t* d_masks_out, uint32_t* d_symbol_len_out,
                                void* stream);
+
+/* ---- wide scatter recover: k + r <= 256 from scattered shards ----
+ * fec_recover_scatter_rs_dev for groups of up to 256 shards: shards taken where they lie in device
+ * memory through a table of addresses, each rebuilt packet written where a table of destinations
+ * says, cut at the group's symbol length.  One call: destinations at d_rebuilt + (g*r + m)*P with a
+ * NULL length table give the slot layout of fec_recover_wide_rs_dev, without its contiguous,
+ * zero-padded copy of every shard and without a mask built by the caller.
+ *   - Served: k >= 1, r >= 1, k + r <= 256, min(k, r) <= 32 (why: see the wide calls above),
+ *     packet_size >= 16, 0 < num_groups < 2^32.  Shapes with k + r <= 64 are served too and give
+ *     byte for byte what fec_recover_scatter_rs_dev gives for the same tables.
+ *   - d_shard_addrs: num_groups*(k+r) absolute device addresses (u64), entry [g*(k+r) + s] for shard
+ *     s of group g (s < k: data shard s; else parity row s - k), any byte alignment.  Address 0 is
+ *     the only loss marker.  The table is only read.
+ *   - d_shard_lens (nullable): num_groups*(k+r) u32, indexed alike: the readable bytes of each
+ *     present shard.  A lost entry's length is ignored.  A length above P is clamped to P.  Shard
+ *     (g, s) stands for the P-byte symbol whose bytes [0, min(len, P)) are the bytes at its address
+ *     and whose other bytes are zero.  No byte at or past address + len is read, and a present shard
+ *     of length 0 is never dereferenced.  NULL: every present shard has P bytes.
+ *   - Decode rule: the one-word rule over the mask the zero addresses imply.  A group is
+ *     unrecoverable when fewer parity rows are present than data shards are lost.  The survivors
+ *     read are the present data shards and the lowest-indexed present parity rows, as many as data
+ *     shards are lost.  A lost shard's source entry is never dereferenced (it is 0), and neither is
+ *     a present parity row the rule does not use.
+ *   - d_symbol_len_out (nullable, u32 per group), written for every group when given: L_g, the
+ *     largest min(len, P) over the group's present entries (P without a length table), 0 when none
+ *     is present.
+ *   - d_dest_addrs: num_groups*k absolute device addresses (u64), entry [g*k + j] for data shard j
+ *     of group g, any byte alignment.  An entry is read only for a data shard the call rebuilds (a
+ *     lost data shard of a recoverable group); every other entry is ignored.  An entry of 0 means
+ *     "not wanted": that row is not stored, the group's other rows are, and the status stays 0.
+ *     At any other entry the call writes exactly L_g bytes: nothing before the address and nothing
+ *     at or past address + L_g.  L_g == 0 writes nothing and dereferences nothing.  Unrecoverable
+ *     groups write nothing.
+ *   - d_status (nullable): one byte per group, every one written when given: 0 = rebuilt or nothing
+ *     lost, 1 = unrecoverable.
+ *   - d_masks_out (nullable): FEC_WIDE_MASK_WORDS u64 per group, group g's words at
+ *     d_masks_out[4g .. 4g + 3], the erasure mask derived from the addresses: shard s is bit s & 63
+ *     of word s >> 6, and every bit at and above k + r is zero.
+ *   - A destination range must not overlap any shard the call reads, in any group, nor another
+ *     destination range.
+ *   - Asynchronous on `stream` (NULL = the context's own), drained by fec_encoder_free; no host
+ *     synchronise and no readback.  The recovery records are always built on the device per call,
+ *     in the caller stream's workspace (record offsets, the masks when d_masks_out is NULL, L_g when
+ *     there is a length table and d_symbol_len_out is NULL, and at most 64 MiB of records at a time;
+ *     larger calls are walked in chunks), whatever fec_decode_plan_mode says.  No per-context state
+ *     beyond the shape's parity matrix on the device, which the wide calls keep too.
+ * Refusals launch nothing and write nothing (fec_hip_last_error names the case): FEC_ERR_NULL for a
+ * NULL context, address table or destination table, the message naming the argument;
+ * FEC_ERR_RANGE, with the texts of the wide calls, for k = 0, r = 0, k + r > 256, min(k, r) > 32,
+ * packet_size < 16, num_groups == 0 or >= 2^32. */
+int fec_recover_scatter_wide_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
+                                    const uint32_t* d_shard_lens, const uint64_t* d_dest_addrs,
+                                    uint64_t num_groups, uint32_t k, uint32_t r, uint32_t packet_size,
+                                    uint8_t* d_status, uint64_t* d_masks_out, uint32_t* d_symbol_len_out,
+                                    void* stream);
 
 /* ---- scatter encode: parity rows written to a table of destinations ----
  * The gather encodes above write every parity row into a library-shaped buffer as a full P-byte

@@ -661,6 +661,40 @@ struct WideLaunch {
   PlanLaunch plan;           // arena, stride = wide_slot_stride, per_chunk, the r x k matrix
 };
 
+// ---- the wide address-table recover (fec_recover_scatter_wide_rs_dev; fec_wide_table.hip) ----
+// The scatter recover's tables (TableRecoverLaunch) for a wide shape: k + r entries per group of
+// addresses (0 = lost) and, nullable, lengths; k destinations per group.  The masks are derived
+// from the addresses, four words per group, and the record builder reads them, so they always have
+// a place: the caller's d_masks_out or the workspace.
+struct WideTableLaunch {
+  const uint64_t* addrs;     // groups * (k + r) absolute device addresses, 0 = lost
+  const uint32_t* lens;      // nullable (NULL = every present shard has P): groups * (k + r)
+  const uint64_t* dests;     // groups * k absolute device addresses, 0 = not wanted
+  uint64_t groups;
+  uint32_t k, r, P;
+  uint8_t* status;           // nullable
+  uint64_t* masks;           // written: four words per group, the caller's or the workspace's
+  uint32_t* symlen;          // written when set: the caller's, else the workspace's when there is a
+                             // length table (the kernel reads it), else nullptr
+  uint32_t* rec_off;         // workspace, one u32 per group
+  PlanLaunch plan;           // arena, stride = wide_slot_stride, per_chunk, the r x k matrix
+};
+// The policy bits of recover_scatter_wide: the table recovers' runtime-k form.
+constexpr int kWideTablePol = kGatherPol | kNoCoefBranch;
+// The workspace of a wide table call, byte offsets from its start, each region aligned as
+// plan_workspace aligns its own: G record offsets; G masks of 32 B when the caller gives no
+// d_masks_out; G symbol lengths when there is a length table and the caller asks for none; the
+// arena (wide_arena), 256-B aligned.  A region not needed is empty.
+inline PlanWorkspace wide_table_workspace(uint64_t G, bool masks_needed, bool symlen_needed, const PlanArena& a) {
+  PlanWorkspace w{};
+  w.rec_off = 0;
+  w.masks = (G * sizeof(uint32_t) + 7u) & ~uint64_t{7};
+  w.symlen = w.masks + (masks_needed ? G * 4u * sizeof(uint64_t) : 0);
+  w.arena = (w.symlen + (symlen_needed ? G * sizeof(uint32_t) : 0) + 255u) & ~uint64_t{255};
+  w.bytes = w.arena + a.bytes;
+  return w;
+}
+
 // The passes of a runtime-k encode: at most kEncodePassRows parity rows per launch, pass p the rows
 // [p * 8, min(r, p * 8 + 8)), the first pass owning the XOR row.  The rule of encode_v16<0, R> (the
 // route the fixed-length gather encode takes for every shape but k=10 r=1) and of the table

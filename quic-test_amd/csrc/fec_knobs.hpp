@@ -118,6 +118,14 @@ enum class WideLaunchForm : int64_t {
   kDecodeWide = 29,        // first_item / items: groups of the call; k = 0, r = 8; pol; aux: first row of the pass
 };
 
+// The kernels of the wide address-table recover (fec_wide_table.hip), numbered on in a list of
+// their own; named by quicfec.WIDE_TABLE_LAUNCH_FORMS.  Its record builds are kBuildRecordsWide's.
+enum class WideTableLaunchForm : int64_t {
+  kClassifyTableWide = 30,   // first_item / items: the launch's first group and its groups
+  kRecoverScatterWide = 31,  // first_item / items: groups of the call; k = 0, r = 8; first: 1 with a
+                             // length table (VAR), 0 without; pol; aux: first row of the pass
+};
+
 // One launch: 16 words, -1 where a field does not apply to the form.
 struct LaunchRecord {
   int64_t form;          // LaunchForm

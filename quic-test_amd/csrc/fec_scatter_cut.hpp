@@ -1,5 +1,5 @@
-// fec_scatter_cut.hpp — which bytes a lane stores in the scatter recover (fec_recover_scatter_rs_dev,
-// fec_scatter.hip): a rebuilt packet goes to a destination of the caller's, exactly L bytes of it
+// fec_scatter_cut.hpp — which bytes a lane stores in the scatter recovers (fec_recover_scatter_rs_dev,
+// fec_scatter.hip; fec_recover_scatter_wide_rs_dev, fec_wide_table.hip): a rebuilt packet goes to a destination of the caller's, exactly L bytes of it
 // (L = the group's symbol length, wave-uniform), at any byte alignment.
 //
 // scatter_walk is the walk of one wave (64 lanes) over [0, L) instead of [0, P): the rebuilt bytes

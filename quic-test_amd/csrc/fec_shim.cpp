@@ -1701,16 +1701,8 @@ QFEC_EXPORT int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_da
 // ---- wide calls: k + r <= 256, four mask words per group (fec_wide.hip) ----
 namespace {
 
-// What both wide calls do after their own NULL checks.  Refused before any lock or device call:
-// whatever fec_forms.hpp wide_served refuses.  Then, under the context's lock and on its device:
-// the shape's parity matrix on the device (one copy per (k, r), uploaded at the shape's first
-// call), the stream -- a caller's stream counts for fec_encoder_free's drain as in every _dev call,
-// and so does the workspace -- and the caller stream's workspace: G record offsets, then the record
-// arena (wide_workspace).  The records are always built on the device; fec_decode_plan_mode is not
-// consulted.
-int wide_call(const char* what, FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
-              const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P, uint8_t* d_out, bool slots,
-              uint8_t* d_status, void* stream) {
+// What wide_served refuses, with the text every wide call reports; FEC_OK when served.
+int wide_refused(const char* what, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
   switch (qfec::wide_served(G, k, r, P)) {
     case qfec::WideRefusal::kServed:
       break;
@@ -1730,8 +1722,12 @@ int wide_call(const char* what, FECEncoderCtx* ctx, const uint8_t* d_data, const
       set_error("%s: %llu groups exceed 32-bit group indices", what, static_cast<unsigned long long>(G));
       return FEC_ERR_RANGE;
   }
-  CtxBound bound(ctx, what);
-  if (bound.rc != FEC_OK) return bound.rc;
+  return FEC_OK;
+}
+
+// The shape's r x k parity matrix on the context's device (ctx->wide_matrices: one copy per (k, r),
+// uploaded at the shape's first wide call).  The context's lock is held.
+int wide_matrix(const char* what, FECEncoderCtx* ctx, uint32_t k, uint32_t r, const uint8_t** out) {
   auto& matrix = ctx->wide_matrices[std::make_pair(k, r)];
   if (!matrix) {
     std::vector<uint8_t> M;
@@ -1745,6 +1741,27 @@ int wide_call(const char* what, FECEncoderCtx* ctx, const uint8_t* d_data, const
     QFEC_HIP(hipMemcpy(buf->ptr, M.data(), M.size(), hipMemcpyHostToDevice));
     matrix = std::move(buf);
   }
+  *out = matrix->as<uint8_t>();
+  return FEC_OK;
+}
+
+// What both wide calls do after their own NULL checks.  Refused before any lock or device call:
+// whatever fec_forms.hpp wide_served refuses.  Then, under the context's lock and on its device:
+// the shape's parity matrix on the device (one copy per (k, r), uploaded at the shape's first
+// call), the stream -- a caller's stream counts for fec_encoder_free's drain as in every _dev call,
+// and so does the workspace -- and the caller stream's workspace: G record offsets, then the record
+// arena (wide_workspace).  The records are always built on the device; fec_decode_plan_mode is not
+// consulted.
+int wide_call(const char* what, FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
+              const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P, uint8_t* d_out, bool slots,
+              uint8_t* d_status, void* stream) {
+  int rc = wide_refused(what, G, k, r, P);
+  if (rc != FEC_OK) return rc;
+  CtxBound bound(ctx, what);
+  if (bound.rc != FEC_OK) return bound.rc;
+  const uint8_t* matrix = nullptr;
+  rc = wide_matrix(what, ctx, k, r, &matrix);
+  if (rc != FEC_OK) return rc;
   const hipStream_t s = pick_stream(ctx, stream);
   const qfec::PlanArena arena = qfec::wide_arena(k, r, G, qfec::plan_arena_budget());
   const qfec::PlanWorkspace w = qfec::wide_workspace(G, arena);
@@ -1763,7 +1780,7 @@ int wide_call(const char* what, FECEncoderCtx* ctx, const uint8_t* d_data, const
   a.plan.arena = static_cast<uint8_t*>(ws) + w.arena;
   a.plan.stride = arena.stride;
   a.plan.per_chunk = arena.per_chunk;
-  a.plan.matrix = matrix->as<uint8_t>();
+  a.plan.matrix = matrix;
   QFEC_HIP(qfec::launch_decode_wide(a, s));
   return FEC_OK;
 }
@@ -1792,6 +1809,57 @@ QFEC_EXPORT int fec_recover_wide_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_dat
       return FEC_ERR_NULL;
     }
     return wide_call("fec_recover_wide_rs_dev", ctx, d_data, d_parity, d_masks, G, k, r, P, d_rebuilt, true, d_status, stream);
+  });
+}
+
+// ---- the wide recover from an address table into a table of destinations (fec_wide_table.hip) ----
+// fec_recover_scatter_rs_dev for a wide shape: refused as the wide calls refuse, before any lock or
+// device call; then the matrix, the stream and the caller stream's workspace (wide_table_workspace:
+// record offsets, the masks when the caller gives no d_masks_out, the symbol lengths when there is a
+// length table and the caller asks for none, the record arena).  Records on the device always.
+QFEC_EXPORT int fec_recover_scatter_wide_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs,
+                                                const uint32_t* d_shard_lens, const uint64_t* d_dest_addrs, uint64_t G,
+                                                uint32_t k, uint32_t r, uint32_t P, uint8_t* d_status,
+                                                uint64_t* d_masks_out, uint32_t* d_symbol_len_out, void* stream) {
+  return api_call(ctx, [&]() -> int {
+    const char* what = "fec_recover_scatter_wide_rs_dev";
+    if (!ctx || !d_shard_addrs || !d_dest_addrs) {
+      set_error("%s: %s is NULL", what, !ctx             ? "the context"
+                                        : !d_shard_addrs ? "d_shard_addrs"
+                                                         : "d_dest_addrs (the destination table)");
+      return FEC_ERR_NULL;
+    }
+    int rc = wide_refused(what, G, k, r, P);
+    if (rc != FEC_OK) return rc;
+    CtxBound bound(ctx, what);
+    if (bound.rc != FEC_OK) return bound.rc;
+    const uint8_t* matrix = nullptr;
+    rc = wide_matrix(what, ctx, k, r, &matrix);
+    if (rc != FEC_OK) return rc;
+    const hipStream_t s = pick_stream(ctx, stream);
+    const bool own_masks = d_masks_out == nullptr;
+    const bool own_symlen = d_shard_lens != nullptr && d_symbol_len_out == nullptr;
+    const qfec::PlanArena arena = qfec::wide_arena(k, r, G, qfec::plan_arena_budget());
+    const qfec::PlanWorkspace w = qfec::wide_table_workspace(G, own_masks, own_symlen, arena);
+    void* ws = nullptr;
+    QFEC_HIP(stream_workspace(ctx, s, w.bytes, &ws));
+    uint8_t* base = static_cast<uint8_t*>(ws);
+    qfec::WideTableLaunch a{};
+    a.addrs = d_shard_addrs;
+    a.lens = d_shard_lens;
+    a.dests = d_dest_addrs;
+    a.groups = G;
+    a.k = k, a.r = r, a.P = P;
+    a.status = d_status;
+    a.masks = own_masks ? reinterpret_cast<uint64_t*>(base + w.masks) : d_masks_out;
+    a.symlen = own_symlen ? reinterpret_cast<uint32_t*>(base + w.symlen) : d_symbol_len_out;
+    a.rec_off = reinterpret_cast<uint32_t*>(base + w.rec_off);
+    a.plan.arena = base + w.arena;
+    a.plan.stride = arena.stride;
+    a.plan.per_chunk = arena.per_chunk;
+    a.plan.matrix = matrix;
+    QFEC_HIP(qfec::launch_recover_scatter_wide(a, s));
+    return FEC_OK;
   });
 }
 

@@ -35,6 +35,7 @@
 #include "fec_launch.hpp"
 #include "fec_mask_wide.hpp"
 #include "fec_plan_build_wide.hpp"
+#include "fec_wide_head.hpp"  // WideHead, the record's header as decode_wide reads it
 
 namespace qfec {
 namespace {
@@ -108,15 +109,6 @@ __global__ __launch_bounds__(256) void build_records_wide(const uint64_t* __rest
     if (!ok && status) status[g] = 1;
   }
 }
-
-// The wide record's header as decode_wide reads it (fec_plan_build_wide.hpp).
-struct WideHead {
-  const uint32_t* rw;
-  __device__ uint32_t e() const { return rw[kWideCountAt / 4u] & 0xFFu; }
-  __device__ bool xor_only() const { return ((rw[kWideXorAt / 4u] >> 8) & 0xFFu) != 0; }
-  __device__ const Tab* tabs() const { return reinterpret_cast<const Tab*>(reinterpret_cast<const uint8_t*>(rw) + kWideHeaderBytes); }
-};
-static_assert(kWideCountAt % 4u == 0 && kWideXorAt == kWideCountAt + 1u, "e and the flag are bytes 0 and 1 of one word");
 
 // decode_piece's SRC: the base of survivor s from the header's id.
 struct WideBases {
@@ -209,6 +201,20 @@ hipError_t run_decode_wide(const WideLaunch& a, uint64_t c0, uint64_t cn, hipStr
 }
 
 }  // namespace
+
+// build_records_wide for another unit's call (fec_wide_table.hip): run_build_records_wide on the
+// fields it reads.
+hipError_t launch_build_records_wide(const PlanLaunch& p, const uint64_t* masks, uint32_t* rec_off, uint8_t* status,
+                                     uint64_t first_group, uint64_t groups, uint32_t k, uint32_t r, hipStream_t s) {
+  if (masks == nullptr || rec_off == nullptr || p.arena == nullptr || p.matrix == nullptr || groups > p.per_chunk ||
+      p.stride != wide_slot_stride(k, r))
+    return hipErrorInvalidValue;
+  WideLaunch a{};
+  a.masks = masks, a.rec_off = rec_off, a.status = status;
+  a.k = k, a.r = r;
+  a.plan = p;
+  return run_build_records_wide(a, first_group, groups, s);
+}
 
 hipError_t launch_decode_wide(const WideLaunch& a, hipStream_t s) {
   // a slot holds the shape's largest record and a chunk has at most per_chunk groups (for_plan_chunks):

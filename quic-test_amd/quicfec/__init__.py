@@ -62,7 +62,7 @@ HIP_SYMBOLS = (
     "fec_recover_gather_rs_dev", "fec_encode_gather_rs_dev",
     "fec_recover_gather_var_rs_dev", "fec_encode_gather_var_rs_dev",
     "fec_recover_scatter_rs_dev", "fec_encode_scatter_rs_dev", "fec_decode_plan_mode",
-    "fec_decode_wide_rs_dev", "fec_recover_wide_rs_dev",
+    "fec_decode_wide_rs_dev", "fec_recover_wide_rs_dev", "fec_recover_scatter_wide_rs_dev",
 )
 
 
@@ -164,6 +164,7 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
         "fec_encode_scatter_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
         "fec_decode_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
         "fec_recover_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
+        "fec_recover_scatter_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -400,6 +401,17 @@ class Context:
         rc = self.lib.fec_recover_wide_rs_dev(self.handle, _opt(d_data), _opt(d_parity), _opt(d_masks), num_groups, k, r,
                                               packet_size, _opt(d_rebuilt), _opt(d_status), stream)
         _check(rc, "fec_recover_wide_rs_dev", self.lib)
+
+    def recover_scatter_wide_dev(self, d_shard_addrs, d_shard_lens, d_dest_addrs, num_groups: int, k: int, r: int,
+                                 packet_size: int, d_status=None, d_masks_out=None, d_symbol_len_out=None,
+                                 stream: Optional[int] = None) -> None:
+        """recover_scatter_dev for k + r <= 256, min(k, r) <= 32: the tables have k + r (addresses,
+        lengths) and k (destinations) entries per group; d_masks_out (nullable) takes WIDE_MASK_WORDS
+        u64 per group, shard s at bit s & 63 of word s >> 6."""
+        rc = self.lib.fec_recover_scatter_wide_rs_dev(self.handle, _opt(d_shard_addrs), _opt(d_shard_lens),
+                                                      _opt(d_dest_addrs), num_groups, k, r, packet_size, _opt(d_status),
+                                                      _opt(d_masks_out), _opt(d_symbol_len_out), stream)
+        _check(rc, "fec_recover_scatter_wide_rs_dev", self.lib)
 
     def decode_prepare(self, k: int, r: int) -> int:
         n = ctypes.c_uint64(0)
@@ -660,6 +672,10 @@ PLAN_LAUNCH_FORMS = {26: "build_records"}
 # the launch's first group in the call and its groups; build_records_wide's aux = its first arena slot,
 # decode_wide's = the first row of the pass
 WIDE_LAUNCH_FORMS = {27: "classify_wide", 28: "build_records_wide", 29: "decode_wide"}
+# the kernels of the wide address-table recover (csrc/fec_wide_table.hip; WideTableLaunchForm), again
+# their own; its record builds are build_records_wide's (28).  recover_scatter_wide: first = 1 with a
+# length table, aux = the first row of the pass
+WIDE_TABLE_LAUNCH_FORMS = {30: "classify_table_wide", 31: "recover_scatter_wide"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -688,7 +704,7 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
         rec = dict(zip(LAUNCH_FIELDS, (int(x) for x in row)))
         form = rec["form"]
         for names in (LAUNCH_FORMS, GATHER_LAUNCH_FORMS, GATHER_VAR_LAUNCH_FORMS, SCATTER_LAUNCH_FORMS,
-                      SCATTER_ENCODE_LAUNCH_FORMS, PLAN_LAUNCH_FORMS, WIDE_LAUNCH_FORMS):
+                      SCATTER_ENCODE_LAUNCH_FORMS, PLAN_LAUNCH_FORMS, WIDE_LAUNCH_FORMS, WIDE_TABLE_LAUNCH_FORMS):
             if form in names:
                 rec["form"] = names[form]
         out.append(rec)
