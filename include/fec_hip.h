@@ -150,8 +150,8 @@ int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const ui
  * Refusals launch nothing and write nothing (fec_hip_last_error names the case): FEC_ERR_NULL for a
  * NULL context or required pointer; FEC_ERR_RANGE for k = 0, r = 0, k + r > 256, min(k, r) > 32,
  * packet_size < 16, num_groups == 0 or >= 2^32.  There are no host-pointer, batcher or packed forms
- * of the wide calls, and no wide address-table encode; the wide address-table recover is
- * fec_recover_scatter_wide_rs_dev, below. */
+ * of the wide calls; the wide address-table calls are fec_recover_scatter_wide_rs_dev and
+ * fec_encode_scatter_wide_rs_dev, below. */
 #define FEC_WIDE_MASK_WORDS 4
 int fec_decode_wide_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
                            const uint64_t* d_erasure_masks, uint64_t num_groups, uint32_t k, uint32_t r,
@@ -299,7 +299,9 @@ int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs
  * zero-padded copy of every shard and without a mask built by the caller.
  *   - Served: k >= 1, r >= 1, k + r <= 256, min(k, r) <= 32 (why: see the wide calls above),
  *     packet_size >= 16, 0 < num_groups < 2^32.  Shapes with k + r <= 64 are served too and give
- *     byte for byte what fec_recover_scatter_rs_dev gives for the same tables.
+ *     byte for byte what fec_recover_scatter_rs_dev gives for the same tables.  The cap on
+ *     min(k, r) is this side's alone: fec_encode_scatter_wide_rs_dev, below, builds no record and
+ *     has none, so it produces parity for shapes (33 + 33, 128 + 128) that no wide call recovers.
  *   - d_shard_addrs: num_groups*(k+r) absolute device addresses (u64), entry [g*(k+r) + s] for shard
  *     s of group g (s < k: data shard s; else parity row s - k), any byte alignment.  Address 0 is
  *     the only loss marker.  The table is only read.
@@ -382,6 +384,49 @@ int fec_encode_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs
                               const uint32_t* d_packet_lens, const uint64_t* d_dest_addrs,
                               uint64_t num_groups, uint32_t k, uint32_t r, uint32_t packet_size,
                               uint32_t* d_symbol_len_out, void* stream);
+
+/* ---- wide scatter encode: k + r <= 256 from scattered packets ----
+ * fec_encode_scatter_rs_dev for groups of up to 256 shards: packets taken where they lie in device
+ * memory through a table of addresses, each parity row written where a table of destinations says,
+ * cut at the group's symbol length.  One call: a NULL length table gives the fixed-length form,
+ * destinations at d_parity + (g*r + i)*P give the contiguous rows of fec_encode_batch_rs_dev
+ * without its contiguous, zero-padded copy of every packet, destinations back to back give packed
+ * repair payloads.
+ *   - Served: k >= 1, r >= 1, k + r <= 256, packet_size >= 16, 0 < num_groups < 2^32.  There is no
+ *     min(k, r) cap: the cap min(k, r) <= 32 of the wide decode, the wide recover and
+ *     fec_recover_scatter_wide_rs_dev is the record builder's (the inverse of an e x e matrix in
+ *     local memory), and an encode builds no record.  33 + 33, 128 + 128 and 1 + 255 are served
+ *     here and refused there.  Shapes with k + r <= 64 are served too and give byte for byte what
+ *     fec_encode_scatter_rs_dev gives for the same tables.
+ *   - d_packet_addrs: num_groups*k absolute device addresses (u64), entry [g*k + j] for packet j of
+ *     group g, any byte alignment.  Address 0 means absent (the flush of a partial group): the
+ *     packet counts as all zero and is never dereferenced.  The table is only read.
+ *   - d_packet_lens (nullable): num_groups*k u32, indexed alike: the readable bytes of each present
+ *     packet.  A length above P is clamped to P.  A packet is its bytes [0, min(len, P)) followed
+ *     by zeros up to P.  No byte at or past address + len is read.  A present packet of length 0 is
+ *     never dereferenced.  An absent packet's length entry is ignored.  NULL: every present packet
+ *     has P bytes; address 0 is still "absent".
+ *   - d_symbol_len_out (nullable, u32 per group), written for every group when given: L_g, the
+ *     largest min(len, P) over the group's present packets; without a length table P when any
+ *     packet is present; 0 when none is present -- the length of the group's repair payloads.
+ *   - d_dest_addrs: num_groups*r absolute device addresses (u64), entry [g*r + i] for parity row i
+ *     of group g, any byte alignment.  An entry of 0 means "not wanted": that row is not stored,
+ *     the group's other rows are.  At any other entry the call writes exactly L_g bytes of the row
+ *     (the row's bytes past L_g are zero by construction): nothing before the address and nothing
+ *     at or past address + L_g.  L_g == 0 writes nothing and dereferences nothing.
+ *   - A destination range must not overlap any packet the call reads, in any group, nor another
+ *     destination range.
+ *   - Asynchronous on `stream` (NULL = the context's own), drained by fec_encoder_free.  No host
+ *     synchronise after the shape's first call, no readback and no workspace.  Per-context state:
+ *     only the shape's r x k coefficient table on the device, uploaded at the shape's first call
+ *     (none for r = 1).
+ * Refusals launch nothing and write nothing (fec_hip_last_error names the case): FEC_ERR_NULL for a
+ * NULL context, address table or destination table, the message naming the argument;
+ * FEC_ERR_RANGE for k = 0, r = 0, k + r > 256, packet_size < 16, num_groups == 0 or >= 2^32. */
+int fec_encode_scatter_wide_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
+                                   const uint32_t* d_packet_lens, const uint64_t* d_dest_addrs,
+                                   uint64_t num_groups, uint32_t k, uint32_t r, uint32_t packet_size,
+                                   uint32_t* d_symbol_len_out, void* stream);
 
 /* Expected share (0..1) of groups that lost data shards in this context's device-resident
  * decode calls, e.g. 1 - (1 - p)^k for iid loss p (the receiver knows its network profile;

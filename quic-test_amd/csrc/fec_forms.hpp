@@ -695,6 +695,55 @@ inline PlanWorkspace wide_table_workspace(uint64_t G, bool masks_needed, bool sy
   return w;
 }
 
+// ---- the wide scatter encode (fec_encode_scatter_wide_rs_dev; fec_wide_encode.hip) ----
+// The scatter encode's tables (TableEncodeLaunch) for groups of up to 256 shards: k entries per
+// group of addresses (0 = absent) and, nullable, lengths; r destinations per group.  An encode
+// builds no record, so the rows cap of wide_served (min(k, r) <= kWideMaxRows, the record
+// builder's) is not its rule: 33 + 33, 128 + 128 and 1 + 255 are served.
+struct WideEncodeLaunch {
+  const uint64_t* addrs;     // groups * k absolute device addresses, 0 = absent (counts as zeros)
+  const uint32_t* lens;      // nullable (NULL = every present packet has P): groups * k
+  const uint64_t* dests;     // groups * r absolute device addresses, 0 = not wanted
+  uint64_t groups;
+  uint32_t k, r, P;
+  uint32_t* symlen_out;      // nullable
+  const void* tables;        // r x k CoefEntry, row 0 (all ones) included; not read when r == 1
+};
+// Whether the wide scatter encode serves (k, r, P, G), and if not, why: the one statement of that
+// rule.
+enum class WideEncodeRefusal : int { kServed = 0, kShape, kPacket, kNoGroups, kGroups };
+constexpr WideEncodeRefusal wide_encode_served(uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  if (k == 0 || r == 0 || uint64_t{k} + r > kWideMaxShards) return WideEncodeRefusal::kShape;
+  if (P < kVecMinP) return WideEncodeRefusal::kPacket;
+  if (G == 0) return WideEncodeRefusal::kNoGroups;
+  if (G >= (1ull << 32)) return WideEncodeRefusal::kGroups;
+  return WideEncodeRefusal::kServed;
+}
+// The policy bits of encode_scatter_wide: recover_scatter_wide's (its rebuild is the same
+// decode_piece<0, 8>, multiplying by every coefficient, row 0's ones included).
+constexpr int kWideEncodePol = kWideTablePol;
+struct WideEncodeForm {
+  bool supported = false;  // false: the call is refused (wide_encode_served)
+  uint32_t passes = 0;     // pass p: rows [p * pass_rows, min(r, (p + 1) * pass_rows))
+  uint32_t pass_rows = 0;
+  bool VAR = false;        // with a length table: loads masked by it
+  bool xor_only = false;   // r == 1: the XOR of the packets, no coefficient table
+  int POL = 0;
+};
+// The form the wide scatter encode runs for (k, r, P) with (var) or without a length table:
+// ceil(r / 8) passes of encode_scatter_wide<POL, VAR>, every shape at runtime k.
+inline WideEncodeForm wide_encode_form(uint32_t k, uint32_t r, uint32_t P, bool var) {
+  WideEncodeForm f;
+  if (wide_encode_served(1, k, r, P) != WideEncodeRefusal::kServed) return f;
+  f.supported = true;
+  f.pass_rows = kWidePassRows;
+  f.passes = (r + kWidePassRows - 1) / kWidePassRows;
+  f.VAR = var;
+  f.xor_only = r == 1;
+  f.POL = kWideEncodePol;
+  return f;
+}
+
 // The passes of a runtime-k encode: at most kEncodePassRows parity rows per launch, pass p the rows
 // [p * 8, min(r, p * 8 + 8)), the first pass owning the XOR row.  The rule of encode_v16<0, R> (the
 // route the fixed-length gather encode takes for every shape but k=10 r=1) and of the table

@@ -2,7 +2,8 @@
 // gfx950 kernels, one translation unit per kernel family: fec_encode.hip, fec_decode.hip,
 // fec_decode_fused.hip, fec_runs.hip, fec_server.hip, fec_util.hip; the address-table units
 // fec_gather.hip, fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip with their shared
-// fec_table.hpp; fec_plan.hip; fec_wide.hip; fec_wide_table.hip.  Internal to libfec_hip.so.
+// fec_table.hpp; fec_plan.hip; fec_wide.hip; fec_wide_table.hip; fec_wide_encode.hip.  Internal to
+// libfec_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -82,6 +83,9 @@ hipError_t launch_build_records_wide(const PlanLaunch& p, const uint64_t* masks,
 // classify_table_wide over every group, then per chunk of a.plan's arena build_records_wide and
 // wide_passes(k, r) launches of recover_scatter_wide, in stream order.
 hipError_t launch_recover_scatter_wide(const WideTableLaunch& a, hipStream_t s);
+// The wide encode from an address table into a table of destinations (fec_wide_encode.hip):
+// wide_encode_form's passes of encode_scatter_wide; no classify, no record, no workspace.
+hipError_t launch_encode_scatter_wide(const WideEncodeLaunch& a, hipStream_t s);
 // Packed recover rows (fec_runs.hip): row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.

@@ -126,6 +126,13 @@ enum class WideTableLaunchForm : int64_t {
                              // length table (VAR), 0 without; pol; aux: first row of the pass
 };
 
+// The kernel of the wide scatter encode (fec_wide_encode.hip), numbered on in a list of its own;
+// named by quicfec.WIDE_ENCODE_LAUNCH_FORMS.
+enum class WideEncodeLaunchForm : int64_t {
+  kEncodeScatterWide = 32,  // first_item / items: groups of the call; k = 0, r = 8; first: 1 with a
+                            // length table (VAR), 0 without; pol; aux: first parity row of the pass
+};
+
 // One launch: 16 words, -1 where a field does not apply to the form.
 struct LaunchRecord {
   int64_t form;          // LaunchForm

@@ -10,7 +10,8 @@
 //   L = 1..3 one pass: every lane rebuilds the 4-B piece at offset 0 and lane i < L stores byte i;
 //   L = 0    nothing.
 // Every piece lies inside [0, L), so scatter_store / scatter_store_byte never touch a byte before
-// the destination or at or past destination + L; a destination of NULL ("not wanted") is never
+// the destination or at or past destination + L (the wide scatter encode, fec_wide_encode.hip, stores
+// its parity rows through them too); a destination of NULL ("not wanted") is never
 // dereferenced.  The kernels call these and nothing else decides where a lane stores.  Plain C++
 // with no HIP dependency: a host program runs every (L, lane) into a heap block of exactly L bytes
 // under AddressSanitizer (tests/csrc/scatter_cut_test.cpp).

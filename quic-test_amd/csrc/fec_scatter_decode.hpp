@@ -1,5 +1,6 @@
 // fec_scatter_decode.hpp — what the scatter recovers (recover_scatter, fec_scatter.hip;
-// recover_scatter_wide, fec_wide_table.hip) share past fec_table.hpp: decode_piece's destination
+// recover_scatter_wide, fec_wide_table.hip) and the wide scatter encode (encode_scatter_wide,
+// fec_wide_encode.hip: its rows are the parity rows) share past fec_table.hpp: decode_piece's destination
 // functor over a table of destinations and the walk of a wave over [0, L) with its choice of loads.
 // Which bytes a lane stores stays fec_scatter_cut.hpp's.  Internal to its translation unit (unnamed
 // namespace), as fec_table.hpp's.

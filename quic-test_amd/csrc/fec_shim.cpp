@@ -314,6 +314,9 @@ struct FECEncoderCtx {
   std::map<std::pair<uint32_t, uint32_t>, std::unique_ptr<DecodePlan>> dec_plans;
   // the r x k parity matrix on the device, one per shape the wide calls met (wide_call)
   std::map<std::pair<uint32_t, uint32_t>, std::unique_ptr<DevBuf>> wide_matrices;
+  // the r x k coefficient table, row 0 included, one per shape the wide scatter encode met
+  // (wide_encode_tables), beside enc_plans' (r - 1) x k tables
+  std::map<std::pair<uint32_t, uint32_t>, std::unique_ptr<DevBuf>> wide_enc_tables;
   // Message of the last failing call on this context (fec_ctx_last_error): callers whose
   // threads migrate between the failing call and the read (Go goroutines) cannot rely on the
   // thread-local fec_hip_last_error.  Own lock: readable while a call holds `mu`.
@@ -365,6 +368,7 @@ struct FECEncoderCtx {
     enc_plans.clear();
     dec_plans.clear();
     wide_matrices.clear();
+    wide_enc_tables.clear();
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -1859,6 +1863,89 @@ QFEC_EXPORT int fec_recover_scatter_wide_rs_dev(FECEncoderCtx* ctx, const uint64
     a.plan.per_chunk = arena.per_chunk;
     a.plan.matrix = matrix;
     QFEC_HIP(qfec::launch_recover_scatter_wide(a, s));
+    return FEC_OK;
+  });
+}
+
+// ---- the wide encode from an address table into a table of destinations (fec_wide_encode.hip) ----
+namespace {
+
+// What wide_encode_served refuses, with the text the call reports; FEC_OK when served.  No rows
+// cap: an encode builds no record.
+int wide_encode_refused(const char* what, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  switch (qfec::wide_encode_served(G, k, r, P)) {
+    case qfec::WideEncodeRefusal::kServed:
+      break;
+    case qfec::WideEncodeRefusal::kShape:
+      set_error("%s: unsupported k=%u r=%u (need k>0, r>0, k+r<=%u)", what, k, r, qfec::kWideMaxShards);
+      return FEC_ERR_RANGE;
+    case qfec::WideEncodeRefusal::kPacket:
+      set_error("%s: packet_size %u is below %u bytes", what, P, qfec::kVecMinP);
+      return FEC_ERR_RANGE;
+    case qfec::WideEncodeRefusal::kNoGroups:
+      set_error("%s: num_groups is 0", what);
+      return FEC_ERR_RANGE;
+    case qfec::WideEncodeRefusal::kGroups:
+      set_error("%s: %llu groups exceed 32-bit group indices", what, static_cast<unsigned long long>(G));
+      return FEC_ERR_RANGE;
+  }
+  return FEC_OK;
+}
+
+// The shape's r x k coefficient table on the context's device, row 0 (the ones) as entries like
+// any other row: encode_scatter_wide reads row m0 + m at tabs[(m0 + m) * k + j], so get_encode_plan's
+// (r - 1) x k table, which leaves the XOR row out, does not serve it.  One copy per (k, r)
+// (ctx->wide_enc_tables), uploaded at the shape's first call; r == 1 needs none (the XOR path).
+// The context's lock is held.
+int wide_encode_tables(const char* what, FECEncoderCtx* ctx, uint32_t k, uint32_t r, const void** out) {
+  *out = nullptr;
+  if (r == 1) return FEC_OK;
+  auto& tables = ctx->wide_enc_tables[std::make_pair(k, r)];
+  if (!tables) {
+    std::vector<uint8_t> M;
+    if (!qfec::parity_matrix(k, r, M)) {
+      ctx->wide_enc_tables.erase(std::make_pair(k, r));
+      set_error("%s: no parity matrix for k=%u r=%u", what, k, r);
+      return FEC_ERR_RANGE;
+    }
+    std::vector<qfec::CoefEntry> tab(size_t(r) * k);
+    for (size_t i = 0; i < tab.size(); ++i) tab[i] = qfec::make_entry(M[i]);
+    auto buf = std::make_unique<DevBuf>();
+    QFEC_HIP(buf->ensure(tab.size() * sizeof(qfec::CoefEntry)));
+    QFEC_HIP(hipMemcpy(buf->ptr, tab.data(), tab.size() * sizeof(qfec::CoefEntry), hipMemcpyHostToDevice));
+    tables = std::move(buf);
+  }
+  *out = tables->ptr;
+  return FEC_OK;
+}
+
+}  // namespace
+
+// fec_encode_scatter_rs_dev for a wide shape: refused before any lock or device call; then the
+// shape's coefficient table and the stream.  No classify, no record, no workspace.
+QFEC_EXPORT int fec_encode_scatter_wide_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_packet_addrs,
+                                               const uint32_t* d_packet_lens, const uint64_t* d_dest_addrs, uint64_t G,
+                                               uint32_t k, uint32_t r, uint32_t P, uint32_t* d_symbol_len_out,
+                                               void* stream) {
+  return api_call(ctx, [&]() -> int {
+    const char* what = "fec_encode_scatter_wide_rs_dev";
+    if (!ctx || !d_packet_addrs || !d_dest_addrs) {
+      set_error("%s: %s is NULL", what, !ctx              ? "the context"
+                                        : !d_packet_addrs ? "d_packet_addrs"
+                                                          : "d_dest_addrs (the destination table)");
+      return FEC_ERR_NULL;
+    }
+    int rc = wide_encode_refused(what, G, k, r, P);
+    if (rc != FEC_OK) return rc;
+    CtxBound bound(ctx, what);
+    if (bound.rc != FEC_OK) return bound.rc;
+    const void* tables = nullptr;
+    rc = wide_encode_tables(what, ctx, k, r, &tables);
+    if (rc != FEC_OK) return rc;
+    const hipStream_t s = pick_stream(ctx, stream);
+    // addrs, lens, dests, groups, k, r, P, symlen_out, tables
+    const qfec::WideEncodeLaunch a{d_packet_addrs, d_packet_lens, d_dest_addrs, G, k, r, P, d_symbol_len_out, tables};
+    QFEC_HIP(qfec::launch_encode_scatter_wide(a, s));
     return FEC_OK;
   });
 }

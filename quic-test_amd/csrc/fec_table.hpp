@@ -1,5 +1,5 @@
 // fec_table.hpp — what the address-table kernel units (fec_gather.hip, fec_gather_var.hip,
-// fec_scatter.hip, fec_scatter_encode.hip, fec_wide_table.hip) share, stated once:
+// fec_scatter.hip, fec_scatter_encode.hip, fec_wide_table.hip, fec_wide_encode.hip) share, stated once:
 //  * shard_ptr / dest_ptr: a table entry as a global-memory pointer; min_u32; load_masked, the
 //    piece load cut at a shard's length; VarSurvivors<K> / VarSurvivorsLds, a group's survivors
 //    with their lengths as decode_piece's loading functor;

@@ -63,6 +63,7 @@ HIP_SYMBOLS = (
     "fec_recover_gather_var_rs_dev", "fec_encode_gather_var_rs_dev",
     "fec_recover_scatter_rs_dev", "fec_encode_scatter_rs_dev", "fec_decode_plan_mode",
     "fec_decode_wide_rs_dev", "fec_recover_wide_rs_dev", "fec_recover_scatter_wide_rs_dev",
+    "fec_encode_scatter_wide_rs_dev",
 )
 
 
@@ -165,6 +166,7 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
         "fec_decode_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
         "fec_recover_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
         "fec_recover_scatter_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+        "fec_encode_scatter_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -412,6 +414,15 @@ class Context:
                                                       _opt(d_dest_addrs), num_groups, k, r, packet_size, _opt(d_status),
                                                       _opt(d_masks_out), _opt(d_symbol_len_out), stream)
         _check(rc, "fec_recover_scatter_wide_rs_dev", self.lib)
+
+    def encode_scatter_wide_dev(self, d_packet_addrs, d_packet_lens, d_dest_addrs, num_groups: int, k: int, r: int,
+                                packet_size: int, d_symbol_len_out=None, stream: Optional[int] = None) -> None:
+        """encode_scatter_dev for k + r <= 256, with no cap on min(k, r): the tables have k (addresses,
+        lengths) and r (destinations) entries per group; address 0 = absent, destination 0 = not wanted."""
+        rc = self.lib.fec_encode_scatter_wide_rs_dev(self.handle, _opt(d_packet_addrs), _opt(d_packet_lens),
+                                                     _opt(d_dest_addrs), num_groups, k, r, packet_size,
+                                                     _opt(d_symbol_len_out), stream)
+        _check(rc, "fec_encode_scatter_wide_rs_dev", self.lib)
 
     def decode_prepare(self, k: int, r: int) -> int:
         n = ctypes.c_uint64(0)
@@ -676,6 +687,9 @@ WIDE_LAUNCH_FORMS = {27: "classify_wide", 28: "build_records_wide", 29: "decode_
 # their own; its record builds are build_records_wide's (28).  recover_scatter_wide: first = 1 with a
 # length table, aux = the first row of the pass
 WIDE_TABLE_LAUNCH_FORMS = {30: "classify_table_wide", 31: "recover_scatter_wide"}
+# the kernel of the wide scatter encode (csrc/fec_wide_encode.hip; WideEncodeLaunchForm), again its own:
+# first = 1 with a length table, aux = the first parity row of the pass
+WIDE_ENCODE_LAUNCH_FORMS = {32: "encode_scatter_wide"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -704,7 +718,8 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
         rec = dict(zip(LAUNCH_FIELDS, (int(x) for x in row)))
         form = rec["form"]
         for names in (LAUNCH_FORMS, GATHER_LAUNCH_FORMS, GATHER_VAR_LAUNCH_FORMS, SCATTER_LAUNCH_FORMS,
-                      SCATTER_ENCODE_LAUNCH_FORMS, PLAN_LAUNCH_FORMS, WIDE_LAUNCH_FORMS, WIDE_TABLE_LAUNCH_FORMS):
+                      SCATTER_ENCODE_LAUNCH_FORMS, PLAN_LAUNCH_FORMS, WIDE_LAUNCH_FORMS, WIDE_TABLE_LAUNCH_FORMS,
+                      WIDE_ENCODE_LAUNCH_FORMS):
             if form in names:
                 rec["form"] = names[form]
         out.append(rec)
