@@ -301,7 +301,8 @@ int fec_recover_scatter_rs_dev(FECEncoderCtx* ctx, const uint64_t* d_shard_addrs
  *     packet_size >= 16, 0 < num_groups < 2^32.  Shapes with k + r <= 64 are served too and give
  *     byte for byte what fec_recover_scatter_rs_dev gives for the same tables.  The cap on
  *     min(k, r) is this side's alone: fec_encode_scatter_wide_rs_dev, below, builds no record and
- *     has none, so it produces parity for shapes (33 + 33, 128 + 128) that no wide call recovers.
+ *     has none, so it produces parity for shapes (33 + 33, 128 + 128) that no wide call recovers
+ *     unless the context is in FEC_WIDE_ROWS_ALL (fec_wide_rows_mode, below).
  *   - d_shard_addrs: num_groups*(k+r) absolute device addresses (u64), entry [g*(k+r) + s] for shard
  *     s of group g (s < k: data shard s; else parity row s - k), any byte alignment.  Address 0 is
  *     the only loss marker.  The table is only read.
@@ -457,6 +458,33 @@ int fec_decode_loss_hint(FECEncoderCtx* ctx, double share);
 #define FEC_PLAN_CODEBOOK 0
 #define FEC_PLAN_DEVICE 1
 int fec_decode_plan_mode(FECEncoderCtx* ctx, int mode);
+
+/* Whether the three wide decoders -- fec_decode_wide_rs_dev, fec_recover_wide_rs_dev and
+ * fec_recover_scatter_wide_rs_dev -- stop at min(k, r) <= 32 or recover every shape the encodes
+ * produce.  Per context, like fec_decode_plan_mode.
+ *   FEC_WIDE_ROWS_CAPPED (default): min(k, r) <= 32, as documented for each call above; 33 + 33,
+ *     100 + 100 and 128 + 128 are refused with FEC_ERR_RANGE, byte for byte as before this mode
+ *     existed.
+ *   FEC_WIDE_ROWS_ALL: every k >= 1, r >= 1, k + r <= 256 with packet_size >= 16 and
+ *     0 < num_groups < 2^32 is served: what fec_encode_batch_rs_dev and
+ *     fec_encode_scatter_wide_rs_dev produce, these calls recover.  Every other contract point is
+ *     the call's own as documented above: the mask rule, which survivors are read, the status
+ *     bytes, the slots or destinations left unwritten, exactly L_g bytes at each destination,
+ *     "not wanted" destinations, asynchronous on `stream` with no host synchronise and no
+ *     readback, drained by fec_encoder_free.  A shape with min(k, r) <= 32 takes exactly the path
+ *     of the capped mode: the same launches, the same bytes.  A shape past the cap takes the deep
+ *     path for every group, whatever the group's own losses: each record is built by a whole
+ *     workgroup (48.5 KiB of local memory, three workgroups per compute unit) instead of a wave.
+ *   What a shape past the cap costs: the record slot is 512 + min(k, r) * k * 32 bytes, which is
+ *     524,800 B at 128 + 128, so 127 groups fit in one 64 MiB plan chunk; each chunk takes one
+ *     record build and ceil(min(k, r) / 8) consumer launches, up to 16, every one of which reads
+ *     the group's survivors again.  DESIGN.md quotes what was measured.
+ * The mode is read under the context's lock when a call starts and applies to the calls made
+ * after this one returns.  FEC_ERR_NULL for a NULL context, FEC_ERR_RANGE for an unknown mode (the
+ * mode is then unchanged). */
+#define FEC_WIDE_ROWS_CAPPED 0
+#define FEC_WIDE_ROWS_ALL 1
+int fec_wide_rows_mode(FECEncoderCtx* ctx, int mode);
 
 /* ---- utilities for benchmarks and tests ---- */
 /* Fill d_dst with the counter-based splitmix64 stream (byte i of the stream at

@@ -695,6 +695,56 @@ inline PlanWorkspace wide_table_workspace(uint64_t G, bool masks_needed, bool sy
   return w;
 }
 
+// ---- the wide calls past the rows cap (fec_wide_rows_mode; fec_wide_deep.hip, fec_plan_build_deep.hpp) ----
+// The cap of wide_served is the wide record builder's, not the code's: M is a scaled Cauchy matrix
+// for every k + r <= 256.  A context in FEC_WIDE_ROWS_ALL serves the shapes past it with a builder
+// that gives a whole workgroup one record (48.5 KiB of LDS, three workgroups per CU) and consumers
+// that read a record whose erased ids lie elsewhere.  A shape wide_served serves takes the wide path
+// in either mode; a shape past the cap takes the deep path for every group, whatever its e.
+constexpr int kWideRowsCapped = 0, kWideRowsAll = 1;  // fec_hip.h FEC_WIDE_ROWS_CAPPED, FEC_WIDE_ROWS_ALL
+constexpr bool wide_rows_mode_known(int mode) { return mode == kWideRowsCapped || mode == kWideRowsAll; }
+constexpr uint32_t kWideDeepMaxRows = 128;  // min(k, r) with k + r <= 256; fec_plan_build_deep.hpp kDeepMaxE
+// What the wide calls serve in FEC_WIDE_ROWS_ALL: wide_served without its rows cap.
+constexpr WideRefusal wide_rows_all_served(uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  if (k == 0 || r == 0 || uint64_t{k} + r > kWideMaxShards) return WideRefusal::kShape;
+  if (P < kVecMinP) return WideRefusal::kPacket;
+  if (G == 0) return WideRefusal::kNoGroups;
+  if (G >= (1ull << 32)) return WideRefusal::kGroups;
+  return WideRefusal::kServed;
+}
+// The path of a wide call on a context in `mode`, decided here and nowhere else.
+enum class WidePath : int { kRefused = 0, kWide, kDeep };
+struct WideRoute {
+  WidePath path;
+  WideRefusal why;   // kServed unless refused
+  uint32_t passes;   // consumer launches per plan chunk: wide_passes(k, r), up to 16 on the deep path
+};
+constexpr WideRoute wide_route(int mode, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  const WideRefusal capped = wide_served(G, k, r, P);
+  if (capped == WideRefusal::kServed) return {WidePath::kWide, capped, wide_passes(k, r)};
+  if (mode != kWideRowsAll) return {WidePath::kRefused, capped, 0};
+  const WideRefusal all = wide_rows_all_served(G, k, r, P);
+  if (all != WideRefusal::kServed) return {WidePath::kRefused, all, 0};
+  return {WidePath::kDeep, all, wide_passes(k, r)};
+}
+// Form bit of the kernels that read a wide record (decode_wide, recover_scatter_wide): the record is
+// a deep one, its erased ids where fec_plan_build_deep.hpp puts them.  Nothing else about the
+// kernels differs, so the deep consumers are two more instantiations of the same templates.
+constexpr int kDeepRecord = 16384;
+constexpr int kWideDeepPolInPlace = kWidePolInPlace | kDeepRecord;
+constexpr int kWideDeepTablePol = kWideTablePol | kDeepRecord;
+// A slot holds the largest deep record of the shape, wide_slot_stride's formula past its cap:
+// 524,800 B at 128 + 128, so kPlanArenaBytes holds 127 groups per chunk there.
+constexpr uint64_t wide_deep_slot_stride(uint32_t k, uint32_t r) { return kWideHeader + uint64_t{k < r ? k : r} * k * 32u; }
+// wide_arena with the deep slot.
+inline PlanArena wide_deep_arena(uint32_t k, uint32_t r, uint64_t G, uint64_t budget) {
+  const uint64_t stride = wide_deep_slot_stride(k, r);
+  uint64_t per = budget / stride;
+  if (per == 0) per = 1;
+  if (per > G) per = G;
+  return {stride, per, per * stride};
+}
+
 // ---- the wide scatter encode (fec_encode_scatter_wide_rs_dev; fec_wide_encode.hip) ----
 // The scatter encode's tables (TableEncodeLaunch) for groups of up to 256 shards: k entries per
 // group of addresses (0 = absent) and, nullable, lengths; r destinations per group.  An encode

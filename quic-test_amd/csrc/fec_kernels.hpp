@@ -2,7 +2,7 @@
 // gfx950 kernels, one translation unit per kernel family: fec_encode.hip, fec_decode.hip,
 // fec_decode_fused.hip, fec_runs.hip, fec_server.hip, fec_util.hip; the address-table units
 // fec_gather.hip, fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip with their shared
-// fec_table.hpp; fec_plan.hip; fec_wide.hip; fec_wide_table.hip; fec_wide_encode.hip.  Internal to
+// fec_table.hpp; fec_plan.hip; fec_wide.hip; fec_wide_table.hip; fec_wide_encode.hip; fec_wide_deep.hip.  Internal to
 // libfec_hip.so.
 #pragma once
 
@@ -86,6 +86,23 @@ hipError_t launch_recover_scatter_wide(const WideTableLaunch& a, hipStream_t s);
 // The wide encode from an address table into a table of destinations (fec_wide_encode.hip):
 // wide_encode_form's passes of encode_scatter_wide; no classify, no record, no workspace.
 hipError_t launch_encode_scatter_wide(const WideEncodeLaunch& a, hipStream_t s);
+// The wide calls for a shape past the wide builder's rows, min(k, r) > 32 (fec_wide_deep.hip; a
+// context in FEC_WIDE_ROWS_ALL, fec_forms.hpp wide_route): the same walk as launch_decode_wide and
+// launch_recover_scatter_wide with a.plan sized by wide_deep_arena -- the unchanged classify, then
+// per chunk build_records_deep (one workgroup per group) and wide_passes(k, r) launches of the
+// consumer: decode_wide over the deep record in place, the wide path's own decode_wide into slots,
+// recover_scatter_wide over the deep record to a table of destinations.
+hipError_t launch_decode_wide_deep(const WideLaunch& a, hipStream_t s);
+hipError_t launch_recover_scatter_wide_deep(const WideTableLaunch& a, hipStream_t s);
+// What fec_wide_deep.hip calls in the units of the kernels it shares: classify_wide over every group
+// of the call and the row passes of decode_wide over groups [first_group, first_group + groups) of a
+// deep call (fec_wide.hip: in place the instantiation over the deep record, into slots the wide
+// path's own); classify_table_wide and the row passes of recover_scatter_wide over the deep record
+// (fec_wide_table.hip).
+hipError_t launch_classify_wide(const WideLaunch& a, hipStream_t s);
+hipError_t launch_decode_wide_deep_rows(const WideLaunch& a, uint64_t first_group, uint64_t groups, hipStream_t s);
+hipError_t launch_classify_table_wide(const WideTableLaunch& a, hipStream_t s);
+hipError_t launch_recover_scatter_wide_deep_rows(const WideTableLaunch& a, uint64_t first_group, uint64_t groups, hipStream_t s);
 // Packed recover rows (fec_runs.hip): row_start[g] = exclusive prefix sum of the rows each group rebuilds
 // (lost data shards when recoverable, else 0); *total (nullable) = all rows.  block_sums:
 // rows_prefix_workspace_bytes(groups) of device workspace.

@@ -160,4 +160,16 @@ constexpr uint64_t kLaunchTraceCapacity = 1u << 16;  // records kept; later laun
 
 void trace_launch(const LaunchRecord& rec);
 
+// The kernels of the wide calls on a context in FEC_WIDE_ROWS_ALL for a shape with min(k, r) > 32,
+// numbered on in a list of their own; named by quicfec.WIDE_DEEP_LAUNCH_FORMS.  The record builder
+// is fec_wide_deep.hip's; the consumers are decode_wide and recover_scatter_wide instantiated over
+// the deep record (fec_forms.hpp kDeepRecord in pol).  The classifies are kClassifyWide's and
+// kClassifyTableWide's, the slots passes kDecodeWide's.
+enum class WideDeepLaunchForm : int64_t {
+  kBuildRecordsDeep = 33,        // first_item / items: the plan chunk's first group and its groups, one launch
+                                 // per chunk, a workgroup per group; aux: 0, the arena slot of the first
+  kDecodeWideDeep = 34,          // as kDecodeWide, in place
+  kRecoverScatterWideDeep = 35,  // as kRecoverScatterWide
+};
+
 }  // namespace qfec

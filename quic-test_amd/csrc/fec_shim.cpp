@@ -328,6 +328,8 @@ struct FECEncoderCtx {
   // fec_decode_plan_mode: where the device-resident calls take the records of a shape without a
   // dense codebook from
   int plan_mode = FEC_PLAN_CODEBOOK;
+  // fec_wide_rows_mode: whether the wide decoders serve the shapes past min(k, r) <= 32
+  int wide_rows_mode = FEC_WIDE_ROWS_CAPPED;
   // per-stream record-offset workspaces of the device-resident decodes (stream_workspace)
   std::vector<std::unique_ptr<StreamWorkspace>> stream_ws;
   uint64_t ws_clock = 0;
@@ -1705,9 +1707,9 @@ QFEC_EXPORT int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_da
 // ---- wide calls: k + r <= 256, four mask words per group (fec_wide.hip) ----
 namespace {
 
-// What wide_served refuses, with the text every wide call reports; FEC_OK when served.
-int wide_refused(const char* what, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
-  switch (qfec::wide_served(G, k, r, P)) {
+// A refusal of the wide calls with the text every one of them reports; FEC_OK when served.
+int wide_refusal(const char* what, qfec::WideRefusal why, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  switch (why) {
     case qfec::WideRefusal::kServed:
       break;
     case qfec::WideRefusal::kShape:
@@ -1727,6 +1729,24 @@ int wide_refused(const char* what, uint64_t G, uint32_t k, uint32_t r, uint32_t 
       return FEC_ERR_RANGE;
   }
   return FEC_OK;
+}
+// What wide_served refuses: the rule of a context in FEC_WIDE_ROWS_CAPPED, the default.
+int wide_refused(const char* what, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  return wide_refusal(what, qfec::wide_served(G, k, r, P), G, k, r, P);
+}
+// A call wide_refused turned away with *rc, its text set: whether the context's rows mode serves it
+// all the same, on the deep path (fec_forms.hpp wide_route; *rc is then FEC_OK).  Still refused,
+// *rc and the text are wide_route's reason: in FEC_WIDE_ROWS_CAPPED the ones wide_refused gave.
+bool wide_deep_admitted(const char* what, FECEncoderCtx* ctx, uint64_t G, uint32_t k, uint32_t r, uint32_t P, int* rc) {
+  int mode;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    mode = ctx->wide_rows_mode;
+  }
+  const qfec::WideRoute route = qfec::wide_route(mode, G, k, r, P);
+  g_last_error.clear();
+  *rc = wide_refusal(what, route.why, G, k, r, P);
+  return route.path == qfec::WidePath::kDeep;
 }
 
 // The shape's r x k parity matrix on the context's device (ctx->wide_matrices: one copy per (k, r),
@@ -1755,11 +1775,14 @@ int wide_matrix(const char* what, FECEncoderCtx* ctx, uint32_t k, uint32_t r, co
 // call), the stream -- a caller's stream counts for fec_encoder_free's drain as in every _dev call,
 // and so does the workspace -- and the caller stream's workspace: G record offsets, then the record
 // arena (wide_workspace).  The records are always built on the device; fec_decode_plan_mode is not
-// consulted.
+// consulted.  A shape wide_served refuses for its rows alone is served on the deep path when the
+// context is in FEC_WIDE_ROWS_ALL (wide_deep_admitted): the same steps with wide_deep_arena's slots
+// and fec_wide_deep.hip's launch.
 int wide_call(const char* what, FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
               const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P, uint8_t* d_out, bool slots,
               uint8_t* d_status, void* stream) {
   int rc = wide_refused(what, G, k, r, P);
+  const bool deep = rc != FEC_OK && wide_deep_admitted(what, ctx, G, k, r, P, &rc);
   if (rc != FEC_OK) return rc;
   CtxBound bound(ctx, what);
   if (bound.rc != FEC_OK) return bound.rc;
@@ -1767,7 +1790,8 @@ int wide_call(const char* what, FECEncoderCtx* ctx, const uint8_t* d_data, const
   rc = wide_matrix(what, ctx, k, r, &matrix);
   if (rc != FEC_OK) return rc;
   const hipStream_t s = pick_stream(ctx, stream);
-  const qfec::PlanArena arena = qfec::wide_arena(k, r, G, qfec::plan_arena_budget());
+  const uint64_t budget = qfec::plan_arena_budget();
+  const qfec::PlanArena arena = deep ? qfec::wide_deep_arena(k, r, G, budget) : qfec::wide_arena(k, r, G, budget);
   const qfec::PlanWorkspace w = qfec::wide_workspace(G, arena);
   void* ws = nullptr;
   QFEC_HIP(stream_workspace(ctx, s, w.bytes, &ws));
@@ -1785,7 +1809,7 @@ int wide_call(const char* what, FECEncoderCtx* ctx, const uint8_t* d_data, const
   a.plan.stride = arena.stride;
   a.plan.per_chunk = arena.per_chunk;
   a.plan.matrix = matrix;
-  QFEC_HIP(qfec::launch_decode_wide(a, s));
+  QFEC_HIP(deep ? qfec::launch_decode_wide_deep(a, s) : qfec::launch_decode_wide(a, s));
   return FEC_OK;
 }
 
@@ -1834,6 +1858,7 @@ QFEC_EXPORT int fec_recover_scatter_wide_rs_dev(FECEncoderCtx* ctx, const uint64
       return FEC_ERR_NULL;
     }
     int rc = wide_refused(what, G, k, r, P);
+    const bool deep = rc != FEC_OK && wide_deep_admitted(what, ctx, G, k, r, P, &rc);
     if (rc != FEC_OK) return rc;
     CtxBound bound(ctx, what);
     if (bound.rc != FEC_OK) return bound.rc;
@@ -1843,7 +1868,8 @@ QFEC_EXPORT int fec_recover_scatter_wide_rs_dev(FECEncoderCtx* ctx, const uint64
     const hipStream_t s = pick_stream(ctx, stream);
     const bool own_masks = d_masks_out == nullptr;
     const bool own_symlen = d_shard_lens != nullptr && d_symbol_len_out == nullptr;
-    const qfec::PlanArena arena = qfec::wide_arena(k, r, G, qfec::plan_arena_budget());
+    const uint64_t budget = qfec::plan_arena_budget();
+    const qfec::PlanArena arena = deep ? qfec::wide_deep_arena(k, r, G, budget) : qfec::wide_arena(k, r, G, budget);
     const qfec::PlanWorkspace w = qfec::wide_table_workspace(G, own_masks, own_symlen, arena);
     void* ws = nullptr;
     QFEC_HIP(stream_workspace(ctx, s, w.bytes, &ws));
@@ -1862,7 +1888,7 @@ QFEC_EXPORT int fec_recover_scatter_wide_rs_dev(FECEncoderCtx* ctx, const uint64
     a.plan.stride = arena.stride;
     a.plan.per_chunk = arena.per_chunk;
     a.plan.matrix = matrix;
-    QFEC_HIP(qfec::launch_recover_scatter_wide(a, s));
+    QFEC_HIP(deep ? qfec::launch_recover_scatter_wide_deep(a, s) : qfec::launch_recover_scatter_wide(a, s));
     return FEC_OK;
   });
 }
@@ -2254,6 +2280,21 @@ QFEC_EXPORT int fec_decode_plan_mode(FECEncoderCtx* ctx, int mode) {
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
     ctx->plan_mode = mode;
+    return FEC_OK;
+  });
+}
+
+static_assert(FEC_WIDE_ROWS_CAPPED == qfec::kWideRowsCapped && FEC_WIDE_ROWS_ALL == qfec::kWideRowsAll,
+              "fec_forms.hpp states the modes for host-only code");
+QFEC_EXPORT int fec_wide_rows_mode(FECEncoderCtx* ctx, int mode) {
+  return api_call(ctx, [&]() -> int {
+    if (!ctx) return FEC_ERR_NULL;
+    if (!qfec::wide_rows_mode_known(mode)) {
+      set_error("fec_wide_rows_mode: unknown mode %d", mode);
+      return FEC_ERR_RANGE;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->wide_rows_mode = mode;
     return FEC_OK;
   });
 }

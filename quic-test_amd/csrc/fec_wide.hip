@@ -20,6 +20,9 @@
 //    or to the slot row (recover).  The policy bits are those of the runtime-k decode_wave<0, 8>
 //    forms (fec_forms.hpp kWidePolInPlace, kWidePolSlots).  Not tuned: nothing about its speed has
 //    been measured against a variant.
+//    With kDeepRecord among its bits it reads a deep record (fec_plan_build_deep.hpp), whose erased
+//    ids start elsewhere (fec_wide_head.hpp wide_erased_at): the in-place consumer of the shapes with
+//    min(k, r) > 32, which fec_wide_deep.hip builds the records of on a context in FEC_WIDE_ROWS_ALL.
 //
 // Algorithmic bytes per group with e rows to rebuild: reads k * P * ceil(e / 8) (the survivors are
 // re-read per row pass, as in every runtime-k form), e * k * 32 of record per walk pass through the
@@ -47,16 +50,6 @@ static_assert(wide_slot_stride(224, 32) == wide_record_bytes(224, 32) && wide_sl
 static_assert(kWideHeaderBytes % 32u == 0, "record offsets are counted in 32-B units");
 static_assert(kPlanRecLimit == kRecBad, "fec_forms.hpp states the record limit for host-only code");
 
-typedef uint32_t u32x4m __attribute__((ext_vector_type(4), aligned(8)));  // a mask's half: the caller's u64 alignment
-
-// Group g's mask, two 16-B loads.
-__device__ __forceinline__ WideMask load_wide_mask(const uint64_t* __restrict__ masks, uint64_t g) {
-  const u32x4m* p = reinterpret_cast<const u32x4m*>(masks + g * kWideMaskWords);
-  const u32x4m lo = p[0], hi = p[1];
-  return {{static_cast<uint64_t>(lo.y) << 32 | lo.x, static_cast<uint64_t>(lo.w) << 32 | lo.z,
-           static_cast<uint64_t>(hi.y) << 32 | hi.x, static_cast<uint64_t>(hi.w) << 32 | hi.z}};
-}
-
 __global__ __launch_bounds__(256) void classify_wide(const uint64_t* __restrict__ masks, uint64_t groups, uint32_t k,
                                                      uint32_t r, uint32_t* __restrict__ rec_off,
                                                      uint8_t* __restrict__ status) {
@@ -65,12 +58,6 @@ __global__ __launch_bounds__(256) void classify_wide(const uint64_t* __restrict_
   const MaskLosses l = wide_mask_losses(load_wide_mask(masks, g), k, r);
   rec_off[g] = l.lost == 0 ? kRecNone : l.unrecoverable ? kRecBad : 0u;
   if (status) status[g] = l.lost != 0 && l.unrecoverable ? 1 : 0;
-}
-
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-  return static_cast<uint64_t>(hi) << 32 | lo;
 }
 
 __global__ __launch_bounds__(256) void build_records_wide(const uint64_t* __restrict__ masks,
@@ -121,15 +108,16 @@ struct WideBases {
     return sid < k ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - k) * static_cast<uint64_t>(P);
   }
 };
-// decode_piece's DST: row m0 + m at the erased shard (in place) or at the slot row (SLOTS).
-template <bool SLOTS>
+// decode_piece's DST: row m0 + m at the erased shard (in place; its id at byte ERASED_AT + m0 + m of
+// the record) or at the slot row (SLOTS, which reads no erased id).
+template <bool SLOTS, uint32_t ERASED_AT>
 struct WideRows {
   const uint32_t* rw;
   uint8_t* og;
   uint32_t P, m0;
   template <int NW, int POL>
   __device__ __forceinline__ void store(uint32_t m, uint32_t off, const uint32_t (&v)[NW]) const {
-    const uint32_t row = SLOTS ? m0 + m : rec_byte(rw, kWideErasedAt + m0 + m);
+    const uint32_t row = SLOTS ? m0 + m : rec_byte(rw, ERASED_AT + m0 + m);
     stw<NW, POL>(og + row * static_cast<uint64_t>(P) + off, v);
   }
 };
@@ -152,7 +140,7 @@ __global__ __launch_bounds__(256) void decode_wide(const uint8_t* data, const ui
   if (m0 >= e) return;
   const Tab* tabs = h.tabs();
   const WideBases src{h.rw, data + gw * k * static_cast<uint64_t>(P), parity + gw * r * static_cast<uint64_t>(P), k, P};
-  const WideRows<kSlots> dst{h.rw, out + gw * (kSlots ? r : k) * static_cast<uint64_t>(P), P, m0};
+  const WideRows<kSlots, wide_erased_at<POL>> dst{h.rw, out + gw * (kSlots ? r : k) * static_cast<uint64_t>(P), P, m0};
   // decode_wave's walk: 16-B pieces per whole 1 KiB, then 4-B tail pieces shifted back to end at P
   const uint32_t main_end = P & ~1023u;
   for (uint32_t base = 0; base < main_end; base += 1024u)
@@ -184,14 +172,17 @@ hipError_t run_build_records_wide(const WideLaunch& a, uint64_t c0, uint64_t cn,
   });
 }
 
-// The row passes over groups [c0, c0 + cn), their records in the arena.
+// The row passes over groups [c0, c0 + cn), their records in the arena.  The instantiation over
+// the deep record (kDeepRecord) is traced under a form of its own.
 template <int POL>
 hipError_t run_decode_wide(const WideLaunch& a, uint64_t c0, uint64_t cn, hipStream_t s) {
+  constexpr int64_t kForm = (POL & kDeepRecord) != 0 ? static_cast<int64_t>(WideDeepLaunchForm::kDecodeWideDeep)
+                                                     : static_cast<int64_t>(WideLaunchForm::kDecodeWide);
   const uint64_t P = a.P;
   const uint32_t rows = a.k < a.r ? a.k : a.r;
   return for_wave_passes(cn, rows, kWidePassRows, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
     const uint64_t first = c0 + g0;
-    LaunchRecord t = launch_record(static_cast<int64_t>(WideLaunchForm::kDecodeWide), bn, 256, first, gn);
+    LaunchRecord t = launch_record(kForm, bn, 256, first, gn);
     t.k = 0, t.r = kWidePassRows, t.pol = POL, t.aux = m0;
     trace_launch(t);
     hipLaunchKernelGGL((decode_wide<POL>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s, a.data + first * a.k * P,
@@ -214,6 +205,23 @@ hipError_t launch_build_records_wide(const PlanLaunch& p, const uint64_t* masks,
   a.k = k, a.r = r;
   a.plan = p;
   return run_build_records_wide(a, first_group, groups, s);
+}
+
+// classify_wide and the row passes of one plan chunk for a call on the deep path (fec_wide_deep.hip,
+// which has checked the launch and built the chunk's deep records).  In place: decode_wide over the
+// deep record.  Slots: the very instantiation the wide path runs -- it reads the count, the flag,
+// the survivor ids and the tables, which a deep record has where a wide one has them, and no
+// erased id (WideRows<true>; decode_piece asks a DST functor for every store).
+hipError_t launch_classify_wide(const WideLaunch& a, hipStream_t s) {
+  if (a.masks == nullptr || a.rec_off == nullptr || a.groups == 0) return hipErrorInvalidValue;
+  return run_classify_wide(a, s);
+}
+hipError_t launch_decode_wide_deep_rows(const WideLaunch& a, uint64_t first_group, uint64_t groups, hipStream_t s) {
+  if (a.data == nullptr || a.parity == nullptr || a.out == nullptr || a.rec_off == nullptr || a.plan.arena == nullptr ||
+      first_group + groups > a.groups)
+    return hipErrorInvalidValue;
+  return a.slots ? run_decode_wide<kWidePolSlots>(a, first_group, groups, s)
+                 : run_decode_wide<kWideDeepPolInPlace>(a, first_group, groups, s);
 }
 
 hipError_t launch_decode_wide(const WideLaunch& a, hipStream_t s) {

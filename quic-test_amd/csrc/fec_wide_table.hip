@@ -24,6 +24,9 @@
 //    is scatter_decode's over [0, L) (fec_scatter_decode.hpp): passes below the shortest survivor
 //    take plain loads, every other pass var_load; which bytes are stored is fec_scatter_cut.hpp's;
 //    the rebuild is decode_piece<0, 8, POL, NW> unchanged.  Not tuned.
+//    With kDeepRecord among its bits the record is a deep one (fec_plan_build_deep.hpp; the erased
+//    ids at fec_wide_head.hpp wide_erased_at): the consumer of the shapes with min(k, r) > 32 on a
+//    context in FEC_WIDE_ROWS_ALL, whose records fec_wide_deep.hip builds.
 //
 // A lost shard's source entry, a parity row the rule does not use, and the destination entry of any
 // shard the call does not rebuild are never read.  A destination of 0 is not stored to.
@@ -140,7 +143,7 @@ __global__ __launch_bounds__(256) void recover_scatter_wide(const uint64_t* __re
       atomicMin(&shortest[wave], l);
     }
   }
-  if (lane < MAXE) dest_slice[lane] = m0 + lane < e ? gd[ids[kWideErasedAt + m0 + lane]] : 0;  // row m0 + lane of the record
+  if (lane < MAXE) dest_slice[lane] = m0 + lane < e ? gd[ids[wide_erased_at<POL> + m0 + lane]] : 0;  // row m0 + lane of the record
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const uint32_t minlen = __builtin_amdgcn_readfirstlane(shortest[wave]);
@@ -164,14 +167,17 @@ hipError_t run_classify_table_wide(const WideTableLaunch& a, hipStream_t s) {
   });
 }
 
-// The row passes over groups [c0, c0 + cn), their records in the arena.
+// The row passes over groups [c0, c0 + cn), their records in the arena.  The instantiations over
+// the deep record (kDeepRecord) are traced under a form of their own.
 template <int POL, bool VAR>
 hipError_t run_recover_scatter_wide(const WideTableLaunch& a, uint64_t c0, uint64_t cn, hipStream_t s) {
+  constexpr int64_t kForm = (POL & kDeepRecord) != 0 ? static_cast<int64_t>(WideDeepLaunchForm::kRecoverScatterWideDeep)
+                                                     : static_cast<int64_t>(WideTableLaunchForm::kRecoverScatterWide);
   const uint64_t n = a.k + a.r;
   const uint32_t rows = a.k < a.r ? a.k : a.r;
   return for_wave_passes(cn, rows, kWidePassRows, [&](uint64_t g0, uint64_t gn, uint64_t bn, uint32_t m0) {
     const uint64_t first = c0 + g0;
-    LaunchRecord t = launch_record(static_cast<int64_t>(WideTableLaunchForm::kRecoverScatterWide), bn, 256, first, gn);
+    LaunchRecord t = launch_record(kForm, bn, 256, first, gn);
     t.k = 0, t.r = kWidePassRows, t.first = VAR, t.pol = POL, t.aux = m0;
     trace_launch(t);
     hipLaunchKernelGGL((recover_scatter_wide<POL, VAR>), dim3(static_cast<uint32_t>(bn)), dim3(256), 0, s,
@@ -182,6 +188,20 @@ hipError_t run_recover_scatter_wide(const WideTableLaunch& a, uint64_t c0, uint6
 }
 
 }  // namespace
+
+// classify_table_wide and the row passes of one plan chunk for a call on the deep path
+// (fec_wide_deep.hip, which has checked the launch and built the chunk's deep records).
+hipError_t launch_classify_table_wide(const WideTableLaunch& a, hipStream_t s) {
+  if (a.addrs == nullptr || a.masks == nullptr || a.rec_off == nullptr || a.groups == 0) return hipErrorInvalidValue;
+  return run_classify_table_wide(a, s);
+}
+hipError_t launch_recover_scatter_wide_deep_rows(const WideTableLaunch& a, uint64_t first_group, uint64_t groups, hipStream_t s) {
+  if (a.addrs == nullptr || a.dests == nullptr || a.rec_off == nullptr || a.plan.arena == nullptr ||
+      (a.lens != nullptr && a.symlen == nullptr) || first_group + groups > a.groups)
+    return hipErrorInvalidValue;
+  return a.lens ? run_recover_scatter_wide<kWideDeepTablePol, true>(a, first_group, groups, s)
+                : run_recover_scatter_wide<kWideDeepTablePol, false>(a, first_group, groups, s);
+}
 
 hipError_t launch_recover_scatter_wide(const WideTableLaunch& a, hipStream_t s) {
   // a slot holds the shape's largest record and a chunk has at most per_chunk groups (for_plan_chunks):

@@ -37,6 +37,9 @@ FEC_ERR_UNRECOVERABLE = -7
 # fec_decode_plan_mode (Context.decode_plan_mode)
 FEC_PLAN_CODEBOOK = 0
 FEC_PLAN_DEVICE = 1
+# fec_wide_rows_mode (Context.wide_rows_mode)
+FEC_WIDE_ROWS_CAPPED = 0
+FEC_WIDE_ROWS_ALL = 1
 # u64 words per group of the wide calls' erasure masks (fec_hip.h FEC_WIDE_MASK_WORDS)
 WIDE_MASK_WORDS = 4
 
@@ -63,7 +66,7 @@ HIP_SYMBOLS = (
     "fec_recover_gather_var_rs_dev", "fec_encode_gather_var_rs_dev",
     "fec_recover_scatter_rs_dev", "fec_encode_scatter_rs_dev", "fec_decode_plan_mode",
     "fec_decode_wide_rs_dev", "fec_recover_wide_rs_dev", "fec_recover_scatter_wide_rs_dev",
-    "fec_encode_scatter_wide_rs_dev",
+    "fec_encode_scatter_wide_rs_dev", "fec_wide_rows_mode",
 )
 
 
@@ -133,6 +136,7 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
         "fec_synchronize": (_int, [_vp]),
         "fec_decode_loss_hint": (_int, [_vp, _dbl]),
         "fec_decode_plan_mode": (_int, [_vp, _int]),
+        "fec_wide_rows_mode": (_int, [_vp, _int]),
         "fec_group_new": (_vp, [ctypes.POINTER(_int), _int]),
         "fec_group_free": (None, [_vp]),
         "fec_group_size": (_int, [_vp]),
@@ -390,15 +394,15 @@ class Context:
 
     def decode_wide_dev(self, d_data, d_parity, d_masks, num_groups: int, k: int, r: int, packet_size: int,
                         d_status=None, stream: Optional[int] = None) -> None:
-        """decode_dev for k + r <= 256, min(k, r) <= 32: d_masks holds WIDE_MASK_WORDS u64 per group,
-        shard s at bit s & 63 of word s >> 6."""
+        """decode_dev for k + r <= 256, min(k, r) <= 32 (any min(k, r) after wide_rows_mode(FEC_WIDE_ROWS_ALL)):
+        d_masks holds WIDE_MASK_WORDS u64 per group, shard s at bit s & 63 of word s >> 6."""
         rc = self.lib.fec_decode_wide_rs_dev(self.handle, _opt(d_data), _opt(d_parity), _opt(d_masks), num_groups, k, r,
                                              packet_size, _opt(d_status), stream)
         _check(rc, "fec_decode_wide_rs_dev", self.lib)
 
     def recover_wide_dev(self, d_data, d_parity, d_masks, num_groups: int, k: int, r: int, packet_size: int,
                          d_rebuilt, d_status=None, stream: Optional[int] = None) -> None:
-        """recover_dev for k + r <= 256, min(k, r) <= 32, masks as decode_wide_dev: rebuilt shards of
+        """recover_dev for k + r <= 256, min(k, r) <= 32 (or FEC_WIDE_ROWS_ALL), masks as decode_wide_dev: rebuilt shards of
         group g at d_rebuilt[(g*r + m)*P:...]; d_data is not modified."""
         rc = self.lib.fec_recover_wide_rs_dev(self.handle, _opt(d_data), _opt(d_parity), _opt(d_masks), num_groups, k, r,
                                               packet_size, _opt(d_rebuilt), _opt(d_status), stream)
@@ -407,7 +411,7 @@ class Context:
     def recover_scatter_wide_dev(self, d_shard_addrs, d_shard_lens, d_dest_addrs, num_groups: int, k: int, r: int,
                                  packet_size: int, d_status=None, d_masks_out=None, d_symbol_len_out=None,
                                  stream: Optional[int] = None) -> None:
-        """recover_scatter_dev for k + r <= 256, min(k, r) <= 32: the tables have k + r (addresses,
+        """recover_scatter_dev for k + r <= 256, min(k, r) <= 32 (or FEC_WIDE_ROWS_ALL): the tables have k + r (addresses,
         lengths) and k (destinations) entries per group; d_masks_out (nullable) takes WIDE_MASK_WORDS
         u64 per group, shard s at bit s & 63 of word s >> 6."""
         rc = self.lib.fec_recover_scatter_wide_rs_dev(self.handle, _opt(d_shard_addrs), _opt(d_shard_lens),
@@ -448,6 +452,11 @@ class Context:
         PLAN_CODEBOOK (default: host-built per call, synchronous; the table recovers refuse the
         shape) or PLAN_DEVICE (built on the device per call: asynchronous, the table recovers serve it)."""
         _check(self.lib.fec_decode_plan_mode(self.handle, mode), "fec_decode_plan_mode", self.lib)
+
+    def wide_rows_mode(self, mode: int) -> None:
+        """Which shapes the three wide decoders serve: FEC_WIDE_ROWS_CAPPED (default: min(k, r) <= 32)
+        or FEC_WIDE_ROWS_ALL (every k + r <= 256: what the encodes produce, these calls recover)."""
+        _check(self.lib.fec_wide_rows_mode(self.handle, mode), "fec_wide_rows_mode", self.lib)
 
     def synchronize(self) -> None:
         _check(self.lib.fec_synchronize(self.handle), "fec_synchronize", self.lib)
@@ -690,6 +699,10 @@ WIDE_TABLE_LAUNCH_FORMS = {30: "classify_table_wide", 31: "recover_scatter_wide"
 # the kernel of the wide scatter encode (csrc/fec_wide_encode.hip; WideEncodeLaunchForm), again its own:
 # first = 1 with a length table, aux = the first parity row of the pass
 WIDE_ENCODE_LAUNCH_FORMS = {32: "encode_scatter_wide"}
+# the kernels of the wide calls past min(k, r) <= 32 (csrc/fec_wide_deep.hip; WideDeepLaunchForm; a context in
+# FEC_WIDE_ROWS_ALL), again their own; the classifies are 27 and 30, the slots passes decode_wide's (29).
+# Fields as build_records_wide's, decode_wide's and recover_scatter_wide's
+WIDE_DEEP_LAUNCH_FORMS = {33: "build_records_deep", 34: "decode_wide_deep", 35: "recover_scatter_wide_deep"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -719,7 +732,7 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
         form = rec["form"]
         for names in (LAUNCH_FORMS, GATHER_LAUNCH_FORMS, GATHER_VAR_LAUNCH_FORMS, SCATTER_LAUNCH_FORMS,
                       SCATTER_ENCODE_LAUNCH_FORMS, PLAN_LAUNCH_FORMS, WIDE_LAUNCH_FORMS, WIDE_TABLE_LAUNCH_FORMS,
-                      WIDE_ENCODE_LAUNCH_FORMS):
+                      WIDE_ENCODE_LAUNCH_FORMS, WIDE_DEEP_LAUNCH_FORMS):
             if form in names:
                 rec["form"] = names[form]
         out.append(rec)
