@@ -3,7 +3,12 @@ count, erasure patterns (up to r + 1 lost, so some groups are unrecoverable) and
 (host pageable, host page-locked, device in place, device recover) drawn from a seeded
 generator.  Each case is small, the whole sweep runs in seconds; it exists to catch the
 interaction bugs that the per-shape parity tests do not pin (form selection, workspace and
-staging reuse across calls of different shapes on one context).  Decode inputs hold junk in every
+staging reuse across calls of different shapes on one context).  The interactions it covers are
+those of the four contiguous entry points with k <= 20, r <= 8 on the context's own stream: host
+staging against device-resident calls, record offsets of one shape under those of another, the
+loss hint set at random between calls, and the packed recover's block sums and runs workspace.
+The address-table, device-plan, wide and deep calls, caller streams and the two modes meeting on
+one context are tests/test_gpu_cross_family.py's.  Decode inputs hold junk in every
 shard and every mask bit the erasure rule does not read (tests/unread_shards.py)."""
 import os
 

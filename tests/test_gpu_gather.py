@@ -415,6 +415,31 @@ def test_free_with_gather_in_flight(quicfec_mod, oracle_mod, torch_cuda):
 # ------------------------------------------------------------------------------------------
 # 6. Encode gather
 # ------------------------------------------------------------------------------------------
+def make_encode(torch, c, seed):
+    """Arena, table and pre-filled parity buffer of one gather encode of case c (no losses).  Everything
+    is uploaded on torch's stream: synchronise before launching on a side stream."""
+    arenas, where = build_arena(c, seed, encode=True)
+    e = SimpleNamespace(c=c, arenas=arenas)
+    e.dev, e.table = upload_arena(torch, arenas, where)
+    e.whole, e.par = guarded(torch, c.G * c.r * c.P, 0x5A)
+    return e
+
+
+def launch_encode(ctx, e, stream=None):
+    c = e.c
+    ctx.encode_gather_dev(e.table, c.G, c.k, c.r, c.P, e.par, stream=stream)
+
+
+def check_encode(e, what=""):
+    c = e.c
+    what = (what, c.k, c.r, c.P)
+    got = e.whole.cpu().numpy()
+    assert np.array_equal(got[GUARD:-GUARD], c.par), what
+    assert (got[:GUARD] == 0x5A).all() and (got[-GUARD:] == 0x5A).all(), what
+    for d, a in zip(e.dev, e.arenas):
+        assert np.array_equal(d.cpu().numpy(), a), what
+
+
 @pytest.mark.parametrize("k,r", [(10, 3), (4, 2), (20, 5), (7, 3)])
 def test_encode_gather(quicfec_mod, oracle_mod, torch_cuda, k, r):
     """Packets scattered like the recover's shards; parity equals rs_encode, the arena is unchanged
@@ -423,17 +448,10 @@ def test_encode_gather(quicfec_mod, oracle_mod, torch_cuda, k, r):
     G = 37
     with product_ctx(quicfec_mod) as ctx:
         for P in (16, 17, 1200, 2048, 8193):
-            c = make_case(oracle_mod, k, r, P, [0] * G, SEED + P + k)
-            arenas, where = build_arena(c, SEED + P, encode=True)
-            dev, table = upload_arena(torch, arenas, where)
-            whole, par = guarded(torch, G * r * P, 0x5A)
-            ctx.encode_gather_dev(table, G, k, r, P, par)
+            e = make_encode(torch, make_case(oracle_mod, k, r, P, [0] * G, SEED + P + k), SEED + P)
+            launch_encode(ctx, e)
             ctx.synchronize()
-            got = whole.cpu().numpy()
-            assert np.array_equal(got[GUARD:-GUARD], c.par), (k, r, P)
-            assert (got[:GUARD] == 0x5A).all() and (got[-GUARD:] == 0x5A).all(), (k, r, P)
-            for d, a in zip(dev, arenas):
-                assert np.array_equal(d.cpu().numpy(), a), (k, r, P)
+            check_encode(e)
 
 
 # ------------------------------------------------------------------------------------------

@@ -365,15 +365,27 @@ def encode_case(oracle, k, r, P):
     return c
 
 
-def run_encode(torch, ctx, c, seed, stream=None):
+def make_encode(torch, c, seed):
+    """Arena, tables and pre-filled outputs of one var gather encode of case c.  Everything is uploaded
+    on torch's stream: synchronise before launching on a side stream."""
     arenas, where, lens = build_arena(c, seed, encode=True)
     e = SimpleNamespace(c=c, arenas=arenas)
     e.dev, e.table, e.lens = upload_arena(torch, arenas, where, lens)
     e.whole, e.par = guarded(torch, c.G * c.r * c.P, 0x5A)
     e.sym = torch.full((c.G,), 0x77777777, dtype=torch.int32, device="cuda")
+    return e
+
+
+def launch_encode(ctx, e, stream=None):
+    c = e.c
+    ctx.encode_gather_var_dev(e.table, e.lens, c.G, c.k, c.r, c.P, e.par, e.sym, stream=stream)
+
+
+def run_encode(torch, ctx, c, seed, stream=None):
+    e = make_encode(torch, c, seed)
     if stream is not None:
         torch.cuda.synchronize()
-    ctx.encode_gather_var_dev(e.table, e.lens, c.G, c.k, c.r, c.P, e.par, e.sym, stream=stream)
+    launch_encode(ctx, e, stream)
     return e
 
 

@@ -5,6 +5,8 @@ total, statuses, `data` untouched (inputs with junk in every shard and every mas
 rule does not read, tests/unread_shards.py); one wave per group and the sparse-loss scan form; prefix
 sums across many 1024-group scan blocks (both prefix forms), masks at an 8-B-aligned address;
 unsupported shapes refused."""
+import zlib
+
 import numpy as np
 import pytest
 
@@ -344,7 +346,9 @@ def test_packed_runs_edges(gpu_ctx, gpu_ctx_hooks, oracle_mod, torch_cuda, monke
     if case != "sparse_hint":
         gpu_ctx = gpu_ctx_hooks  # QUICFEC_PACKED_RUNS / QUICFEC_MAX_WAVE_BLOCKS: test-library switches
     k, r, P = 10, 3, 1200
-    rng = np.random.default_rng(hash(case) & 0xFFFF)
+    # the same draw in every process (hash() of a str is salted per process, and about one draw in
+    # seven of sparse_hint's holds fewer than the three full groups its masks_in plant)
+    rng = np.random.default_rng(zlib.crc32(case.encode()) & 0xFFFF)
     off = 0
     need = {}
     if case == "chunks":

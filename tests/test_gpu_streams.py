@@ -189,8 +189,9 @@ def make_call(torch, c, api, inputs=None, env=None):
 
 
 def launch(ctx, b, stream, monkeypatch=None):
-    """Queue the call on `stream` (a torch stream); returns without waiting for it."""
-    c, s = b.c, stream.cuda_stream
+    """Queue the call on `stream` (a torch stream; None: the context's own); returns without waiting
+    for it."""
+    c, s = b.c, stream.cuda_stream if stream is not None else None
     assert s != 0                                          # a side stream, not the default one
     if b.env:
         with monkeypatch.context() as mp:                  # the test library reads its switches per call
