@@ -149,9 +149,9 @@ int fec_recover_batch_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const ui
  *     workgroup of four waves, and a compute unit has 160 KiB.
  * Refusals launch nothing and write nothing (fec_hip_last_error names the case): FEC_ERR_NULL for a
  * NULL context or required pointer; FEC_ERR_RANGE for k = 0, r = 0, k + r > 256, min(k, r) > 32,
- * packet_size < 16, num_groups == 0 or >= 2^32.  There are no host-pointer, batcher or packed forms
- * of the wide calls; the wide address-table calls are fec_recover_scatter_wide_rs_dev and
- * fec_encode_scatter_wide_rs_dev, below. */
+ * packet_size < 16, num_groups == 0 or >= 2^32.  There are no host-pointer or batcher forms of
+ * the wide calls; the packed form is fec_recover_packed_wide_rs_dev, the wide address-table calls
+ * are fec_recover_scatter_wide_rs_dev and fec_encode_scatter_wide_rs_dev, below. */
 #define FEC_WIDE_MASK_WORDS 4
 int fec_decode_wide_rs_dev(FECEncoderCtx* ctx, uint8_t* d_data, const uint8_t* d_parity,
                            const uint64_t* d_erasure_masks, uint64_t num_groups, uint32_t k, uint32_t r,
@@ -188,6 +188,107 @@ int fec_recover_batch_rs_dev_packed(FECEncoderCtx* ctx, const uint8_t* d_data, c
                                     const uint64_t* d_masks, uint64_t num_groups, uint32_t k, uint32_t r,
                                     uint32_t packet_size, uint8_t* d_rebuilt, uint32_t* d_row_start,
                                     uint64_t* d_total, uint8_t* d_status, void* stream);
+
+/* ---- packed recover for every shape, one-word masks ----
+ * The packed layout of fec_recover_batch_rs_dev_packed for every shape fec_recover_batch_rs_dev
+ * recovers on the device.  Use this call unless the caller depends on the old call's refusals.
+ *   - Layouts: d_data and d_parity are in the contiguous layouts and are only read.  d_masks holds
+ *     one u64 per group and is only read.
+ *   - Decode rule: the mask rule, the choice of survivors, the status bytes and "bits at and above
+ *     k + r are ignored" are those of fec_recover_batch_rs_dev: bit j < k means data shard j is
+ *     lost, bit k + i parity row i; a group is unrecoverable when fewer parity rows survive than
+ *     data shards are lost; the survivors read are the surviving data shards and the
+ *     lowest-indexed surviving parity rows, as many as data shards are lost.
+ *   - Rows per group: group g rebuilds rows_g rows: the number of its lost data shards when it is
+ *     recoverable, 0 when nothing is lost or the group is unrecoverable.
+ *   - d_row_start: d_row_start[g] is the sum of rows_h for h < g, a u32.  The call writes it for
+ *     every group.
+ *   - Row placement: the m-th lost data shard of group g, in ascending order, goes to
+ *     d_rebuilt + (d_row_start[g] + m) * packet_size as a full packet_size-byte row.  No byte at
+ *     or past total * packet_size is written.
+ *   - d_total (nullable, device memory, u64): *d_total is the number of all rows.
+ *   - d_status (nullable): one byte per group, every byte written; 0 = recovered or nothing lost,
+ *     1 = unrecoverable.
+ *   - No overlap: d_rebuilt must not overlap any input.
+ *   - Stream behaviour: asynchronous on `stream` (NULL = the context's own stream); drained by
+ *     fec_encoder_free like every _dev call.  There is no host synchronise and no readback.
+ *   - Stream workspace: everything the call keeps in the caller stream's workspace -- the
+ *     prefix's block sums, the record offsets, and the record arena where records are built on
+ *     the device -- comes from ONE workspace request per call, because a second, larger request
+ *     may synchronise and reallocate, which would leave the first pointer stale.
+ *   - Served: k >= 1, r >= 1, k + r <= 64, packet_size >= 16, num_groups < 2^32.
+ *     num_groups == 0 is served: nothing is launched, and *d_total = 0 when d_total is given.
+ *   - Records: a shape with a dense codebook takes its records from the codebook, as
+ *     fec_recover_gather_rs_dev does.  A shape past the 2 GiB cap (16+16, 32+8, 60+4) is served
+ *     only on a context in FEC_PLAN_DEVICE (fec_decode_plan_mode): its records are built on the
+ *     device per chunk of the arena, and the row starts stay global across chunks.  On a context
+ *     in FEC_PLAN_CODEBOOK such a shape is refused with FEC_ERR_RANGE: this call never reads masks
+ *     back.
+ *   - A call fec_recover_batch_rs_dev_packed serves is handed to it: the output is byte for byte
+ *     the old call's.  Every other call runs a row prefix, a classify and a record-addressed
+ *     kernel that places a group's rows by d_row_start[g].
+ *   - Zero pivot: the code's matrix is MDS, so a record build cannot meet one; if it did, the
+ *     group would get status 1 and its reserved rows (counted in d_row_start and *d_total) would
+ *     stay unwritten, as its slots do in fec_recover_batch_rs_dev.
+ *   - Refusals launch nothing and write nothing, d_row_start and *d_total included;
+ *     fec_hip_last_error names the case.  FEC_ERR_NULL for a NULL context or a NULL d_data,
+ *     d_parity, d_masks, d_rebuilt or d_row_start (the message names the argument).
+ *     FEC_ERR_RANGE for k = 0, r = 0, k + r > 64, packet_size < 16, num_groups >= 2^32,
+ *     num_groups * min(k, r) >= 2^32 (row indices are 32-bit), and a shape past the codebook cap
+ *     on a context in FEC_PLAN_CODEBOOK. */
+int fec_recover_packed_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
+                              const uint64_t* d_masks, uint64_t num_groups, uint32_t k, uint32_t r,
+                              uint32_t packet_size, uint8_t* d_rebuilt, uint32_t* d_row_start,
+                              uint64_t* d_total, uint8_t* d_status, void* stream);
+
+/* ---- packed recover for every shape, four-word masks ----
+ * The packed layout for what fec_recover_wide_rs_dev recovers: k + r <= 256.
+ *   - Layouts: d_data and d_parity are in the contiguous layouts and are only read.
+ *     d_erasure_masks holds FEC_WIDE_MASK_WORDS u64 per group, shard s at bit s & 63 of word
+ *     s >> 6, and is only read.
+ *   - Decode rule: the mask rule, the choice of survivors, the status bytes and "bits at and above
+ *     k + r are ignored" (in the partial word and in the whole words above it) are those of
+ *     fec_recover_wide_rs_dev: bit j < k means data shard j is lost, bit k + i parity row i; a
+ *     group is unrecoverable when fewer parity rows survive than data shards are lost; the
+ *     survivors read are the surviving data shards and the lowest-indexed surviving parity rows,
+ *     as many as data shards are lost.
+ *   - Rows per group: group g rebuilds rows_g rows: the number of its lost data shards when it is
+ *     recoverable, 0 when nothing is lost or the group is unrecoverable.
+ *   - d_row_start: d_row_start[g] is the sum of rows_h for h < g, a u32.  The call writes it for
+ *     every group.
+ *   - Row placement: the m-th lost data shard of group g, in ascending order, goes to
+ *     d_rebuilt + (d_row_start[g] + m) * packet_size as a full packet_size-byte row.  No byte at
+ *     or past total * packet_size is written.
+ *   - d_total (nullable, device memory, u64): *d_total is the number of all rows.
+ *   - d_status (nullable): one byte per group, every byte written; 0 = recovered or nothing lost,
+ *     1 = unrecoverable.
+ *   - No overlap: d_rebuilt must not overlap any input.
+ *   - Stream behaviour: asynchronous on `stream` (NULL = the context's own stream); drained by
+ *     fec_encoder_free like every _dev call.  There is no host synchronise and no readback.
+ *   - Stream workspace: everything the call keeps in the caller stream's workspace -- the
+ *     prefix's block sums, the record offsets, and the record arena -- comes from ONE workspace
+ *     request per call, because a second, larger request may synchronise and reallocate, which
+ *     would leave the first pointer stale.
+ *   - Served: what fec_recover_wide_rs_dev serves on the same context: k >= 1, r >= 1,
+ *     k + r <= 256, min(k, r) <= 32 by default and every min(k, r) after
+ *     fec_wide_rows_mode(ctx, FEC_WIDE_ROWS_ALL); packet_size >= 16; 0 < num_groups < 2^32.
+ *   - Records are always built on the device, whatever fec_decode_plan_mode says.
+ *   - Shapes with k + r <= 64 are served and give byte for byte what fec_recover_packed_rs_dev
+ *     gives for the same masks in word 0, whatever words 1..3 hold.
+ *   - Zero pivot: the code's matrix is MDS, so a record build cannot meet one; if it did, the
+ *     group would get status 1 and its reserved rows (counted in d_row_start and *d_total) would
+ *     stay unwritten, as its slots do in fec_recover_wide_rs_dev.
+ *   - Refusals launch nothing and write nothing, d_row_start and *d_total included;
+ *     fec_hip_last_error names the case.  FEC_ERR_NULL for a NULL context or a NULL d_data,
+ *     d_parity, d_erasure_masks, d_rebuilt or d_row_start (the message names the argument).
+ *     FEC_ERR_RANGE for what fec_recover_wide_rs_dev refuses, with its texts (k = 0, r = 0,
+ *     k + r > 256, min(k, r) > 32 in FEC_WIDE_ROWS_CAPPED, packet_size < 16, num_groups == 0 or
+ *     >= 2^32), and for num_groups * min(k, r) >= 2^32, because row indices are 32-bit. */
+int fec_recover_packed_wide_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
+                                   const uint64_t* d_erasure_masks /* FEC_WIDE_MASK_WORDS per group */,
+                                   uint64_t num_groups, uint32_t k, uint32_t r, uint32_t packet_size,
+                                   uint8_t* d_rebuilt, uint32_t* d_row_start, uint64_t* d_total,
+                                   uint8_t* d_status, void* stream);
 
 /* ---- address tables: shards and packets wherever they are in device memory ----
  * A receiver that keeps its packets in device memory, in arrival order in a ring or an arena,

@@ -446,6 +446,13 @@ hipError_t launch_decode(const DecodeLaunch& a, hipStream_t s) {
   return hipErrorNotSupported;
 }
 
+// `classify` alone, for another unit's call (fec_packed.hip): run_classify on the fields it reads.
+// With an all-zero a.meta it is the device plans' classify (0 where a record is needed).
+hipError_t launch_classify(const DecodeLaunch& a, hipStream_t s) {
+  if (a.masks == nullptr || a.rec_off == nullptr || a.groups == 0) return hipErrorInvalidValue;
+  return run_classify(a, s);
+}
+
 hipError_t load_decode_unit() {
   hipFuncAttributes at;
   return hipFuncGetAttributes(&at, reinterpret_cast<const void*>(classify));

@@ -745,6 +745,138 @@ inline PlanArena wide_deep_arena(uint32_t k, uint32_t r, uint64_t G, uint64_t bu
   return {stride, per, per * stride};
 }
 
+// ---- packed recover for every shape (fec_recover_packed_rs_dev, fec_recover_packed_wide_rs_dev;
+// fec_packed.hip) ----
+// The packed layout (fec_recover_batch_rs_dev_packed: group g's rows from row row_start[g], nothing
+// between groups) for every shape a slot recover serves.  The row prefix writes row_start for every
+// group; a record-addressed consumer then reads rec_off[g] and row_start[g] together and puts row
+// m0 + m at out + (row_start[g] + m0 + m) * P.  A call the old packed call serves is handed to it.
+//
+// The paths of a call, decided here and nowhere else; the shim only launches.
+enum class PackedPath : int {
+  kRefused = 0,
+  kEmpty,       // num_groups == 0 (one-word call): nothing launched, *total = 0
+  kDelegate,    // what fec_recover_batch_rs_dev_packed serves: its forms (packed_form), untouched
+  kCodebook,    // records from the dense codebook: rows prefix, classify, recover_packed
+  kDevicePlan,  // past the codebook cap in FEC_PLAN_DEVICE: the same with build_records per plan chunk
+  kWide,        // four-word masks: the wide prefix, classify_wide, per chunk build_records_wide, recover_packed_wide
+  kDeep,        // the same past the wide builder's rows (FEC_WIDE_ROWS_ALL): build_records_deep
+};
+enum class PackedRefusal : int {
+  kServed = 0,
+  kShape,       // k = 0, r = 0 or k + r past the mask's width
+  kRows,        // wide: min(k, r) > 32 on a context in FEC_WIDE_ROWS_CAPPED
+  kPacket,      // packet_size < 16
+  kNoGroups,    // wide: num_groups == 0
+  kGroups,      // num_groups >= 2^32
+  kRowIndex,    // num_groups * min(k, r) >= 2^32: row indices are 32-bit
+  kNoCodebook,  // one-word: the codebook is past its cap and the context is in FEC_PLAN_CODEBOOK
+};
+struct PackedRoute {
+  PackedPath path;
+  PackedRefusal why;  // kServed unless refused
+  uint32_t passes;    // consumer launches per (plan) chunk of the new consumers: ceil(min(k, r) / 8); else 0
+};
+// What the context's modes and the shape's codebook say, as bits.
+constexpr int kPackedPlanDevice = 1;  // fec_decode_plan_mode is FEC_PLAN_DEVICE
+constexpr int kPackedDense = 2;       // the shape's codebook of every pattern is inside its cap (gf256.hpp codebook_layout)
+constexpr int kPackedRowsAll = 4;     // fec_wide_rows_mode is FEC_WIDE_ROWS_ALL
+constexpr uint32_t kPackedMaxShards = 64;  // one-word masks (gf256.hpp kMaxDecodeShards)
+// The policy bits of recover_packed and recover_packed_wide: the slot layout's runtime-k forms
+// (decode_wave<0, 8> as decode_form picks it for compact_out; kWidePolSlots), 8 rows per pass.
+constexpr int kPackedPol = kNtStore | kNoCoefBranch | kCompactOut;
+constexpr uint32_t kPackedPassRows = 8;
+constexpr uint32_t packed_passes(uint32_t k, uint32_t r) { return ((k < r ? k : r) + kPackedPassRows - 1) / kPackedPassRows; }
+constexpr bool packed_rows_fit(uint64_t G, uint32_t k, uint32_t r) { return G * (k < r ? k : r) < (1ull << 32); }
+// Whether fec_recover_batch_rs_dev_packed serves (G > 0, k, r, P): its own rule (decode_form of the
+// compact-out call with device masks and a dense codebook, then packed_form) and its row-index limit.
+inline bool packed_old_serves(uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  if (k == 0 || r == 0 || k + r > kPackedMaxShards || P == 0 || G * r >= (1ull << 32)) return false;
+  const uint64_t some_mask = 0;
+  DecodeLaunch a{};
+  a.masks = &some_mask;  // not read: decode_form asks only whether there are masks
+  a.compact_out = true;
+  a.groups = G, a.k = k, a.r = r, a.P = P;
+  return packed_form(a, decode_form(a), -1) != PackedForm::kRefused;
+}
+// fec_recover_packed_rs_dev.
+inline PackedRoute packed_route(int bits, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  if (k == 0 || r == 0 || uint64_t{k} + r > kPackedMaxShards) return {PackedPath::kRefused, PackedRefusal::kShape, 0};
+  if (P < kVecMinP) return {PackedPath::kRefused, PackedRefusal::kPacket, 0};
+  if (G >= (1ull << 32)) return {PackedPath::kRefused, PackedRefusal::kGroups, 0};
+  if (!packed_rows_fit(G, k, r)) return {PackedPath::kRefused, PackedRefusal::kRowIndex, 0};
+  if (G == 0) return {PackedPath::kEmpty, PackedRefusal::kServed, 0};
+  // (a shape the old call serves has a dense codebook: the mask-addressed shapes' books are a few KiB)
+  if ((bits & kPackedDense) != 0 && packed_old_serves(G, k, r, P)) return {PackedPath::kDelegate, PackedRefusal::kServed, 0};
+  if ((bits & kPackedDense) != 0) return {PackedPath::kCodebook, PackedRefusal::kServed, packed_passes(k, r)};
+  if ((bits & kPackedPlanDevice) != 0) return {PackedPath::kDevicePlan, PackedRefusal::kServed, packed_passes(k, r)};
+  return {PackedPath::kRefused, PackedRefusal::kNoCodebook, 0};
+}
+// fec_recover_packed_wide_rs_dev: wide_route's verdict, then the row-index limit.
+inline PackedRoute packed_wide_route(int bits, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  const WideRoute w = wide_route((bits & kPackedRowsAll) != 0 ? kWideRowsAll : kWideRowsCapped, G, k, r, P);
+  switch (w.why) {
+    case WideRefusal::kServed: break;
+    case WideRefusal::kShape: return {PackedPath::kRefused, PackedRefusal::kShape, 0};
+    case WideRefusal::kRows: return {PackedPath::kRefused, PackedRefusal::kRows, 0};
+    case WideRefusal::kPacket: return {PackedPath::kRefused, PackedRefusal::kPacket, 0};
+    case WideRefusal::kNoGroups: return {PackedPath::kRefused, PackedRefusal::kNoGroups, 0};
+    case WideRefusal::kGroups: return {PackedPath::kRefused, PackedRefusal::kGroups, 0};
+  }
+  if (!packed_rows_fit(G, k, r)) return {PackedPath::kRefused, PackedRefusal::kRowIndex, 0};
+  return {w.path == WidePath::kDeep ? PackedPath::kDeep : PackedPath::kWide, PackedRefusal::kServed, w.passes};
+}
+// The record arena of a packed call on `path` of G groups: plan_arena, wide_arena or wide_deep_arena;
+// none (all zero) on the codebook path, whose records are the codebook's.
+inline PlanArena packed_arena(PackedPath path, uint32_t k, uint32_t r, uint64_t G, uint64_t budget) {
+  switch (path) {
+    case PackedPath::kDevicePlan: return plan_arena(k, r, G, budget);
+    case PackedPath::kWide: return wide_arena(k, r, G, budget);
+    case PackedPath::kDeep: return wide_deep_arena(k, r, G, budget);
+    default: return {0, 0, 0};
+  }
+}
+// The workspace of a packed call that takes a new consumer, byte offsets from its start, all of it
+// ONE stream_workspace request (a second, larger request may synchronise and reallocate, which would
+// leave the first pointer stale): the prefix's block sums, one u32 per kPackedRowsPerBlock groups; G
+// record offsets; the record arena, 256-B aligned, empty on the codebook path.  The u32 arrays are
+// 8-B aligned.
+constexpr uint32_t kPackedRowsPerThread = 4;
+constexpr uint32_t kPackedRowsPerBlock = 256 * kPackedRowsPerThread;  // fec_runs.hip kRowsPerBlock
+// Blocks up to which every block of the row-start write adds up the sums before it itself (two
+// launches); past it a one-block scan of the sums runs in between (fec_runs.hip kRowsDirectBlocks).
+constexpr uint32_t kPackedRowsDirectBlocks = 4096;
+struct PackedWorkspace {
+  uint64_t block_sums, rec_off, arena, bytes;
+};
+inline PackedWorkspace packed_workspace(uint64_t G, const PlanArena& a) {
+  PackedWorkspace w{};
+  w.block_sums = 0;
+  w.rec_off = ((G + kPackedRowsPerBlock - 1) / kPackedRowsPerBlock * sizeof(uint32_t) + 7u) & ~uint64_t{7};
+  w.arena = (w.rec_off + G * sizeof(uint32_t) + 255u) & ~uint64_t{255};
+  w.bytes = w.arena + a.bytes;
+  return w;
+}
+// One packed call on a new consumer (fec_packed.hip launch_recover_packed).
+struct PackedLaunch {
+  PackedPath path;           // kCodebook, kDevicePlan, kWide or kDeep
+  const uint8_t* data;       // the contiguous layouts, only read
+  const uint8_t* parity;
+  const uint64_t* masks;     // one word per group (kCodebook, kDevicePlan) or four, only read
+  uint64_t groups;
+  uint32_t k, r, P;
+  uint8_t* out;              // packed rows
+  uint32_t* row_start;       // one u32 per group, written for every group
+  uint64_t* total;           // nullable
+  uint8_t* status;           // nullable
+  uint32_t* block_sums;      // workspace (packed_workspace)
+  uint32_t* rec_off;         // workspace, one u32 per group
+  const uint8_t* codebook;   // kCodebook: the dense CoefEntry codebook, device
+  const uint64_t* binom;     // kCodebook, kDevicePlan: device, 65 x 65
+  LevelMeta meta;            // kCodebook
+  PlanLaunch plan;           // the other paths: arena (packed_arena), stride, per_chunk, the r x k matrix
+};
+
 // ---- the wide scatter encode (fec_encode_scatter_wide_rs_dev; fec_wide_encode.hip) ----
 // The scatter encode's tables (TableEncodeLaunch) for groups of up to 256 shards: k entries per
 // group of addresses (0 = absent) and, nullable, lengths; r destinations per group.  An encode

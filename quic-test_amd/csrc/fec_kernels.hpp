@@ -2,8 +2,8 @@
 // gfx950 kernels, one translation unit per kernel family: fec_encode.hip, fec_decode.hip,
 // fec_decode_fused.hip, fec_runs.hip, fec_server.hip, fec_util.hip; the address-table units
 // fec_gather.hip, fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip with their shared
-// fec_table.hpp; fec_plan.hip; fec_wide.hip; fec_wide_table.hip; fec_wide_encode.hip; fec_wide_deep.hip.  Internal to
-// libfec_hip.so.
+// fec_table.hpp; fec_plan.hip; fec_wide.hip; fec_wide_table.hip; fec_wide_encode.hip; fec_wide_deep.hip;
+// fec_packed.hip.  Internal to libfec_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -109,6 +109,21 @@ hipError_t launch_recover_scatter_wide_deep_rows(const WideTableLaunch& a, uint6
 uint64_t rows_prefix_workspace_bytes(uint64_t groups);
 hipError_t launch_rows_prefix(const uint64_t* masks, uint64_t groups, uint32_t k, uint32_t r, uint32_t* row_start,
                               uint32_t* block_sums, uint64_t* total, hipStream_t s);
+// The packed recovers for every shape (fec_packed.hip; fec_forms.hpp PackedLaunch, a.path one of
+// kCodebook, kDevicePlan, kWide, kDeep): the row prefix over the call's masks (launch_rows_prefix for
+// one-word masks, the unit's own block sums and row-start write for four-word masks), the path's
+// classify over every group, then per chunk of a.plan's arena (the codebook path: all groups at once)
+// the path's record build and packed_passes(k, r) launches of recover_packed / recover_packed_wide,
+// in stream order.
+hipError_t launch_recover_packed(const PackedLaunch& a, hipStream_t s);
+// What fec_packed.hip calls in the units of the kernels it shares: `classify` over every group of a
+// one-word call (fec_decode.hip; an all-zero a.meta gives the device plans' classify), the one-block
+// scan of `blocks` block sums (fec_runs.hip rows_scan_blocks, which reads no mask) and the deep
+// records of one plan chunk (fec_wide_deep.hip build_records_deep, as launch_build_records_wide).
+hipError_t launch_classify(const DecodeLaunch& a, hipStream_t s);
+hipError_t launch_rows_scan_blocks(uint32_t* block_sums, uint64_t blocks, uint64_t groups, uint64_t* total, hipStream_t s);
+hipError_t launch_build_records_deep(const PlanLaunch& p, const uint64_t* masks, uint32_t* rec_off, uint8_t* status,
+                                     uint64_t first_group, uint64_t groups, uint32_t k, uint32_t r, hipStream_t s);
 // LDS run image per workgroup of 512 groups (tools/probe_runs.hip; DESIGN_HISTORY.md §5 round 4): C5's
 // ~59 rows per tile fit 48 KB (40 rows) mostly; two workgroups per CU.
 // recover_runs' run image per workgroup.

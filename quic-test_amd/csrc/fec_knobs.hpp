@@ -172,4 +172,15 @@ enum class WideDeepLaunchForm : int64_t {
   kRecoverScatterWideDeep = 35,  // as kRecoverScatterWide
 };
 
+// The kernels of the packed recovers for every shape (fec_packed.hip: fec_recover_packed_rs_dev,
+// fec_recover_packed_wide_rs_dev), numbered on in a list of their own; named by
+// quicfec.PACKED_LAUNCH_FORMS.  The one-word prefix is kRowsBlockSums .. kRowsWrite's, the scan of the
+// block sums kRowsScanBlocks for either mask width, the classifies and record builds their families'.
+enum class PackedLaunchForm : int64_t {
+  kRowsBlockSumsWide = 36,   // first_item / items: 0 and the call's groups
+  kRowsWriteWide = 37,       // as kRowsWrite; direct: writes the total itself
+  kRecoverPacked = 38,       // first_item / items: groups of the call; k = 0, r = 8; pol; aux: first row of the pass
+  kRecoverPackedWide = 39,   // as kRecoverPacked, over a wide or a deep record
+};
+
 }  // namespace qfec

@@ -1,7 +1,7 @@
 // fec_launch.hpp — what the host launchers of the kernel translation units (fec_encode.hip,
 // fec_decode.hip, fec_decode_fused.hip, fec_runs.hip, fec_server.hip, fec_util.hip, fec_gather.hip,
 // fec_gather_var.hip, fec_scatter.hip, fec_scatter_encode.hip, fec_plan.hip, fec_wide.hip,
-// fec_wide_table.hip, fec_wide_encode.hip, fec_wide_deep.hip) share: the per-launch
+// fec_wide_table.hip, fec_wide_encode.hip, fec_wide_deep.hip, fec_packed.hip) share: the per-launch
 // limits with their test switches, the chunk walk, the pass-and-chunk walk of the wave-per-group
 // kernels, the row passes of the runtime-k encodes, the launch trace's record, and the small
 // launch arguments more than one unit computes (knob, decode_swizzle, rank_meta).  Host code only.

@@ -17,6 +17,7 @@
 #include "fec_kernels.hpp"
 #include "fec_knobs.hpp"
 #include "fec_launch.hpp"  // launch limits, for_chunks, launch_record, knob, rank_meta
+#include "fec_scan.hpp"    // block_inclusive_scan, block_sum
 
 namespace qfec {
 namespace {
@@ -357,30 +358,10 @@ constexpr uint32_t kRowsPerThread = 4;
 static_assert(kRowsPerThread == 4, "thread_rows and the rows_* kernels are written for 4 groups per thread");
 constexpr uint32_t kRowsPerBlock = 256 * kRowsPerThread;
 constexpr uint32_t kRowsDirectBlocks = 4096;
-
-// Inclusive scan of one value per thread over a 256-thread block (LDS, 8 steps).
-__device__ __forceinline__ uint32_t block_inclusive_scan(uint32_t v, uint32_t* lds) {
-  const uint32_t t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    const uint32_t add = t >= d ? lds[t - d] : 0u;
-    __syncthreads();
-    lds[t] += add;
-    __syncthreads();
-  }
-  return lds[t];
-}
-
-// Sum of one value per thread over a 256-thread block (wave reduction, then 4 partials).
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* lds) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const uint32_t total = lds[0] + lds[1] + lds[2] + lds[3];
-  __syncthreads();
-  return total;
-}
+// (block_inclusive_scan and block_sum: fec_scan.hpp, shared with the prefix over four-word masks,
+// fec_packed.hip, which takes the same block and the same limit from fec_forms.hpp)
+static_assert(kRowsPerBlock == kPackedRowsPerBlock && kRowsDirectBlocks == kPackedRowsDirectBlocks,
+              "fec_forms.hpp states the prefix's block and its two-launch limit for fec_packed.hip and host-only code");
 
 // The rows of a thread's kRowsPerThread consecutive groups (one 32-B load of their masks when
 // they are all in range).
@@ -487,6 +468,15 @@ hipError_t launch_rows_prefix(const uint64_t* masks, uint64_t groups, uint32_t k
     hipLaunchKernelGGL(rows_write<false>, grid, dim3(256), 0, s, masks, groups, k, r, block_sums, row_start,
                        nullptr);
   }
+  return hipGetLastError();
+}
+
+// rows_scan_blocks alone, for the prefix over four-word masks (fec_packed.hip): the one-block scan of
+// block sums does not read a mask.
+hipError_t launch_rows_scan_blocks(uint32_t* block_sums, uint64_t blocks, uint64_t groups, uint64_t* total, hipStream_t s) {
+  if (block_sums == nullptr || blocks == 0 || blocks > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  trace_launch(launch_record(LaunchForm::kRowsScanBlocks, 1, 256, 0, groups));
+  hipLaunchKernelGGL(rows_scan_blocks, dim3(1), dim3(256), 0, s, block_sums, static_cast<uint32_t>(blocks), total);
   return hipGetLastError();
 }
 

@@ -1893,6 +1893,158 @@ QFEC_EXPORT int fec_recover_scatter_wide_rs_dev(FECEncoderCtx* ctx, const uint64
   });
 }
 
+// ---- packed recover for every shape (fec_packed.hip) ----
+namespace {
+
+// A refusal of the two packed calls with its text; FEC_OK when served.  The wide call's texts are
+// the wide calls' (wide_refusal).
+int packed_refusal(const char* what, bool wide, qfec::PackedRefusal why, uint64_t G, uint32_t k, uint32_t r, uint32_t P) {
+  using R = qfec::PackedRefusal;
+  switch (why) {
+    case R::kServed:
+      return FEC_OK;
+    case R::kShape:
+      if (wide) return wide_refusal(what, qfec::WideRefusal::kShape, G, k, r, P);
+      set_error("%s: unsupported k=%u r=%u (need k>0, r>0, k+r<=%u)", what, k, r, qfec::kPackedMaxShards);
+      return FEC_ERR_RANGE;
+    case R::kRows:
+      return wide_refusal(what, qfec::WideRefusal::kRows, G, k, r, P);
+    case R::kPacket:
+      return wide_refusal(what, qfec::WideRefusal::kPacket, G, k, r, P);
+    case R::kNoGroups:
+      return wide_refusal(what, qfec::WideRefusal::kNoGroups, G, k, r, P);
+    case R::kGroups:
+      return wide_refusal(what, qfec::WideRefusal::kGroups, G, k, r, P);
+    case R::kRowIndex:
+      set_error("%s: %llu groups x %u rows exceed 32-bit row indices", what, static_cast<unsigned long long>(G), k < r ? k : r);
+      return FEC_ERR_RANGE;
+    case R::kNoCodebook:  // the address-table recovers' text: this call never reads masks back either
+      set_error("%s: the codebook of k=%u r=%u exceeds the %llu-byte cap (sparse-plan shape: use "
+                "fec_recover_batch_rs_dev, or fec_decode_plan_mode(ctx, FEC_PLAN_DEVICE))", what, k, r,
+                static_cast<unsigned long long>(kCodebookCap));
+      return FEC_ERR_RANGE;
+  }
+  return FEC_ERR_RANGE;
+}
+
+// The context's modes as packed_route's bits.
+int packed_mode_bits(FECEncoderCtx* ctx) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return (ctx->plan_mode == FEC_PLAN_DEVICE ? qfec::kPackedPlanDevice : 0) |
+         (ctx->wide_rows_mode == FEC_WIDE_ROWS_ALL ? qfec::kPackedRowsAll : 0);
+}
+
+struct PackedCall {
+  const uint8_t *data, *parity;
+  const uint64_t* masks;
+  uint64_t G;
+  uint32_t k, r, P;
+  uint8_t* out;
+  uint32_t* row_start;
+  uint64_t* total;
+  uint8_t* status;
+  void* stream;
+};
+
+// A packed call on one of the new consumers (route.path kCodebook, kDevicePlan, kWide or kDeep),
+// under the context's lock and on its device: the records' source, the stream, and ONE request to
+// the caller stream's workspace for everything the call keeps there (packed_workspace: block sums,
+// record offsets, the record arena).
+int packed_call_locked(const char* what, FECEncoderCtx* ctx, const PackedCall& c, const qfec::PackedRoute& route) {
+  const uint64_t G = c.G;
+  const uint32_t k = c.k, r = c.r, P = c.P;
+  CtxBound bound(ctx, what);
+  if (bound.rc != FEC_OK) return bound.rc;
+  qfec::PackedLaunch a{};
+  a.path = route.path;
+  int rc = FEC_OK;
+  if (route.path == qfec::PackedPath::kCodebook || route.path == qfec::PackedPath::kDevicePlan) {
+    DecodePlan* plan = nullptr;
+    if ((rc = get_decode_plan(ctx, k, r, &plan)) != FEC_OK) return rc;
+    a.binom = ctx->d_binom.as<uint64_t>();
+    if (route.path == qfec::PackedPath::kCodebook) {
+      a.codebook = plan->codebook.as<uint8_t>();
+      a.meta = level_meta(plan->layout, r);
+    } else if ((rc = plan_matrix(plan, &a.plan.matrix)) != FEC_OK) {
+      return rc;
+    }
+  } else if ((rc = wide_matrix(what, ctx, k, r, &a.plan.matrix)) != FEC_OK) {
+    return rc;
+  }
+  const hipStream_t s = pick_stream(ctx, c.stream);
+  const qfec::PlanArena arena = qfec::packed_arena(route.path, k, r, G, qfec::plan_arena_budget());
+  const qfec::PackedWorkspace w = qfec::packed_workspace(G, arena);
+  void* ws = nullptr;
+  QFEC_HIP(stream_workspace(ctx, s, w.bytes, &ws));
+  uint8_t* base = static_cast<uint8_t*>(ws);
+  a.data = c.data, a.parity = c.parity, a.masks = c.masks;
+  a.groups = G, a.k = k, a.r = r, a.P = P;
+  a.out = c.out, a.row_start = c.row_start, a.total = c.total, a.status = c.status;
+  a.block_sums = reinterpret_cast<uint32_t*>(base + w.block_sums);
+  a.rec_off = reinterpret_cast<uint32_t*>(base + w.rec_off);
+  if (arena.bytes != 0) {
+    a.plan.arena = base + w.arena;
+    a.plan.stride = arena.stride;
+    a.plan.per_chunk = arena.per_chunk;
+  }
+  QFEC_HIP(qfec::launch_recover_packed(a, s));
+  return FEC_OK;
+}
+
+// The NULL checks of both packed calls; the message names the argument.
+int packed_nulls(const char* what, FECEncoderCtx* ctx, const PackedCall& c, const char* masks_name) {
+  const char* name = !ctx ? "the context" : !c.data ? "d_data" : !c.parity ? "d_parity" : !c.masks ? masks_name
+                     : !c.out ? "d_rebuilt" : !c.row_start ? "d_row_start" : nullptr;
+  if (name == nullptr) return FEC_OK;
+  set_error("%s: %s is NULL", what, name);
+  return FEC_ERR_NULL;
+}
+
+}  // namespace
+
+QFEC_EXPORT int fec_recover_packed_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
+                                          const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
+                                          uint8_t* d_rebuilt, uint32_t* d_row_start, uint64_t* d_total, uint8_t* d_status,
+                                          void* stream) {
+  return api_call(ctx, [&]() -> int {
+    const char* what = "fec_recover_packed_rs_dev";
+    const PackedCall c{d_data, d_parity, d_masks, G, k, r, P, d_rebuilt, d_row_start, d_total, d_status, stream};
+    int rc = packed_nulls(what, ctx, c, "d_masks");
+    if (rc != FEC_OK) return rc;
+    qfec::CodebookLayout layout;
+    const int bits = packed_mode_bits(ctx) | (qfec::codebook_layout(k, r, kCodebookCap, layout) ? qfec::kPackedDense : 0);
+    const qfec::PackedRoute route = qfec::packed_route(bits, G, k, r, P);
+    if ((rc = packed_refusal(what, false, route.why, G, k, r, P)) != FEC_OK) return rc;
+    if (route.path == qfec::PackedPath::kEmpty) {
+      if (!d_total) return FEC_OK;
+      CtxBound bound(ctx, what);
+      if (bound.rc != FEC_OK) return bound.rc;
+      QFEC_HIP(hipMemsetAsync(d_total, 0, sizeof(uint64_t), pick_stream(ctx, stream)));
+      return FEC_OK;
+    }
+    // what the old call serves is the old call's, byte for byte: its forms, its workspace, its errors
+    if (route.path == qfec::PackedPath::kDelegate)
+      return fec_recover_batch_rs_dev_packed(ctx, d_data, d_parity, d_masks, G, k, r, P, d_rebuilt, d_row_start, d_total,
+                                             d_status, stream);
+    return packed_call_locked(what, ctx, c, route);
+  });
+}
+
+QFEC_EXPORT int fec_recover_packed_wide_rs_dev(FECEncoderCtx* ctx, const uint8_t* d_data, const uint8_t* d_parity,
+                                               const uint64_t* d_masks, uint64_t G, uint32_t k, uint32_t r, uint32_t P,
+                                               uint8_t* d_rebuilt, uint32_t* d_row_start, uint64_t* d_total,
+                                               uint8_t* d_status, void* stream) {
+  return api_call(ctx, [&]() -> int {
+    const char* what = "fec_recover_packed_wide_rs_dev";
+    const PackedCall c{d_data, d_parity, d_masks, G, k, r, P, d_rebuilt, d_row_start, d_total, d_status, stream};
+    int rc = packed_nulls(what, ctx, c, "d_erasure_masks");
+    if (rc != FEC_OK) return rc;
+    const qfec::PackedRoute route = qfec::packed_wide_route(packed_mode_bits(ctx), G, k, r, P);
+    if ((rc = packed_refusal(what, true, route.why, G, k, r, P)) != FEC_OK) return rc;
+    return packed_call_locked(what, ctx, c, route);
+  });
+}
+
 // ---- the wide encode from an address table into a table of destinations (fec_wide_encode.hip) ----
 namespace {
 

@@ -97,17 +97,7 @@ __global__ __launch_bounds__(256) void build_records_wide(const uint64_t* __rest
   }
 }
 
-// decode_piece's SRC: the base of survivor s from the header's id.
-struct WideBases {
-  const uint32_t* rw;
-  const uint8_t* dg;
-  const uint8_t* pg;
-  uint32_t k, P;
-  __device__ __forceinline__ const uint8_t* operator()(uint32_t s) const {
-    const uint32_t sid = rec_byte(rw, s);
-    return sid < k ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - k) * static_cast<uint64_t>(P);
-  }
-};
+// (decode_piece's SRC, WideBases: fec_wide_head.hpp, shared with the packed consumer, fec_packed.hip)
 // decode_piece's DST: row m0 + m at the erased shard (in place; its id at byte ERASED_AT + m0 + m of
 // the record) or at the slot row (SLOTS, which reads no erased id).
 template <bool SLOTS, uint32_t ERASED_AT>

@@ -113,6 +113,16 @@ hipError_t launch_decode_wide_deep(const WideLaunch& a, hipStream_t s) {
       [&](uint64_t c0, uint64_t cn) { return launch_decode_wide_deep_rows(a, c0, cn, s); });
 }
 
+// build_records_deep for another unit's call (fec_packed.hip), as launch_build_records_wide: groups
+// [first_group, first_group + groups) of a call on the deep path, one plan chunk.
+hipError_t launch_build_records_deep(const PlanLaunch& p, const uint64_t* masks, uint32_t* rec_off, uint8_t* status,
+                                     uint64_t first_group, uint64_t groups, uint32_t k, uint32_t r, hipStream_t s) {
+  if (masks == nullptr || rec_off == nullptr || p.arena == nullptr || p.matrix == nullptr ||
+      p.stride != wide_deep_slot_stride(k, r) || uint64_t{k} + r > kWideMaxShards || (k < r ? k : r) > kWideDeepMaxRows)
+    return hipErrorInvalidValue;
+  return run_build_records_deep(p, masks, rec_off, status, first_group, groups, k, r, s);
+}
+
 hipError_t launch_recover_scatter_wide_deep(const WideTableLaunch& a, hipStream_t s) {
   if (!deep_plan_ok(a.plan, a.groups, a.k, a.r, a.P) || a.addrs == nullptr || a.dests == nullptr || a.masks == nullptr ||
       a.rec_off == nullptr)

@@ -1,6 +1,6 @@
 // fec_wide_head.hpp — the wide record's header as the kernels that consume a wide record read it
-// (fec_plan_build_wide.hpp states the layout): decode_wide (fec_wide.hip) and recover_scatter_wide
-// (fec_wide_table.hip); the deep record's (fec_plan_build_deep.hpp) is the same header but for the
+// (fec_plan_build_wide.hpp states the layout): decode_wide (fec_wide.hip), recover_scatter_wide
+// (fec_wide_table.hip) and recover_packed_wide (fec_packed.hip); the deep record's (fec_plan_build_deep.hpp) is the same header but for the
 // place of the erased ids, which a kernel takes from its form bits (wide_erased_at).  And a group's
 // mask as the record builders load it (build_records_wide, fec_wide.hip; build_records_deep,
 // fec_wide_deep.hip).  Internal to its translation unit (unnamed namespace), as fec_device.hpp's.
@@ -30,6 +30,19 @@ static_assert(kWideCountAt % 4u == 0 && kWideXorAt == kWideCountAt + 1u, "e and 
 // Where the erased ids start in the record a kernel with form bits POL reads.
 template <int POL>
 constexpr uint32_t wide_erased_at = (POL & kDeepRecord) != 0 ? kDeepErasedAt : kWideErasedAt;
+
+// decode_piece's SRC over the contiguous layouts: the base of survivor s from the header's id
+// (decode_wide, fec_wide.hip; recover_packed_wide, fec_packed.hip).
+struct WideBases {
+  const uint32_t* rw;
+  const uint8_t* dg;
+  const uint8_t* pg;
+  uint32_t k, P;
+  __device__ __forceinline__ const uint8_t* operator()(uint32_t s) const {
+    const uint32_t sid = rec_byte(rw, s);
+    return sid < k ? dg + sid * static_cast<uint64_t>(P) : pg + (sid - k) * static_cast<uint64_t>(P);
+  }
+};
 
 typedef uint32_t u32x4m __attribute__((ext_vector_type(4), aligned(8)));  // a mask's half: the caller's u64 alignment
 

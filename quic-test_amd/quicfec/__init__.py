@@ -67,6 +67,7 @@ HIP_SYMBOLS = (
     "fec_recover_scatter_rs_dev", "fec_encode_scatter_rs_dev", "fec_decode_plan_mode",
     "fec_decode_wide_rs_dev", "fec_recover_wide_rs_dev", "fec_recover_scatter_wide_rs_dev",
     "fec_encode_scatter_wide_rs_dev", "fec_wide_rows_mode",
+    "fec_recover_packed_rs_dev", "fec_recover_packed_wide_rs_dev",
 )
 
 
@@ -171,6 +172,8 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
         "fec_recover_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp]),
         "fec_recover_scatter_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
         "fec_encode_scatter_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
+        "fec_recover_packed_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+        "fec_recover_packed_wide_rs_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -333,6 +336,25 @@ class Context:
                                                       _ptr(d_total) if d_total is not None else None,
                                                       _ptr(d_status) if d_status is not None else None, stream)
         _check(rc, "fec_recover_batch_rs_dev_packed", self.lib)
+
+    def recover_packed_any_dev(self, d_data, d_parity, d_masks, num_groups: int, k: int, r: int, packet_size: int,
+                               d_rebuilt, d_row_start, d_total=None, d_status=None, stream: Optional[int] = None) -> None:
+        """recover_packed_dev for every shape recover_dev serves on the device (k + r <= 64, packet_size >= 16;
+        past the codebook cap after decode_plan_mode(FEC_PLAN_DEVICE)): group g's m-th lost data shard at row
+        d_row_start[g] + m of d_rebuilt, d_total (one u64, nullable) = all rows."""
+        rc = self.lib.fec_recover_packed_rs_dev(self.handle, _opt(d_data), _opt(d_parity), _opt(d_masks), num_groups, k, r,
+                                                packet_size, _opt(d_rebuilt), _opt(d_row_start), _opt(d_total),
+                                                _opt(d_status), stream)
+        _check(rc, "fec_recover_packed_rs_dev", self.lib)
+
+    def recover_packed_wide_dev(self, d_data, d_parity, d_masks, num_groups: int, k: int, r: int, packet_size: int,
+                                d_rebuilt, d_row_start, d_total=None, d_status=None, stream: Optional[int] = None) -> None:
+        """recover_packed_any_dev for what recover_wide_dev serves (k + r <= 256, masks as decode_wide_dev):
+        the rebuilt rows of all groups back to back, row starts and total as recover_packed_any_dev's."""
+        rc = self.lib.fec_recover_packed_wide_rs_dev(self.handle, _opt(d_data), _opt(d_parity), _opt(d_masks), num_groups,
+                                                     k, r, packet_size, _opt(d_rebuilt), _opt(d_row_start), _opt(d_total),
+                                                     _opt(d_status), stream)
+        _check(rc, "fec_recover_packed_wide_rs_dev", self.lib)
 
     def recover_gather_dev(self, d_shard_addrs, num_groups: int, k: int, r: int, packet_size: int, d_rebuilt,
                            d_status=None, d_masks_out=None, stream: Optional[int] = None) -> None:
@@ -703,6 +725,11 @@ WIDE_ENCODE_LAUNCH_FORMS = {32: "encode_scatter_wide"}
 # FEC_WIDE_ROWS_ALL), again their own; the classifies are 27 and 30, the slots passes decode_wide's (29).
 # Fields as build_records_wide's, decode_wide's and recover_scatter_wide's
 WIDE_DEEP_LAUNCH_FORMS = {33: "build_records_deep", 34: "decode_wide_deep", 35: "recover_scatter_wide_deep"}
+# the kernels of the packed recovers for every shape (csrc/fec_packed.hip; PackedLaunchForm), again their own:
+# the row prefix over four-word masks (the scan of the block sums between them is rows_scan_blocks, 10; the
+# one-word prefix is 9..11) and the consumers: first_item / items = groups of the call, aux = the first row
+# of the pass; recover_packed_wide reads a wide or a deep record
+PACKED_LAUNCH_FORMS = {36: "rows_block_sums_wide", 37: "rows_write_wide", 38: "recover_packed", 39: "recover_packed_wide"}
 LAUNCH_FIELDS = ("form", "k", "r", "nm", "nt", "off", "first", "pol", "direct", "scan", "tile", "grid", "block",
                  "first_item", "items", "aux")
 LAUNCH_TRACE_CAPACITY = 1 << 16
@@ -732,7 +759,7 @@ def launch_trace(lib: ctypes.CDLL, clear: bool = True) -> list:
         form = rec["form"]
         for names in (LAUNCH_FORMS, GATHER_LAUNCH_FORMS, GATHER_VAR_LAUNCH_FORMS, SCATTER_LAUNCH_FORMS,
                       SCATTER_ENCODE_LAUNCH_FORMS, PLAN_LAUNCH_FORMS, WIDE_LAUNCH_FORMS, WIDE_TABLE_LAUNCH_FORMS,
-                      WIDE_ENCODE_LAUNCH_FORMS, WIDE_DEEP_LAUNCH_FORMS):
+                      WIDE_ENCODE_LAUNCH_FORMS, WIDE_DEEP_LAUNCH_FORMS, PACKED_LAUNCH_FORMS):
             if form in names:
                 rec["form"] = names[form]
         out.append(rec)
